@@ -1,8 +1,21 @@
 #!/usr/bin/env python3
 """bench.py -- SVGD particle-updates/s on MI355X, with the MFMA roofline of the dominant kernel.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline needs: set-up, the W warm-up steps and the clock settle below, ONE timed loop of
+exactly K steps without any event in it, and the result line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step`, the config, the settle and window counts).  `--full` adds everything else described below: the roofline and
+stage split (a second, instrumented loop), the stall check and re-timing, the parity sample, the CPU baseline, the miss /
+fp32 / per-tile-distance variants, train_on_batch, the secondary workload, the other BASELINE configs and, on several
+ranks, the native-vs-torch communicator cross-check.
+
+--dump-outputs DIR: after the timed loop, what its last step handed its caller -- phi, the updated theta (rank 0's rows)
+and the bandwidth h2 -- is written as DIR/phi.npy, DIR/theta.npy, DIR/h2.npy (float32).  The inputs are seeded and the
+timed loop starts from the state the W warm-up steps and the first K settle steps left (the time-bounded rest of the
+settle phase is rolled back), so two runs with the same arguments compute the same steps.  Above 64 MB the two matrices
+are cut to a fixed, seeded sample of rows, listed in DIR/rows.npy (float64).
 
 A "step" is one full particle update given the score matrix G (resident in HBM): the fused C call
 stein_svgd_phi (row norms, operand scales and split planes -> distance pass on the 16-bit matrix cores with the
@@ -25,13 +38,15 @@ on), `frac` = achieved / peak (= `frac_algorithmic`).  The split path executes 3
 `frac_vs_fp32_mfma_peak` the algorithmic flops against the 157.3 TFLOP/s fp32-input MFMA peak (what an fp32 GEMM could
 reach at most); the strict fp32-input MFMA kernels are timed under `fp32_path`.
 
-Headline timing (one rank): `ms_per_step` / `value` come from a timed loop of exactly K steps that carries two HIP events per
-step (they bracket the contraction: `roofline.ms_per_launch`, measured live); `stage_ms`, `events_ms`, `wall_minus_events_ms` and
+Headline timing (one rank, --full): `ms_per_step` / `value` come from a timed loop of exactly K steps that carries two HIP events
+per step (they bracket the contraction: `roofline.ms_per_launch`, measured live); `stage_ms`, `events_ms`, `wall_minus_events_ms` and
 `instrumented_ms_per_step` come from a second loop of K steps with an event at every stage boundary.  An event between two kernels
 costs the step ~3 us of GPU time (scratch/event_cost.py): eight of them are 2.5 % of a C3 step and a quarter of a C2 step.
 Behind the W warm-up steps the same loop keeps running untimed until 80 ms of load have passed (`settle_steps` says how many
 steps that took): the chip's clock governor settles under this load in ~50 ms, and the 20 steps behind a 5-step warm-up alone
 are 8 % slower than every later block of 20 (scratch/step_trend.py); `first_block_ms_per_step` is that block, timed on the side.
+The particles, the optimizer state and the median predictor are then put back to where that first block left them, so the
+number of settle steps, which depends on the clock, never changes what the timed steps compute.  (Plain and --full runs alike.)
 
 wall_minus_events_ms (every timed entry): wall time per step minus the GPU time the HIP events of the same steps bracket;
 `host_stall_suspected` when the gap exceeds max(0.03 ms, 4 %) (a healthy C3 loop shows 0.012 ms).  A stalled timed loop
@@ -167,12 +182,14 @@ def parity_sample(torch, T_all, G_all, phi_local, row0, h2, n_rows=48):
 
 
 def run_workload(torch, dist, wl, device, rank, world, group, steps, warmup, clock_stages=True, x3=None, window=True,
-                 comm="torch", tile_distance=False, light=False, settle=False):
+                 comm="torch", tile_distance=False, light=False, settle=False, check=True, keep_outputs=False):
     """light (one rank): the timed loop carries only the two HIP events that bracket the contraction (the roofline's kernel time,
     measured live); the full stage split comes from a second loop of the same number of steps right behind it, with every stage
     event and the apply kernel's pair.  A HIP event between two kernels costs the step ~3 us of GPU time (scratch/event_cost.py:
     eight of them are 2.5 % of a C3 step and a quarter of a C2 step), so the loop whose wall time is the headline should not
-    be the one that carries them."""
+    be the one that carries them.
+    check: the finiteness check and the parity sample after the timed loop.  keep_outputs: device copies of what the timed
+    loop's last step produced (phi, theta, h2) under "outputs"."""
     from stein_amd import _lib
     from stein_amd.engine import SvgdEngine
     from stein_amd.optimizers import AdagradGradientDescent
@@ -232,6 +249,7 @@ def run_workload(torch, dist, wl, device, rank, world, group, steps, warmup, clo
         else:
             phi = eng.compute_phi(feed(), G, mark=(lambda s: None) if clock_stages else None)
             gd.apply_(theta, phi, eng.sqnorm)
+        return phi
 
     t_warm = time.perf_counter()
     for _ in range(warmup):
@@ -251,12 +269,21 @@ def run_workload(torch, dist, wl, device, rank, world, group, steps, warmup, clo
         torch.cuda.synchronize(device)
         first_block_ms = (time.perf_counter() - tb) / steps * 1e3
         settle_steps = steps
+        # how many steps the rest takes depends on the clock: roll the particles, the optimizer state and the median
+        # predictor (the workspace's SELECT section, carried from call to call) back to here before the timed loop
+        o = eng._offs[_lib.WS_SELECT]
+        saved = [(t, t.clone()) for t in (theta, gd.hist, eng.ws[o:o + _lib.SELECT_BYTES]) if t is not None]
+        saved_iters = gd.n_iters
         while (time.perf_counter() - t_warm) * 1e3 < SETTLE_MS and settle_steps < 2000:
             for _ in range(10):
                 step(False)
             settle_steps += 10
             torch.cuda.synchronize(device)
-    if world > 1 and clock_stages:
+        for t, copy in saved:
+            t.copy_(copy)
+        gd.n_iters = saved_iters
+        del saved
+    if world > 1 and (clock_stages or settle):
         # several ranks: a FIXED number of settle steps (every rank must take the same number of steps: each holds collectives)
         for _ in range(SETTLE_STEPS_MULTI):
             step(False)
@@ -266,9 +293,10 @@ def run_workload(torch, dist, wl, device, rank, world, group, steps, warmup, clo
     torch.cuda.synchronize(device)
     has_window = world == 1 and window and n > 160       # the one-kernel path (n <= 160) keeps no window state
     stats0 = eng.window_stats() if has_window else (0, 0)
+    last = None
     t0 = time.perf_counter()
     for _ in range(steps):
-        step(True)
+        last = step(True)
     torch.cuda.synchronize(device)
     if world > 1:
         dist.barrier(group=group)
@@ -279,6 +307,7 @@ def run_workload(torch, dist, wl, device, rank, world, group, steps, warmup, clo
         dist.all_reduce(te, op=dist.ReduceOp.MAX, group=group)
         elapsed = float(te.item())
     stats1 = eng.window_stats() if has_window else (0, 0)
+    outputs = dict(phi=last.clone(), theta=theta.clone(), h2=eng.h2.clone()) if keep_outputs and last is not None else None
     contract_live = instr_elapsed = None
     if light:
         per_call = _lib.timing_read(steps)
@@ -303,20 +332,22 @@ def run_workload(torch, dist, wl, device, rank, world, group, steps, warmup, clo
             stages["apply"] = stages.pop("end")
     # the GPU time the stage events account for, per step (one rank: every stage of the fused call + the apply kernel)
     events_ms = float(sum(stages.values())) if (world == 1 and clock_stages and stages) else None
-    finite = bool(torch.isfinite(theta).all().item())
-    # parity on sampled rows: one more call, untimed, no apply (theta and phi then belong together)
-    cur = feed()
-    phi = eng.compute_phi(cur, G)
-    torch.cuda.synchronize(device)
-    if world > 1:
-        T_all, G_all = eng.T_all.float(), eng.G_all.float()
-    else:
-        T_all, G_all = cur.float(), G.float()
-    relerr, nrows = parity_sample(torch, T_all, G_all, phi, row0, float(eng.h2.item()))
+    finite = relerr = nrows = None
+    if check:
+        finite = bool(torch.isfinite(theta).all().item())
+        # parity on sampled rows: one more call, untimed, no apply (theta and phi then belong together)
+        cur = feed()
+        phi = eng.compute_phi(cur, G)
+        torch.cuda.synchronize(device)
+        if world > 1:
+            T_all, G_all = eng.T_all.float(), eng.G_all.float()
+        else:
+            T_all, G_all = cur.float(), G.float()
+        relerr, nrows = parity_sample(torch, T_all, G_all, phi, row0, float(eng.h2.item()))
     crosscheck = None
     return dict(comm=eng.comm, comm_note=comm_note, comm_crosscheck=crosscheck, n=n, d=d, n_local=n_local, elapsed=elapsed, stages=stages, events_ms=events_ms, finite=finite, split=eng.split,
                 contract_live_ms=contract_live, instr_elapsed=instr_elapsed, settle_steps=settle_steps, first_block_ms=first_block_ms,
-                ws_bytes=eng.ws_bytes, T64=T64, G64=G64, x3=eng.x3, parity_relerr=relerr, parity_rows=nrows,
+                ws_bytes=eng.ws_bytes, T64=T64, G64=G64, x3=eng.x3, parity_relerr=relerr, parity_rows=nrows, outputs=outputs,
                 window=dict(timed_steps=stats1[0] - stats0[0], hits=stats1[1] - stats0[1]) if has_window else None)
 
 
@@ -528,70 +559,29 @@ def pmc_traffic(workload_key, x3):
         return None, None, None, {}
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
-    ap.add_argument("--n", type=int, default=0, help="override the workload's particle count (experiments)")
-    ap.add_argument("--d", type=int, default=0, help="override the workload's parameter count (experiments)")
-    ap.add_argument("--cpu-rows", type=int, default=16384, help="rows of the bounded CPU-baseline sample")
-    ap.add_argument("--cpu-rows-one-thread", type=int, default=2048, help="rows of the one-thread CPU sample (0: skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--comm", default="torch", choices=["torch", "native"],
-                    help="several ranks: who issues the timed steps' collectives (torch.distributed over RCCL, or the "
-                         "library's own RCCL communicator); the other way is run once afterwards as a cross-check")
-    ap.add_argument("--no-train-on-batch", action="store_true", help="skip the SteinSampler.train_on_batch entry (one GPU)")
-    ap.add_argument("--secondary", default="c5", help="also time this workload briefly (extra key); 'none' to skip")
-    ap.add_argument("--secondary-steps", type=int, default=10)
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the brief C1 / C2 / C4 timings (one GPU)")
-    ap.add_argument("--fp32-mfma", action="store_true", help="headline on the strict fp32-input MFMA kernels (x3=False)")
-    ap.add_argument("--no-variants", action="store_true", help="skip the miss-path and fp32-path timings (one GPU)")
-    args = ap.parse_args()
+DUMP_BYTES = 64 * 10**6
 
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs a GPU (there is no CPU path in stein_amd)")
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    if args.gpus != world:
-        if world == 1 and args.gpus > 1:
-            raise SystemExit("--gpus %d needs one process per GPU: launch with python -m torch.distributed.run "
-                             "--nproc-per-node %d ..." % (args.gpus, args.gpus))
-        raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
-    if os.environ.get("STEIN_REHEARSAL_ONE_GPU"):   # rehearse the multi-rank path with all ranks on one card
-        local_rank = 0
-    device = torch.device("cuda", local_rank)
-    torch.cuda.set_device(device)
-    dist, group = None, None
-    if world > 1:
-        import torch.distributed as dist
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        backend = os.environ.get("STEIN_DIST_BACKEND", "nccl")   # RCCL; "gloo" only for one-GPU rehearsals
-        if backend == "nccl":
-            dist.init_process_group(backend="nccl", device_id=device)
-        else:
-            dist.init_process_group(backend=backend)
-        group = dist.group.WORLD
 
-    import __graft_entry__ as ge
-    ge.build()
+def dump_outputs(path, outputs):
+    """outputs {name: device tensor} -> path/<name>.npy in float32.  When phi and theta together exceed DUMP_BYTES, both are
+    cut to the same fixed, seeded sample of rows (sorted), whose indices go to path/rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.float().cpu().numpy() for k, v in outputs.items()}
+    rows_n, d = arrays["phi"].shape
+    keep = min(rows_n, (DUMP_BYTES - 10**6) // (2 * 4 * d))      # (10^6 bytes left for h2, the row list and the headers)
+    if keep < rows_n:
+        rows = np.sort(np.random.default_rng(0).choice(rows_n, size=keep, replace=False))
+        arrays["phi"], arrays["theta"] = arrays["phi"][rows], arrays["theta"][rows]
+        arrays["rows"] = rows.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
-    wl = dict(WORKLOADS[args.workload])
-    if args.n or args.d:
-        wl["n"], wl["d"] = args.n or wl["n"], args.d or wl["d"]
-        wl["name"] = "custom n=%d d=%d fp32" % (wl["n"], wl["d"])
-    env_x3 = not args.fp32_mfma
-    hx3 = False if args.fp32_mfma else None
-    # (a stalled timed loop -- a launch thread that lost its core on a shared box -- is timed once more; `retimed` keeps the
-    # first run's numbers)
-    res, retimed = run_stable(torch, dist, wl, device, rank, world, group, args.steps, args.warmup, comm=args.comm, x3=hx3,
-                              light=True)
+
+def full_entries(torch, dist, args, wl, res, retimed, out, device, rank, world, group):
+    """--full: the roofline, stage split, checks and further runs the headline does not need, added to the line `out`"""
     n, d, nl = res["n"], res["d"], res["n_local"]
-    ms_per_step = res["elapsed"] / args.steps * 1e3
-    value = n * args.steps / res["elapsed"]
+    ms_per_step, value = out["ms_per_step"], out["value"]
+    env_x3 = not args.fp32_mfma
     nprod = (1 if wl.get("bf16") else 3) if res["x3"] else 1     # 16-bit MFMA products per operand pair
     # the contraction's mean launch time: from the two events that bracket it inside the timed loop (one rank), else from
     # the stage events
@@ -636,28 +626,11 @@ def main():
         }
     roof.update({"algorithmic_flops_per_launch": flops, "executed_flops_per_launch": nprod * flops, "ms_per_launch": k_ms,
                  "traffic": traffic, "traffic_source": traffic_src})
-    out = {
-        "metric": "SVGD particle-updates/sec",
-        "value": value,
-        "unit": "particle-updates/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "strong",
+    out.update({
         "scaling_note": ("`value` is BASELINE's roofline config (n=16384, d=256) sharded by rows over the ranks: at 8 ranks a rank holds "
                          "2048 rows, ~0.3 ms of kernels next to four latency-bound collectives, so this series saturates near 2-3x; the "
                          "configuration the north star's >= 6x at 8 GPUs refers to (n=131072, d=256) is timed in the same run under "
                          "`secondary`, one entry per N") if world > 1 else None,
-        "vs_baseline": None,
-        "dtype": "bf16" if wl.get("bf16") else "f32",
-        "data": "synthetic",
-        "config": {"workload": wl["name"], "n": n, "d": d, "rows_per_rank": nl,
-                   "optimizer": "adagrad lr=1e-3 alpha=0.9",
-                   "parallelism": "rows sharded x%d, all-gather(theta,G) + median (3 histogram all-reduces, or one window-table "
-                                  "all-reduce when the local block has >= 2^24 entries) + 1 scalar all-reduce" % world
-                   if world > 1 else "single GPU"},
         "element_updates_per_s": value * d,
         "pair_interactions_per_s": value * n,
         "roofline": roof,
@@ -670,7 +643,7 @@ def main():
         "finite": res["finite"],
         "parity_sample_relerr": res["parity_relerr"],
         "parity_sample_rows": res["parity_rows"],
-    }
+    })
     # the distance pass (north star: "achieved HBM GB/s on the distance pass"): one rank stores the 128 x 128 tiles on and
     # above the diagonal, a row block all of its tiles; 2 n_local n d algorithmic flops (half with the symmetry), x nprod executed
     d_ms = res["stages"].get("distance")
@@ -788,6 +761,109 @@ def main():
                                                            2048 if key == "c4" else ro["n"])
             del ro
         out["other_configs"] = others
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
+    ap.add_argument("--n", type=int, default=0, help="override the workload's particle count (experiments)")
+    ap.add_argument("--d", type=int, default=0, help="override the workload's parameter count (experiments)")
+    ap.add_argument("--cpu-rows", type=int, default=16384, help="rows of the bounded CPU-baseline sample")
+    ap.add_argument("--cpu-rows-one-thread", type=int, default=2048, help="rows of the one-thread CPU sample (0: skip)")
+    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--comm", default="torch", choices=["torch", "native"],
+                    help="several ranks: who issues the timed steps' collectives (torch.distributed over RCCL, or the "
+                         "library's own RCCL communicator); the other way is run once afterwards as a cross-check")
+    ap.add_argument("--no-train-on-batch", action="store_true", help="skip the SteinSampler.train_on_batch entry (one GPU)")
+    ap.add_argument("--secondary", default="c5", help="also time this workload briefly (extra key); 'none' to skip")
+    ap.add_argument("--secondary-steps", type=int, default=10)
+    ap.add_argument("--no-other-configs", action="store_true", help="skip the brief C1 / C2 / C4 timings (one GPU)")
+    ap.add_argument("--fp32-mfma", action="store_true", help="headline on the strict fp32-input MFMA kernels (x3=False)")
+    ap.add_argument("--no-variants", action="store_true", help="skip the miss-path and fp32-path timings (one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: roofline and stage split, stall check, parity sample, CPU baseline, "
+                         "variants, train_on_batch, secondary and other configs, communicator cross-check (the --no-* / "
+                         "--secondary / --cpu-rows options shape this part)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write phi, theta and h2 of the timed loop's last step as DIR/<name>.npy (float32)")
+    args = ap.parse_args()
+
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("bench.py needs a GPU (there is no CPU path in stein_amd)")
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    if args.gpus != world:
+        if world == 1 and args.gpus > 1:
+            raise SystemExit("--gpus %d needs one process per GPU: launch with python -m torch.distributed.run "
+                             "--nproc-per-node %d ..." % (args.gpus, args.gpus))
+        raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
+    if os.environ.get("STEIN_REHEARSAL_ONE_GPU"):   # rehearse the multi-rank path with all ranks on one card
+        local_rank = 0
+    device = torch.device("cuda", local_rank)
+    torch.cuda.set_device(device)
+    dist, group = None, None
+    if world > 1:
+        import torch.distributed as dist
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        backend = os.environ.get("STEIN_DIST_BACKEND", "nccl")   # RCCL; "gloo" only for one-GPU rehearsals
+        if backend == "nccl":
+            dist.init_process_group(backend="nccl", device_id=device)
+        else:
+            dist.init_process_group(backend=backend)
+        group = dist.group.WORLD
+
+    import __graft_entry__ as ge
+    ge.build()
+
+    wl = dict(WORKLOADS[args.workload])
+    if args.n or args.d:
+        wl["n"], wl["d"] = args.n or wl["n"], args.d or wl["d"]
+        wl["name"] = "custom n=%d d=%d fp32" % (wl["n"], wl["d"])
+    hx3 = False if args.fp32_mfma else None
+    keep = args.dump_outputs is not None and rank == 0
+    if args.full:
+        # (a stalled timed loop -- a launch thread that lost its core on a shared box -- is timed once more; `retimed` keeps the
+        # first run's numbers)
+        res, retimed = run_stable(torch, dist, wl, device, rank, world, group, args.steps, args.warmup, comm=args.comm, x3=hx3,
+                                  light=True, keep_outputs=keep)
+    else:
+        res = run_workload(torch, dist, wl, device, rank, world, group, args.steps, args.warmup, comm=args.comm, x3=hx3,
+                           clock_stages=False, settle=True, check=False, keep_outputs=keep)
+        retimed = None
+    if keep:
+        dump_outputs(args.dump_outputs, res.pop("outputs"))
+    n, d, nl = res["n"], res["d"], res["n_local"]
+    ms_per_step = res["elapsed"] / args.steps * 1e3
+    value = n * args.steps / res["elapsed"]
+    out = {
+        "metric": "SVGD particle-updates/sec",
+        "value": value,
+        "unit": "particle-updates/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "bf16" if wl.get("bf16") else "f32",
+        "data": "synthetic",
+        "config": {"workload": wl["name"], "n": n, "d": d, "rows_per_rank": nl,
+                   "optimizer": "adagrad lr=1e-3 alpha=0.9",
+                   "parallelism": "rows sharded x%d, all-gather(theta,G) + median (3 histogram all-reduces, or one window-table "
+                                  "all-reduce when the local block has >= 2^24 entries) + 1 scalar all-reduce" % world
+                   if world > 1 else "single GPU"},
+        "settle_steps": res["settle_steps"],
+        "window": res["window"],
+    }
+    if args.full:
+        full_entries(torch, dist, args, wl, res, retimed, out, device, rank, world, group)
+    del res
     # the commit the working tree was at: from git where there is one, else from the stamp build() leaves beside the library
     # (the GPU boxes get a snapshot without .git)
     commit = None
@@ -802,7 +878,7 @@ def main():
         except OSError:
             commit = None
     out["commit"] = commit
-    if world > 1 and str(dist.get_backend(group)) == "nccl" and not os.environ.get("STEIN_NO_CROSSCHECK"):
+    if args.full and world > 1 and str(dist.get_backend(group)) == "nccl" and not os.environ.get("STEIN_NO_CROSSCHECK"):
         # Last, and guarded: the library's own communicator has only ever run on one-rank groups before this machine.  If the
         # native-vs-torch cross-check hangs (a mismatched collective has no timeout in RCCL), a watchdog prints the line that
         # is already complete -- the timed numbers above do not depend on it -- and ends the process.

@@ -1,11 +1,12 @@
 #!/bin/bash
 # FETCH_SIZE / WRITE_SIZE / MFMA-busy counters of a bench workload's kernels: bash scratch/pmc_cfg.sh <tag> <workload>
 set -e -o pipefail
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 TAG=$1; WL=$2
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python3 $GRAFT_REPO_ROOT/bench.py --workload $WL --steps 6 --warmup 4 --no-cpu-baseline --secondary none --no-other-configs --no-variants --no-train-on-batch"
+B="python3 $REPO/bench.py --full --workload $WL --steps 6 --warmup 4 --no-cpu-baseline --secondary none --no-other-configs --no-variants --no-train-on-batch"
 for C in FETCH_SIZE WRITE_SIZE "SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES"; do
   N=$(echo $C | tr ' ' '+')
   rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/$N -o x -- $B > $OUT/$N.log 2>&1

@@ -6,8 +6,8 @@ out=gpurun_out/$tag
 mkdir -p $out
 python -m pytest tests -m gpu -x -q > $out/gputest.log 2>&1; echo "pytest rc=$?" >> $out/gputest.log
 tail -4 $out/gputest.log
-python bench.py > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"
-python bench.py --workload c2 --steps 200 --secondary none --no-other-configs --no-variants --no-cpu-baseline > $out/bench_c2_200.json 2> $out/bench_c2.err; echo "bench c2 rc=$?"
+python bench.py --full > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"
+python bench.py --full --workload c2 --steps 200 --secondary none --no-other-configs --no-variants --no-cpu-baseline > $out/bench_c2_200.json 2> $out/bench_c2.err; echo "bench c2 rc=$?"
 python - <<PY
 import json
 b = json.load(open("$out/bench.json"))

@@ -48,3 +48,27 @@ def test_headline_gap_describes_the_instrumented_loop_and_flags_a_slow_timed_loo
     # several ranks (no second loop): the plain gap fields plus the settle count
     multi = bench.headline_gap(0.30, dict(instr_elapsed=None, events_ms=None, settle_steps=60), 20)
     assert multi["settle_steps"] == 60 and multi["host_stall_suspected"] is None
+
+
+def test_dump_outputs_keeps_small_outputs_whole_and_samples_large_ones(tmp_path):
+    """--dump-outputs: float32 .npy files; C3 (2 x 16 MB) is written whole, C4 (2 x 66 MB) is cut to the same seeded rows of phi
+    and theta, listed in rows.npy, everything within 64 MB."""
+    import numpy as np
+    import torch
+    for n, d, whole in ((16384, 256, True), (8192, 2001, False)):
+        phi = torch.arange(n, dtype=torch.float32)[:, None].repeat(1, d)
+        out, again = tmp_path / str(d), tmp_path / ("%d_again" % d)
+        for where in (out, again):
+            bench.dump_outputs(str(where), {"phi": phi, "theta": phi + 0.5, "h2": torch.tensor([3.0], dtype=torch.float64)})
+        files = {f: np.load(out / f) for f in os.listdir(out)}
+        assert sorted(os.listdir(again)) == sorted(files)
+        assert all(np.array_equal(a, np.load(again / f)) for f, a in files.items())      # seeded: the same rows every time
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert sum(os.path.getsize(out / f) for f in files) <= 64 * 10**6
+        assert files["h2.npy"].dtype == np.float32 and files["h2.npy"].tolist() == [3.0]
+        if whole:
+            assert sorted(files) == ["h2.npy", "phi.npy", "theta.npy"] and files["phi.npy"].shape == (n, d)
+            continue
+        rows = files["rows.npy"]
+        assert len(np.unique(rows)) == len(rows) == files["phi.npy"].shape[0] > n // 3
+        assert np.array_equal(files["phi.npy"][:, 0], rows) and np.array_equal(files["theta.npy"][:, 7], rows + 0.5)

@@ -1,24 +1,29 @@
 """GPU: bench.py prints ONE JSON line with the keys the driver's contract names (a short run of the C2 workload, which
-takes a second; the default run is the same code on C3)."""
+takes a second; the default run is the same code on C3).  A plain run carries the headline only; --full adds the rest."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 
 
-def test_bench_line_has_the_contract_keys(cuda):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c2", "--steps", "4", "--warmup", "3",
-           "--secondary", "none", "--no-other-configs", "--no-variants"]
+def run_bench(*extra):
+    """bench.py on C2, 4 timed steps behind 3 warm-up steps -> its one JSON line"""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c2", "--steps", "4", "--warmup", "3", *extra]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, res.stdout                                   # exactly one line on stdout
-    b = json.loads(lines[0])
+    return json.loads(lines[0])
+
+
+def test_bench_line_has_the_contract_keys(cuda):
+    b = run_bench("--full", "--secondary", "none", "--no-other-configs", "--no-variants")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in b, key
@@ -73,3 +78,28 @@ def test_train_on_batch_entry(cuda):
     assert ent["finite"] and ent["ms_per_step"] > 0 and ent["window"]["timed_steps"] == 6
     assert abs(ent["wall_minus_events_ms"] - (ent["ms_per_step"] - ent["events_ms"])) < 2e-4
     assert 0 <= ent["window"]["hits"] <= 6
+
+
+def test_plain_run_times_the_headline_and_dumps_its_last_step(cuda, tmp_path):
+    """A plain run: the headline keys over exactly the steps asked for, none of --full's entries.  --dump-outputs writes what the
+    timed loop's last step produced; a --full run of the same arguments (events in its timed loop, a second loop and the
+    parity call behind it, possibly re-timed) dumps the very same step, bit for bit: the settle phase's length never leaks
+    into what is computed."""
+    b = run_bench("--dump-outputs", str(tmp_path / "plain"))
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+        assert key in b, key
+    assert b["steps"] == 4 and b["warmup"] == 3 and b["dtype"] == "bf16" and b["higher_is_better"] is True
+    assert b["window"]["timed_steps"] == 4
+    assert abs(b["value"] - b["config"]["n"] * 1e3 / b["ms_per_step"]) <= 1e-6 * b["value"]
+    for key in ("roofline", "cpu_baseline", "stage_ms", "instrumented_ms_per_step", "parity_sample_relerr", "retimed",
+                "train_on_batch", "secondary", "other_configs", "miss_path"):
+        assert key not in b, key
+    run_bench("--full", "--secondary", "none", "--no-other-configs", "--no-variants", "--no-cpu-baseline", "--no-train-on-batch",
+              "--dump-outputs", str(tmp_path / "full"))
+    n, d = b["config"]["n"], b["config"]["d"]
+    assert sorted(os.listdir(tmp_path / "plain")) == ["h2.npy", "phi.npy", "theta.npy"]
+    for name, shape in (("phi", (n, d)), ("theta", (n, d)), ("h2", (1,))):
+        plain, full = np.load(tmp_path / "plain" / (name + ".npy")), np.load(tmp_path / "full" / (name + ".npy"))
+        assert plain.dtype == np.float32 and plain.shape == shape and np.isfinite(plain).all(), name
+        assert np.array_equal(plain, full), name
+    assert float(np.load(tmp_path / "plain" / "h2.npy")[0]) > 0
