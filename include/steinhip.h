@@ -367,11 +367,12 @@ int stein_cast_f32_to_bf16(const float* src, void* dst, int64_t count, void* str
  * was computing (the step's bandwidth: the reference's own failure value, compute_median.py:4-16 of identical particles)
  * and raises a per-device word in page-locked host memory; stein_svgd_phi and stein_apply_* look at that word -- a plain
  * host read, no synchronisation -- before they queue anything and return STEIN_E_HIP once, naming the kernel.  Today one
- * kernel can raise it: the one-launch radix select of the fused call (512 < n <= 4096), whose level barriers are
+ * kernel can raise it: the one-launch radix select of the fused call (every n > 512), whose level barriers are
  * bounded although they cannot deadlock by construction.
  * stein_take_device_error: the same check on demand (0, or STEIN_E_HIP once).
  * Test hooks (per calling thread, no effect on results): stein_debug_hist_all_grid(blocks) launches that kernel with
- * `blocks` workgroups instead of 512 (0 = default; any grid >= 1 gives the same median: tests/test_gpu_spec.py);
+ * `blocks` workgroups instead of one per virtual workgroup (nvb: 512 up to n = 4096, above that as many as the chip
+ * holds at once; 0 = default; any grid >= 1 gives the same median: tests/test_gpu_spec.py);
  * stein_debug_raise_device_error raises the current device's word as a kernel would. */
 int stein_take_device_error(void);
 int stein_debug_hist_all_grid(int blocks);

@@ -130,13 +130,10 @@ struct SpecState {
   u32 n_hits;     // ... and how many of them came from the window: the hit rate a harness reports (bench.py)
 };
 static_assert(sizeof(SpecState) == 64, "SpecState must stay 64 bytes");
-// Third 64-byte block of the SELECT section (fused call only): "last workgroup out" tickets that let a kernel's last
-// workgroup do what used to be a one-workgroup follow-up launch (scales after the column maxima, the final resolve after
-// the level-2 histogram, the |phi|^2 sum after k_phi_finish's partials when that kernel has at most 512 workgroups -- with
-// 1024 of them waiting on their stores the ticket cost more than the launch it saved).  Zeroed by the fused call's first
-// kernel; each ticket also resets itself.
+// Third 64-byte block of the SELECT section (fused call only), zeroed by the fused call's first kernel.  (The completion
+// counts that find a kernel's last workgroup live in HistSync: tree_report_done.)
 struct FuseState {
-  u32 done_colmax, done_finish;
+  u32 pad0[2];
   u32 gave_up;     // k_hist_all: a bounded wait ran out (cannot happen by construction; the bandwidth becomes NaN and the host is told)
   u32 pad[13];
 };
@@ -165,6 +162,11 @@ struct HistSync {
 };
 // thread 0 of a workgroup whose results have been acknowledged: is this the last of `nblocks` workgroups to report?  A
 // two-level tree (64 leaves, one top): no counter sees more than nblocks / 64 returning atomics.  Counters zero at launch.
+// The 8 XCDs have private L2s, so a device-wide fence per workgroup would write back and invalidate a whole L2 every time
+// (measured: 3x the kernel time).  Instead the results that cross workgroups must be WRITTEN with device-scope atomics
+// (atomicAdd / atomicMax / __hip_atomic_store) and READ with load_fresh -- those go to the coherent level themselves --
+// and only the order matters: every wave waits until its outstanding memory operations have been acknowledged
+// (s_waitcnt vmcnt(0); a workgroup barrier alone does not) and the workgroup meets at a barrier before thread 0 reports.
 __device__ __forceinline__ bool tree_report_done(HistSync::Leaf* leaf, HistSync::Top* top, u32 id, u32 nblocks) {
   const u32 c = id % HS_CLASSES;
   const u32 quota = (nblocks - c + HS_CLASSES - 1) / HS_CLASSES;
@@ -195,25 +197,6 @@ __device__ __forceinline__ float key_f32(u32 k) {
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 
-// "Last workgroup out".  Call once per workgroup, by every thread, after the workgroup's results have been issued: true
-// in exactly one workgroup, the last to arrive.  The 8 XCDs have private L2s, so a device-wide fence per workgroup would
-// write back and invalidate a whole L2 every time (measured: 3x the kernel time).  Instead the results that cross
-// workgroups must be WRITTEN with device-scope atomics (atomicAdd / atomicMax) and READ with load_fresh --
-// those go to the coherent level themselves -- and only the order matters here: every wave waits until its outstanding
-// memory operations have been acknowledged (s_waitcnt vmcnt(0); a workgroup barrier alone does not) before thread 0
-// draws the ticket.  The counter is left at zero.
-__device__ __forceinline__ bool last_workgroup_out(u32* counter, u32 nblocks) {
-  __shared__ u32 s_last;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0 && threadIdx.y == 0) {
-    const u32 last = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nblocks - 1u ? 1u : 0u;
-    if (last) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = last;
-  }
-  __syncthreads();
-  return s_last != 0u;
-}
 __device__ __forceinline__ u64 load_fresh(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ u32 load_fresh(const u32* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 

@@ -28,14 +28,7 @@
 #include <type_traits>
 #include "stein_x3.h"
 #include "stein_x3_dev.h"
-#define STEIN_ABLATE_DPANEL
-#include "stein_ablate.h"   // DP_STAMP* / DP_STORE16: hooks of the diagnostic builds (nothing in the shipped library)
 
-#ifdef STEIN_DP_NOPRIO   // (A/B hook: the kernels without their issue priorities)
-#define DP_SETPRIO(p) do {} while (0)
-#else
-#define DP_SETPRIO(p) __builtin_amdgcn_s_setprio(p)
-#endif
 constexpr int DP_THREADS = 512;        // 8 waves: two per SIMD
 constexpr int DP_RING = 4;             // k tiles of the strip operand in flight per wave
 constexpr int DP_PITCH = 144;          // bytes per staged row: 32 floats + 16 (conflict-free 16-byte writes down a column)
@@ -90,14 +83,10 @@ __device__ __forceinline__ void dp_step(const unsigned char* pk /* panel k tile 
   for (int s = 0; s < NP; ++s) b[0][s] = *reinterpret_cast<const u32x4*>(pk + s * XPLANE);
 #pragma unroll
   for (int ib = 0; ib < 8; ++ib) {
-#ifdef STEIN_DP_ABL_NOPANEL   // (timing-only ablation: one LDS fragment read per k tile instead of eight)
-    b[(ib + 1) & 1][0] = b[ib & 1][0]; b[(ib + 1) & 1][1] = b[ib & 1][1];
-#else
     if (ib + 1 < 8) {
 #pragma unroll
       for (int s = 0; s < NP; ++s) b[(ib + 1) & 1][s] = *reinterpret_cast<const u32x4*>(pk + s * XPLANE + (ib + 1) * 1024);
     }
-#endif
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int jb = 0; jb < 2; ++jb) acc[ib][jb] = x3_products16<NP>(a[jb], b[ib & 1], acc[ib][jb]);
@@ -329,10 +318,6 @@ __global__ __launch_bounds__(DP_THREADS, 2) void k_distance_panel(const u16* __r
   u32x4 ring[DP_RING][2][3];
   f32x4g rj[2];
   float ri[8];
-#ifdef STEIN_DP_ABL_NOSTREAM
-  int abl_requests = 0;
-#endif
-  DP_STAMP_DECL;
 
   for (; unit < U; unit += unit_step)
   for (int half = 0; half < (SYM ? 2 : 1); ++half) {
@@ -365,7 +350,6 @@ __global__ __launch_bounds__(DP_THREADS, 2) void k_distance_panel(const u16* __r
       if (t == 0) *dealer = (u32)(sb + 16);
     }
     __syncthreads();
-    DP_STAMP(4);
 
     // ---- the wave's strips: sb + w and sb + 8 + w first, then whichever strip of the piece is next (a counter in LDS deals
     // them: at equal priority the older wave of a SIMD wins every issue arbitration, and dealt statically the younger one
@@ -385,14 +369,6 @@ __global__ __launch_bounds__(DP_THREADS, 2) void k_distance_panel(const u16* __r
       // a diagnostic build with more SGPR pressure sent its atomics to address 0).
       auto request = [&](const u16* sbase, int kt, u32x4 (&slot)[2][3]) {
         const u16* src = sbase + (size_t)(kt < ntk ? kt : ntk - 1) * 3 * XTILE_E;   // past the end: a harmless re-read keeps the counts
-#ifdef STEIN_DP_ABL_NOSTREAM   // (timing-only ablation: the strip operand is fetched for the wave's first eight k tiles only;
-        // after that the ring keeps those -- real -- values: MFMA power depends on the data, zeros would flatter it)
-        if (abl_requests >= 8) {
-          asm volatile("" : "+v"(slot[0][0]), "+v"(slot[0][1]), "+v"(slot[1][0]), "+v"(slot[1][1]) : "s"(src));
-          return;
-        }
-        ++abl_requests;
-#endif
         if constexpr (NP == 2) {
           asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %4, %6\n\tglobal_load_dwordx4 %1, %5, %6\n\t"
                        "global_load_dwordx4 %2, %4, %6 offset:1024\n\tglobal_load_dwordx4 %3, %5, %6 offset:1024"
@@ -414,7 +390,6 @@ __global__ __launch_bounds__(DP_THREADS, 2) void k_distance_panel(const u16* __r
       for (int u = 0; u < DP_RING; ++u) request(cur, u, ring[u]);
       bool regular = false;                        // the previous epilogue issued exactly 16 stores + 2 norm loads
       for (;;) {
-        DP_STRIP_BEGIN;
         u32 drawn = 0u;                            // the strip after s1
         if (lane == 0) drawn = __hip_atomic_fetch_add(dealer, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         const int s2 = __builtin_amdgcn_readfirstlane((int)drawn);
@@ -431,61 +406,42 @@ __global__ __launch_bounds__(DP_THREADS, 2) void k_distance_panel(const u16* __r
         // measurements: another wave's plain VALU, scalar and LDS instructions cost the matrix pipe nothing
         // (scratch/coissue_probe.hip), and with / without these two s_setprio the pass takes 0.2034 / 0.2027 ms unsettled and
         // 0.1877 / 0.1891 ms settled (scratch/ab_fused.py): inside the noise, kept because it never loses.
-        DP_SETPRIO(2);
+        __builtin_amdgcn_s_setprio(2);
         for (int g = 0; g < groups; ++g) {
           const bool last = g + 1 >= groups;
 #pragma unroll
           for (int u = 0; u < DP_RING; ++u) {
             const int kt = g * DP_RING + u;
-            DP_STAMP(2);
             // (the looser wait first, unconditionally: every path from a request to its use then passes a wait, which is
             // what stein_amd/csrc/isa_check.py verifies on the assembly)
             stream_wait<W_EARLY>();
             if (!(g == 0 && regular)) stream_wait<W_LATE>();
-            DP_STAMP(0);
             if (kt < ntk) dp_step<NP>(panel + kt * NP * XPLANE + aoff, ring[u], acc);
-            DP_STAMP(1);
             request(last ? nxt : cur, last ? u : kt + DP_RING, ring[u]);
           }
         }
         // the strip's column norms were requested a whole k loop ago: everything but the last four requests of this loop is
         // younger than they are (with more than one group of k tiles the loop's own waits have covered them already and
         // this one costs nothing)
-        DP_STAMP(2);
-        DP_SETPRIO(0);
+        __builtin_amdgcn_s_setprio(0);
         stream_wait<DP_RING * LPS>();
         // ---- epilogue of the strip ----------------------------------------------------------------------------------------
-#ifdef STEIN_DP_ABL_NOEPI   // (timing-only ablation: no epilogue at all; the accumulators are kept alive)
-        const bool diag = false;
-#pragma unroll
-        for (int ib = 0; ib < 8; ++ib)
-#pragma unroll
-          for (int jb = 0; jb < 2; ++jb) asm volatile("" :: "v"(acc[ib][jb]));
-#else
 #define DP_RI(ib) ri[ib]
 #define DP_EPI_FAST
 #include "stein_dpanel_epilogue.inc"
 #undef DP_EPI_FAST
 #undef DP_RI
-#endif
         regular = !diag;
         if (window && sx.qn >= (u32)(DP_QCAP / 2)) { dp_flush(sx, spec, spec_buf, lane); regular = false; }
         request_norms(snext);                      // ("memory": the strip's stores are issued before this point)
         cur = nxt;
-        if (diag) { DP_STAMP(6); DP_STAMP_COUNT(7); } else DP_STAMP(3);
-        DP_STAMP_COUNT(5);
-        DP_STRIP_END(2 * unit + half, s);
         if (!more) break;
         s = s1;
         s1 = s2;
       }
       stream_wait<0>();                            // the trailing re-reads land before their registers move on
     }
-    DP_STAMP(4);
   }
-  DP_STAMP_FLUSH(lane);
-  DP_STAMP_WG(p, w, lane);
-  DP_SLOW_FLUSH(p, w, lane);
   DP_HIST_FINISH
   if (window) {
     dp_flush(sx, spec, spec_buf, lane);

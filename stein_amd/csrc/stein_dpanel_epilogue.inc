@@ -45,27 +45,21 @@
               for (int jb = 0; jb < 2; ++jb)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[jb][e] = __builtin_fmaf(acc[ib][jb][e], nts, rib + rj[jb][e]);
-#ifndef STEIN_DP_ABL_NOCOUNT   // (timing-only ablation: no window counting)
               if (MODE == 1) dp_count8(sx, v, wt, lane);
-#endif
               if (MODE == 2) { dp_hist4(hx, v[0]); dp_hist4(hx, v[1]); }
-#ifdef STEIN_DP_ABL_NOSTAGE   // (timing-only ablation: the values go out in the accumulator layout, no LDS round trip)
-              const float4 x0 = make_float4(v[0][0], v[0][1], v[0][2], v[0][3]), x1 = make_float4(v[1][0], v[1][1], v[1][2], v[1][3]);
-#else
 #pragma unroll
               for (int jb = 0; jb < 2; ++jb)
                 *reinterpret_cast<float4*>(stg + li * DP_PITCH + jb * 64 + lq * 16) = make_float4(v[jb][0], v[jb][1], v[jb][2], v[jb][3]);
               const float4 x0 = *reinterpret_cast<const float4*>(stg + sr * DP_PITCH + sc4 * 4);
               const float4 x1 = *reinterpret_cast<const float4*>(stg + (8 + sr) * DP_PITCH + sc4 * 4);
-#endif
               if (ib > 0) {
-                DP_STORE16(dt + (ib - 1) * 512 + lane * 4, px0);          // rows 16 (ib - 1) .. + 7: 1 KB contiguous
-                DP_STORE16(dt + (ib - 1) * 512 + 256 + lane * 4, px1);    // rows 16 (ib - 1) + 8 .. + 15
+                *reinterpret_cast<float4*>(dt + (ib - 1) * 512 + lane * 4) = px0;          // rows 16 (ib - 1) .. + 7: 1 KB contiguous
+                *reinterpret_cast<float4*>(dt + (ib - 1) * 512 + 256 + lane * 4) = px1;    // rows 16 (ib - 1) + 8 .. + 15
               }
               px0 = x0; px1 = x1;
             }
-            DP_STORE16(dt + 7 * 512 + lane * 4, px0);
-            DP_STORE16(dt + 7 * 512 + 256 + lane * 4, px1);
+            *reinterpret_cast<float4*>(dt + 7 * 512 + lane * 4) = px0;
+            *reinterpret_cast<float4*>(dt + 7 * 512 + 256 + lane * 4) = px1;
           };
           regular_strip(std::integral_constant<int, 1>{});
         } else
@@ -95,8 +89,8 @@
           const float4 x0 = *reinterpret_cast<const float4*>(stg + sr * DP_PITCH + sc4 * 4);
           const float4 x1 = *reinterpret_cast<const float4*>(stg + (8 + sr) * DP_PITCH + sc4 * 4);
           if (!diag) {
-            DP_STORE16(dt + ib * 512 + lane * 4, x0);          // rows 16 ib .. + 7: 1 KB contiguous
-            DP_STORE16(dt + ib * 512 + 256 + lane * 4, x1);    // rows 16 ib + 8 .. + 15
+            *reinterpret_cast<float4*>(dt + ib * 512 + lane * 4) = x0;          // rows 16 ib .. + 7: 1 KB contiguous
+            *reinterpret_cast<float4*>(dt + ib * 512 + 256 + lane * 4) = x1;    // rows 16 ib + 8 .. + 15
           } else if (ib < 2 * d4 + 2) {                                          // (blocks below the diagonal block: nothing)
 #pragma unroll
             for (int h = 0; h < 2; ++h) {

@@ -27,24 +27,6 @@ static inline int small_chunk(int64_t n, int64_t d) {
   return (int)(ck < dr ? ck : dr);
 }
 
-#ifdef STEIN_STAMPS   // diagnostic build only (scratch/small_stamps.py): cycles per phase of workgroup 0
-__device__ unsigned long long g_small_stamps[16];
-extern "C" int stein_debug_small(unsigned long long* out) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_small_stamps), sizeof(unsigned long long) * 16) == hipSuccess ? 0 : -1;
-}
-#define SST(k)                                                                     \
-  do {                                                                             \
-    __syncthreads();                                                               \
-    if (threadIdx.x == 0 && blockIdx.x == 0) {                                     \
-      const unsigned long long now_ = __builtin_amdgcn_s_memtime();                \
-      g_small_stamps[k] = now_ - sst_last;                                         \
-      sst_last = now_;                                                             \
-    }                                                                              \
-  } while (0)
-#else
-#define SST(k) do {} while (0)
-#endif
-
 __global__ __launch_bounds__(SM_THREADS) void k_svgd_small(const float* __restrict__ T, const float* __restrict__ G, int n,
                                                            int d, float ln_n, float* __restrict__ phi,
                                                            float* __restrict__ h2_out, double* __restrict__ sqpart,
@@ -60,9 +42,6 @@ __global__ __launch_bounds__(SM_THREADS) void k_svgd_small(const float* __restri
   __shared__ float s_h2;
   __shared__ double s_red[SM_THREADS / 64];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-#ifdef STEIN_STAMPS
-  unsigned long long sst_last = __builtin_amdgcn_s_memtime();
-#endif
 
   // ---- S = T T^T, theta staged SM_CK columns at a time.  Thread (bi, bj) = (t / 32, t % 32) owns the entries
   //      (bi + 32 r, bj + 32 s), r, s < R = ceil(n / 32): 2 R LDS reads feed R^2 FMAs per column, the row reads are
@@ -149,7 +128,6 @@ __global__ __launch_bounds__(SM_THREADS) void k_svgd_small(const float* __restri
     case 4: distances(std::integral_constant<int, 4>()); break;
     default: distances(std::integral_constant<int, 5>()); break;
   }
-  SST(0);   // distances (+ row norms, level-0 histogram)
   // this workgroup's theta / score columns for the phi stage: requested now, so the loads fly during the median
   const int cw0 = blockIdx.x * SM_COLS;
   const int ncols = min(SM_COLS, d - cw0);
@@ -223,7 +201,6 @@ __global__ __launch_bounds__(SM_THREADS) void k_svgd_small(const float* __restri
     }
     if (t == 0) s_div = s_prefix[0] != s_prefix[1] ? 1u : 0u;
     __syncthreads();
-    SST(1 + level);   // median levels (level 0: locate only)
   }
   if (t == 0) {
     const float lo = key_f32(s_prefix[0]), hi = key_f32(s_prefix[1]);
@@ -234,7 +211,6 @@ __global__ __launch_bounds__(SM_THREADS) void k_svgd_small(const float* __restri
   }
   __syncthreads();
   const float h2 = s_h2;
-  SST(4);   // bandwidth
   // ---- K in place (exp(-D / h2 / 2) = exp2(kc D), as the tiled kernels form it), rowsum(K): the 32 lanes that share
   //      bi hold 32 columns of a row, so a row's sum is this thread's R entries plus one shuffle reduction (a fixed order) ----
   const float kc = -1.44269504088896341f / (2.f * h2);
@@ -256,7 +232,6 @@ __global__ __launch_bounds__(SM_THREADS) void k_svgd_small(const float* __restri
     if (bj == 0 && i < n) rn[i] = s;
   }
   __syncthreads();
-  SST(5);   // K + rowsum
   // ---- phi for this workgroup's SM_COLS columns.  Their theta / score columns are staged in LDS first (the chunk
   //      buffer and the histograms are free now): read from global memory inside the j loop, every iteration paid
   //      the L2 latency (30+ us at n = 100).  thread -> (row i, column c), lanes along c ----
@@ -342,7 +317,6 @@ __global__ __launch_bounds__(SM_THREADS) void k_svgd_small(const float* __restri
   else if (n <= 8 * (SM_THREADS / 64)) phi_cols(std::integral_constant<int, 8>());
   else phi_cols(std::integral_constant<int, 10>());
   static_assert(SM_MAXN <= 10 * (SM_THREADS / 64), "rows per wave");
-  SST(6);   // stage + phi
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
   if (lane == 0) s_red[wave] = sq;

@@ -61,8 +61,6 @@ constexpr int PEXP_H2 = 14;   // KIND 2: P = exp2(c D + 14), in (0, 2^14] (fp16 
 template <int KIND> struct SplitTraits { static constexpr int pexp = KIND == 2 ? PEXP_H2 : 0; };
 
 #include <type_traits>
-#define STEIN_ABLATE_X3
-#include "stein_ablate.h"   // STAMP / X3_STAMP_*: phase-stamp hooks of the diagnostic builds (nothing in the shipped library)
 
 __device__ __forceinline__ int xswz(int row, int chunk) { return (chunk ^ ((row >> 2) & 3)) * 16; }
 // LDS image of a P plane in the contraction: [128 rows][64 B], chunk c of row r at 16 * (c ^ g((r >> 2) & 3)) with
@@ -422,33 +420,27 @@ __global__ __launch_bounds__(NTHREADS, 3) void k_distance_x3(const u16* __restri
   // the next k tile's operands are prefetched into registers under the MFMAs (a second register set, two tiles
   // ahead, bought nothing and costs the third workgroup per CU)
   u32x4 ra[6], rb[6];
-  X3_STAMP_DECL;
   t3_load<NP>(pa0, pa1, 0, ra);
   t3_load<NP>(pb0, pb1, 0, rb);
   for (int kt = 0; kt < ntk; ++kt) {
     x3_store_swz<NP>(As, t, ra);
     x3_store_swz<NP>(Bs, t, rb);
-    STAMP(0);   // waiting for the tile's loads + LDS stores
     __syncthreads();
-    STAMP(1);   // barrier
     if (kt + 1 < ntk) {
       t3_load<NP>(pa0, pa1, kt + 1, ra);
       t3_load<NP>(pb0, pb1, kt + 1, rb);
     }
     x3_mma_tile<NP>(As, Bs, wy, wx, lane, acc);
-    STAMP(2);   // load issue + fragment reads + MFMAs
     __syncthreads();
-    STAMP(1);
   }
   // SYM: only the tiles on and above the diagonal are stored (the contraction reads the others transposed)
   distance_epilogue<SYM, false>(acc, reinterpret_cast<u32*>(smem), D, n, n_local, ldD, tile_m, tile_n, hist0, pf,
                                 two_s_v, spec, spec_buf);
-  X3_STAMP_FLUSH_DISTANCE;
 }
 
 // ------------------------------------------------------------------------------------------------
 // k_phi_x3fs: the contraction, warp-specialised, V fragments streamed straight from L2.
-//   History (phase stamps, STEIN_STAMPS build): a monolithic kernel (every wave stages, then every wave multiplies)
+//   History (measured with per-phase cycle stamps): a monolithic kernel (every wave stages, then every wave multiplies)
 //   fell into lockstep phases; a producer/consumer split that staged P AND the V tiles through LDS was bound by its
 //   producers (64 KB of loads per k tile accepted at the vector-L1 rate while they also ran the exp/split VALU work).
 //   Here a 768-thread workgroup owns a 128 x 256 tile of [K.G | K.theta]:
@@ -516,14 +508,11 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
   int cb, tile_m;
   const int plane = cblocks * tiles_m, l2 = logical % plane;
   const int z = logical / plane;
-#ifndef STEIN_PHI_ROWMAJOR_MAP   // (diagnostic builds: the plain order everywhere, for same-box A/B runs)
   if (cblocks > 4 && (cblocks & 3) == 0 && (tiles_m & 7) == 0) {
     const int sb = l2 >> 5, in = l2 & 31, cgroups = cblocks >> 2;
     cb = (sb % cgroups) * 4 + (in & 3);
     tile_m = (sb / cgroups) * 8 + (in >> 2);
-  } else
-#endif
-  {
+  } else {
     cb = l2 % cblocks;
     tile_m = l2 / cblocks;
   }
@@ -740,7 +729,6 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
       }
     };
     auto jt = [&](int tile) { return jbeg + tile * BK; };   // tile index -> first column (jbeg % 32 == 0)
-    X3_STAMP_DECL;
     // A pipeline stage holds FS_KT consecutive k tiles, so the workgroup synchronises once per FS_KT tiles.  Tile
     // parity picks the register set (X even, Y odd); a tile's loads are issued two tiles ahead, right after the set is free.
 #pragma unroll
@@ -753,9 +741,7 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
       for (int u = 0; u < FS_KT; ++u) {
         const int tile_u = tile_at(st, u), next_u = tile_at(st + 1, u);
         if (tile_u < ntile) {
-          STAMP(0);
           wait_loads(st * FS_KT + u, rd[u % PD]);   // (tiles are requested in visit order: position = st * FS_KT + u)
-          STAMP(1);   // diagnostic builds: how long the producer waited for this tile's D loads
           if (tr_now) produce_tr(buf + u * FS_KTB, rd[u % PD]);
           else produce(jt(tile_u), buf + u * FS_KTB, rd[u % PD]);
         }
@@ -766,13 +752,9 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
     __syncthreads();
     // iteration st (consumers are on stage st): fill stage st+1 into the other buffer
     for (int st = 0; st < nstage; ++st) {
-      STAMP(5);
       if (st + 1 < nstage) produce_stage(st + 1, smem + ((st + 1) & 1) * FS_STAGE);
-      STAMP(0);   // produce (includes waiting for the tiles' loads)
       __syncthreads();
-      STAMP(2);   // barrier
     }
-    X3_STAMP_FLUSH_PRODUCER;
     if (up) {
       // natural tiles: rows lr + 32 p, the 8 threads of a row are 8 consecutive lanes; mirrored tiles: rows 4 ig + e, the 8
       // threads of a row are the lanes jq = 0..7 (lane bits 3..5).  The two row sets meet in LDS (the stage buffers are
@@ -808,7 +790,6 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
     // than on 32x32x16 at the same cycles per flop (MI355X_MICROARCH.md, DVFS give-back item 7).
     const int ct = t - 256, lane = ct & 63, cw = ct >> 6;
     const int l15 = lane & 15, lq = lane >> 4;
-    X3_STAMP_WG_ENTRY;
     // this wave's 128-column block of [G | theta] and its CJ 16-column blocks inside it
     const int g = RB == 8 ? 2 * cb + (cw >> 2) : 4 * cb + (cw >> 1);
     const int wcol = RB == 8 ? (cw & 3) * 32 : (cw & 1) * 64;   // first column inside the block (16 CJ columns)
@@ -868,9 +849,7 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
     };
     if (ntile > 0) load_b(tile_at(0, 0), bX);
     __syncthreads();
-    X3_STAMP_DECL_CONSUMER;
     for (int st = 0; st < nstage; ++st) {
-      STAMP(5);
       const unsigned char* As = smem + (st & 1) * FS_STAGE;
       auto after = [&](int u) { return tile_at(st, u); };   // the tile in slot u of this stage (u >= FS_KT: of the next stage)
       constexpr bool kLoadV = true;
@@ -879,9 +858,7 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
         if (after(u) >= ntile) break;
         const bool n1 = after(u + 1) < ntile;
         if (kLoadV && n1) load_b(after(u + 1), bY);
-        STAMP(3);
         wait_b(kLoadV && n1, bX);
-        STAMP(0);   // diagnostic builds: waiting for this tile's V fragments
         // The two matrix waves of a SIMD (cw and cw + 4) take turns at the higher issue priority, tile by tile.  At equal
         // priority the older wave wins every arbitration: it ran ahead (1460 vs 2070 cycles per k tile, per-wave stamps)
         // and idled at the stage barrier while the younger one finished alone.  Measured -2 % on the launch.
@@ -890,18 +867,13 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
         if (n1) {
           const bool n2 = after(u + 2) < ntile;
           if (kLoadV && n2) load_b(after(u + 2), bX);
-          STAMP(3);
           wait_b(kLoadV && n2, bY);
-          STAMP(0);
           if (cw >> 2) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(0);
           mma_tile(As + (u + 1) * FS_KTB, bY);
         }
       }
-      STAMP(3);   // consumer: fragment reads + MFMAs
       __syncthreads();
-      STAMP(4);   // consumer: barrier
     }
-    X3_STAMP_FLUSH_CONSUMER;
     if (up) __syncthreads();   // the producers' row-sum exchange (same barrier count in both roles)
     if (g >= 2 * gblocks) return;   // (an odd block count leaves the last workgroup's upper waves without columns)
     float* __restrict__ Oz = (g < gblocks ? OG : OT) + (size_t)z * n_local * d;

@@ -640,13 +640,6 @@ __device__ __forceinline__ void spec_locate2(const u32* hA, u32 rankA, const u32
 // One workgroup: exact weighted selection of the two median targets among the buffered window entries.
 // Entry = key << 2 | weight, offset o = key - lo_key < 65536: pass 1 histograms o >> 8, pass 2 the low byte of the
 // entries that share each target's high byte.  Returns (workgroup-uniform) whether the window held both targets.
-#ifdef STEIN_SEL_STAMPS
-__device__ unsigned long long g_sel_stamps[16];
-extern "C" int stein_debug_sel_stamps(unsigned long long* out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sel_stamps), sizeof(g_sel_stamps)) == hipSuccess ? 0 : -1; }
-#define SEL_STAMP(k) do { if (threadIdx.x == 0) { g_sel_stamps[k] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); } } while (0)
-#else
-#define SEL_STAMP(k) do {} while (0)
-#endif
 __device__ __forceinline__ bool spec_select_body(SelState* st, SpecState* sp, const u64* __restrict__ slots, float ln_n,
                                                  float* h2_out, int update) {
   const u64* __restrict__ buf = slots + SPEC_SLOTS * 8;
@@ -654,10 +647,8 @@ __device__ __forceinline__ bool spec_select_body(SelState* st, SpecState* sp, co
   __shared__ u32 sel[8];   // [0,1] high bytes, [2,3] ranks inside them, [4,5] low bytes, [6,7] scratch
   __shared__ u64 below_s;
   const int t = threadIdx.x;
-  SEL_STAMP(0);
   const u32 cnt = sp->count, lo = sp->lo_key, width = sp->width;
   if (width == 0u || sp->overflow || cnt > SPEC_CAP || cnt == 0u) return false;   // miss: the radix select runs
-  SEL_STAMP(1);
   // thread 0 asks now for what it will need at the very end (the result and the predictor update are a chain of dependent
   // loads otherwise: ~3 k cycles behind the last barrier)
   u32 even0 = 0u;
@@ -676,7 +667,6 @@ __device__ __forceinline__ bool spec_select_body(SelState* st, SpecState* sp, co
   }
   __syncthreads();
   const u64 below = below_s;
-  SEL_STAMP(2);
   const u64 r0 = (total & 1ull) ? total / 2 : total / 2 - 1, r1 = total / 2;
   if (r0 < below || r1 - below > 0xfffffff0ull) return false;   // the target lies below the window
   // Pass 1 histograms the HIGH byte of the offsets: a window of `width` keys occupies (width >> 8) + 1 bins, a handful, and
@@ -741,9 +731,7 @@ __device__ __forceinline__ bool spec_select_body(SelState* st, SpecState* sp, co
     }
   }
   __syncthreads();
-  SEL_STAMP(3);
   spec_locate2(h1, (u32)(r0 - below), h1, (u32)(r1 - below), scan, &sel[0], &sel[2]);
-  SEL_STAMP(4);
   const u32 ba = sel[0], bb = sel[1];
   if (ba == 256u || bb == 256u) return false;   // a target lies above the window
   const bool two_hb = ba != bb;                 // (both targets in one high byte, the usual case: one low-byte histogram serves both)
@@ -766,9 +754,7 @@ __device__ __forceinline__ bool spec_select_body(SelState* st, SpecState* sp, co
     }
   }
   __syncthreads();
-  SEL_STAMP(5);
   spec_locate2(h2a, sel[2], two_hb ? h2b : h2a, sel[3], scan, &sel[4], &sel[6]);
-  SEL_STAMP(6);
   if (t == 0) {
     const float flo = key_f32(lo + ((ba << 8) | sel[4])), fhi = key_f32(lo + ((bb << 8) | sel[5]));
     const float med = even0 ? 0.5f * (flo + fhi) : flo;
@@ -779,7 +765,6 @@ __device__ __forceinline__ bool spec_select_body(SelState* st, SpecState* sp, co
     sp->hit = 1u;
     sp->skip_l0 = 1u;
     if (update) spec_update_dev(st, sp);   // fused call: no separate k_spec_update launch
-    SEL_STAMP(7);
   }
   return true;
 }
@@ -1237,7 +1222,7 @@ __global__ __launch_bounds__(256) void k_phi_finish(const float* __restrict__ OG
     if (threadIdx.x == 0) sqpart[blockIdx.x] = part;
     return;
   }
-  // the partials cross workgroups: written with device-scope atomics, read with load_fresh (last_workgroup_out)
+  // the partials cross workgroups: written with device-scope atomics, read with load_fresh (tree_report_done)
   if (threadIdx.x == 0)
     __hip_atomic_store(reinterpret_cast<u64*>(sqpart) + blockIdx.x, (u64)__double_as_longlong(part), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   {
@@ -1399,9 +1384,6 @@ int stein_make_layout(int64_t n_local, int64_t n, int64_t d, int dtype, int flag
     const double eff = rounds / ceil(rounds) - 0.004 * (double)(s - 1);
     if (eff > best + 1e-9) { best = eff; split = s; }
   }
-#ifdef STEIN_FORCE_SPLIT   // (diagnostic builds: scratch/build_variant.py splitN -DSTEIN_FORCE_SPLIT=N)
-  split = STEIN_FORCE_SPLIT <= max_split ? STEIN_FORCE_SPLIT : max_split;
-#endif
   int64_t tiles_per = (jt + split - 1) / split;
   if (x3) tiles_per = (tiles_per + 3) / 4 * 4;   // a j range of the split kernel starts on a multiple of 128 columns (its
                                                  // pipeline stages then never straddle a row tile's diagonal block)
@@ -2030,7 +2012,7 @@ extern "C" int stein_svgd_phi(const void* theta_all, const void* score_all, int6
     return STEIN_OK;
   }
   // The prologue carries the row norms and all set-up; kernels let their last workgroup do what a one-workgroup follow-up
-  // launch would (FuseState tickets: scales, |phi|^2 sum); the chained radix select is ONE launch (k_hist_all) and none
+  // launch would (scales, |phi|^2 sum); the chained radix select is ONE launch (k_hist_all) and none
   // for n <= SOLO_MAX_N (k_spec_select covers it); bf16 inputs need no scales, so their prologue rides in the split's
   // launch.  fp32 inputs: k_prologue, k_colmax, k_split, distance, k_spec_select, k_hist_all, contraction, k_phi_finish:
   // eight launches whatever n (the last workgroups of k_colmax and k_phi_finish are found with two-level completion counts,
@@ -2088,16 +2070,20 @@ extern "C" int stein_svgd_phi(const void* theta_all, const void* score_all, int6
     // beyond residency would leave the surplus to the thieves); small ones: 512 (measured at C2)
     long want = HIST_ALL_VBLOCKS;
     if (n > HIST_ALL_SMALL_N) {
-      static int resident = 0;   // (a benign race: every thread computes the same value)
-      if (!resident) {
-        int per_cu = 0, dev = 0, ncu = 0;
+      static int resident[MAX_DEVICES];   // per device, computed on first use (threads that race store the same value)
+      int dev = 0;
+      HIP_TRY(hipGetDevice(&dev));
+      const bool cached = dev >= 0 && dev < MAX_DEVICES;
+      int res = cached ? __atomic_load_n(&resident[dev], __ATOMIC_RELAXED) : 0;
+      if (!res) {
+        int per_cu = 0, ncu = 0;
         HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_hist_all, 256, 0));
-        HIP_TRY(hipGetDevice(&dev));
         HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
         const long r = (long)(per_cu > 0 ? per_cu : 4) * (ncu > 0 ? ncu : 256);
-        resident = (int)(r > HIST_BLOCKS ? HIST_BLOCKS : r);
+        res = (int)(r > HIST_BLOCKS ? HIST_BLOCKS : r);
+        if (cached) __atomic_store_n(&resident[dev], res, __ATOMIC_RELAXED);
       }
-      want = resident;
+      want = res;
     }
     if (g_hist_all_nvb > 0) want = g_hist_all_nvb;
     if (want > HS_NV) want = HS_NV;   // (HistSync::claim holds one flag per virtual workgroup)

@@ -110,7 +110,7 @@ def test_timing_flag_reports_every_stage(cuda):
 @pytest.mark.parametrize("seed", [0, 1])
 def test_last_workgroup_tickets_match_separate_launches(cuda, seed):
     """The fused call lets the last workgroup of k_colmax write the scales and the last workgroup of the level-2 pass do
-    the final resolve (stein_common.h: last_workgroup_out); the staged calls launch k_make_scales / k_resolve instead.
+    the final resolve (stein_common.h: tree_report_done); the staged calls launch k_make_scales / k_resolve instead.
     Random rescaling makes the window miss, so the chained select really runs.  Both must agree bit for bit."""
     rng = np.random.default_rng(seed)
     for n, d in [(129, 17), (333, 130), (777, 64), (1500, 3), (2048, 256), (3000, 128)]:
@@ -151,11 +151,13 @@ def test_one_launch_select_without_the_window(cuda, n, d, dtype):
 
 @pytest.mark.parametrize("grid,n", [(1, 2304), (3, 2304), (40, 2304), (4096, 2304), (7, 4608), (3000, 4608)])
 def test_one_launch_select_needs_no_co_residency(cuda, grid, n):
-    """k_hist_all's level barriers never wait for a workgroup that has not started: the work of a level is cut into 512
-    virtual workgroups that the running workgroups DRAW (FuseState::draw / done / gen).  Forced here: the launch gets 1, 3
-    or 40 workgroups (far fewer than the 512 virtual ones: the few present take them all over) or 4096 (more than the chip
-    holds at once: the late ones find every counter exhausted and fall through).  The median -- hence bandwidth, phi and
-    |phi|^2 -- equals the staged calls' bit for bit every time, and no error is raised."""
+    """k_hist_all's level barriers never wait for a workgroup that has not started: the work of a level is cut into nvb
+    virtual workgroups (HistSync): each running workgroup CLAIMS its own, reports it done on a two-level leaf / top count,
+    and one that has waited long enough claims the virtual workgroups nobody has taken yet.  Forced here: the launch gets
+    1, 3 or 40 workgroups (far fewer than the nvb virtual ones: the few present take them all over) or 4096 (more than the
+    chip holds at once: the late ones find every virtual workgroup claimed and every level published, and fall through).
+    The median -- hence bandwidth, phi and |phi|^2 -- equals the staged calls' bit for bit every time, and no error is
+    raised."""
     d = 24                                                           # n = 2304: 512 virtual workgroups; 4608: 2048
     g = torch.Generator(device="cpu").manual_seed(grid)
     fused = SvgdEngine(n, d, device=cuda, window=False, small=False)
