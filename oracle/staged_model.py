@@ -21,7 +21,7 @@ BITS = (11, 11, 10)
 
 
 def f32_keys(x):
-    """Monotone map fp32 -> uint32 (same as f32_key in steinhip.hip)."""
+    """Monotone map fp32 -> uint32 (same as f32_key in stein_common.h)."""
     u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
     neg = (u & np.uint32(0x80000000)) != 0
     return np.where(neg, ~u, u | np.uint32(0x80000000)).astype(np.uint32)
@@ -114,7 +114,7 @@ class NumpyStages:
         hist.zero_()
         self._st = SelectState(total)
 
-    # ---- speculative window across ranks (stein_common.h: SpecState; steinhip.hip: k_median_init, k_spec_tally,
+    # ---- speculative window across ranks (stein_common.h: SpecState; stein_select.hip: k_median_init, k_spec_tally,
     #      k_spec_pick, k_spec_update).  The predictor lives in self._sp; the two state words the engine reads back
     #      (hit, skip_l0) are mirrored into the SELECT section at the offsets of the device struct. ----
     HW_MAX, TABLE_HDR, TABLE_OFF = 32767, 8, 1 << 21

@@ -14,7 +14,7 @@
 
 #include <cstring>
 
-#include "stein_common.h"
+#include "stein_host.h"
 #include "stein_x3.h"
 #include "steinhip.h"
 
@@ -203,9 +203,7 @@ extern "C" int stein_rank_step(void* comm, const void* theta_local, const void* 
   int rc = stein_make_layout(n_local, n, d, dtype, (flags & STEIN_FLAG_X3) | STEIN_FLAG_TILED, &L);
   if (rc) return rc;
   if (ws_bytes < L.total) return stein_fail(STEIN_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L.total);
-  char* ws = static_cast<char*>(workspace);
-  u64* hist = reinterpret_cast<u64*>(ws + L.off[STEIN_WS_HIST]);
-  u64* table = reinterpret_cast<u64*>(ws + L.off[STEIN_WS_SPEC]) + (SPEC_SLOTS * 8 + SPEC_CAP);
+  const StepViews v = stein_step_views(L, workspace);
 
   // Everything a rank can get wrong by itself has been checked above, before its first collective.  From here on a failure
   // goes through fail_in_step: the communicator is aborted, so the peers' collectives fail instead of waiting for ever.
@@ -237,10 +235,10 @@ extern "C" int stein_rank_step(void* comm, const void* theta_local, const void* 
   auto score_planes = [&]() -> int {   // first reader of the gathered score rows: the caller's stream joins the side stream
     if (hipStreamWaitEvent(stream, c->join, 0) != hipSuccess) return stein_fail(STEIN_E_HIP, "hipStreamWaitEvent failed");
     if (!(flags & STEIN_FLAG_X3)) return STEIN_OK;
-    return stein_x3_split(nullptr, score_all, dtype, n, d, L, ws + L.off[STEIN_WS_PLANES], stream);
+    return stein_x3_split(nullptr, score_all, dtype, n, d, L, v.planes, stream);
   };
   auto level_sum = [&](int level) -> int {   // hist[level] summed over the ranks, in place
-    u64* h = hist + (size_t)level * 2 * STEIN_HIST_BINS;
+    u64* h = v.hist + (size_t)level * 2 * STEIN_HIST_BINS;
     ncclResult_t r_ = g_rccl.AllReduce(h, h, 2 * STEIN_HIST_BINS, ncclUint64, ncclSum, c->comm, stream);
     if (r_ != ncclSuccess) return stein_fail(STEIN_E_RCCL, "ncclAllReduce(histogram): %s", g_rccl.GetErrorString(r_));
     return STEIN_OK;
@@ -261,7 +259,7 @@ extern "C" int stein_rank_step(void* comm, const void* theta_local, const void* 
   // (3) the median of the n^2 distances, identical on every rank
   int hit = -1;
   if (window) {
-    STEP_RCCL(g_rccl.AllReduce(table, table, SPEC_TABLE, ncclUint64, ncclSum, c->comm, stream));
+    STEP_RCCL(g_rccl.AllReduce(v.table, v.table, SPEC_TABLE, ncclUint64, ncclSum, c->comm, stream));
     STEP_TRY(stein_rank_pick(n, d, row0, n_local, dtype, workspace, ws_bytes, seg_flags, h2_out, median_out, c->flags_host,
                              stream));
     STEP_HIP(hipEventRecord(c->flags_ready, stream));

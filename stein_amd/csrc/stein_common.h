@@ -1,5 +1,6 @@
-// stein_common.h -- device helpers shared by the fp32-MFMA kernels (steinhip.hip) and the split-precision
-// kernels (stein_x3.hip): tile geometry, tile-id mapping, radix-select keys/state, and the two epilogues.
+// stein_common.h -- device helpers shared by the fp32-MFMA kernels (stein_fp32.hip), the select (stein_select.hip) and the
+// split-precision kernels (stein_x3.hip): tile geometry, tile-id mapping, radix-select keys/state, the two epilogues, and
+// the workspace layout.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -12,7 +13,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned long long u64;
 typedef unsigned int u32;
 
-// ---- error plumbing (defined in steinhip.hip) ---------------------------------------------------
+// ---- error plumbing (defined in steinhip.hip; stein_host.h names it `fail`) ---------------------------------------------------
 int stein_fail(int code, const char* fmt, ...);
 
 #define HIP_TRY(expr)                                                                          \
@@ -138,7 +139,7 @@ struct FuseState {
   u32 pad[13];
 };
 static_assert(sizeof(FuseState) == 64, "FuseState must stay 64 bytes");
-// Synchronisation state of k_hist_all (the fused call's chained radix select in one launch, steinhip.hip): lives in the
+// Synchronisation state of k_hist_all (the fused call's chained radix select in one launch, stein_select.hip): lives in the
 // rank-summed window table of the SPEC section, which a single-rank fused call has no other use for; zeroed by the fused
 // call's first kernel.  Laid out so that NO address is hit by more than a few dozen workgroups: a device-scope atomic that
 // returns its value costs ~20 ns when two thousand workgroups aim it at one address (they are performed one after the
@@ -187,7 +188,8 @@ constexpr u32 SPEC_HW_MAX = 32767;       // window <= 65535 keys: two 8-bit sele
 // [2] entries, [8 + k] weight of key lo_key + k.
 constexpr u32 SPEC_TABLE_HDR = 8;
 constexpr u32 SPEC_TABLE = SPEC_TABLE_HDR + 2 * SPEC_HW_MAX + 2;   // 65544 u64
-static_assert(SPEC_SLOTS * 8 + SPEC_CAP == (1u << 21), "the table starts 2^21 words into the SPEC section (stein_amd/_lib.py)");
+constexpr u32 SPEC_TABLE_AT = SPEC_SLOTS * 8 + SPEC_CAP;   // u64 words from the SPEC section's start to the table
+static_assert(SPEC_TABLE_AT == (1u << 21), "the table starts 2^21 words into the SPEC section (stein_amd/_lib.py)");
 
 __device__ __forceinline__ u32 f32_key(float x) {  // monotone: a < b  <=>  key(a) < key(b)
   const u32 u = __float_as_uint(x);
@@ -195,6 +197,16 @@ __device__ __forceinline__ u32 f32_key(float x) {  // monotone: a < b  <=>  key(
 }
 __device__ __forceinline__ float key_f32(u32 k) {
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+// the two order statistics of the select -> the median and the squared bandwidth of the kernel
+struct MedianBw { float med, h2; };
+__device__ __forceinline__ MedianBw median_bandwidth(float lo, float hi, u32 even, float ln_n) {
+  MedianBw m;
+  m.med = even ? 0.5f * (lo + hi) : lo;      // compute_median.py:12-15
+  const float bw = sqrtf(m.med / ln_n);      // abstract_kernel.py:40
+  m.h2 = bw * bw;                            // squared_exponential_kernel.py:22 squares it again
+  return m;
 }
 
 __device__ __forceinline__ u64 load_fresh(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -566,15 +578,8 @@ struct SteinLayout {
 };
 int stein_make_layout(int64_t n_local, int64_t n, int64_t d, int dtype, int flags, SteinLayout* L);
 
-// stein_small.hip: the whole phi computation in one kernel for n <= 160 (the reference's own example sizes)
-bool stein_small_ok(int64_t n, int64_t d, int dtype);
-int stein_small_phi(const float* theta, const float* score, int64_t n, int64_t d, float* phi, float* h2_out,
-                    double* sqpart /* one partial |phi|^2 per workgroup, *nparts of them (<= ceil(d / 32)) */,
-                    float* K_out, float* dK_out, int* nparts /* 0: a single workgroup wrote *sqnorm_out itself */,
-                    double* sqnorm_out, hipStream_t stream);
-
 // ------------------------------------------------------------------------------------------------
-// fused-call prologue (k_prologue, steinhip.hip; for bf16 inputs a slice of k_split's grid, stein_x3.hip): k_sel_init + the window set-up + zeroing of the histograms and of the "below" slots
+// fused-call prologue (k_prologue, steinhip.hip; for bf16 inputs a slice of k_split's grid, stein_x3.hip): k_sel_init's work (stein_select.hip) + the window set-up + zeroing of the histograms and of the "below" slots
 // (gt of gn threads share the zeroing; thread 0 sets the states up)
 __device__ __forceinline__ void median_init_body(int gt, int gn, SelState* st, SpecState* sp, u64 total,
                                                  u64* __restrict__ hist, u64* __restrict__ slots, int allow_window = 1) {

@@ -9,7 +9,7 @@
 //   h2   = sqrt(med / ln n)^2                                abstract_kernel.py:40, squared_exponential_kernel.py:22
 //   K    = exp(-D / h2 / 2);  dK = (rowsum(K) theta - K theta) / h2     squared_exponential_kernel.py:22-35
 //   phi  = (K G + dK) / n                                    stein/samplers/abstract_stein_sampler.py:100-105
-#include "stein_common.h"
+#include "stein_host.h"
 
 #include <type_traits>
 
@@ -204,9 +204,7 @@ __global__ __launch_bounds__(SM_THREADS) void k_svgd_small(const float* __restri
   }
   if (t == 0) {
     const float lo = key_f32(s_prefix[0]), hi = key_f32(s_prefix[1]);
-    const float med = (total & 1u) ? lo : 0.5f * (lo + hi);        // compute_median.py:12-15
-    const float bw = sqrtf(med / ln_n);                             // abstract_kernel.py:40
-    s_h2 = bw * bw;                                                 // squared_exponential_kernel.py:22
+    s_h2 = median_bandwidth(lo, hi, (total & 1u) ^ 1u, ln_n).h2;
     if (blockIdx.x == 0) *h2_out = s_h2;
   }
   __syncthreads();

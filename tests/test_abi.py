@@ -113,8 +113,11 @@ def test_library_reads_no_environment():
     import subprocess
     out = subprocess.run(["nm", "-D", "--undefined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
     assert "getenv" not in out
-    for src in ("steinhip.hip", "stein_x3.hip", "stein_small.hip", "stein_score.hip", "stein_common.h"):
-        assert "getenv" not in open(os.path.join(ROOT, "stein_amd", "csrc", src)).read()
+    csrc = os.path.join(ROOT, "stein_amd", "csrc")
+    srcs = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h", ".inc")))
+    assert {"steinhip.hip", "stein_select.hip", "stein_x3.hip", "stein_common.h", "stein_host.h"} <= set(srcs)
+    for src in srcs:
+        assert "getenv" not in open(os.path.join(csrc, src)).read(), src
 
 
 def test_build_digest_does_not_depend_on_where_the_tree_lives(monkeypatch):

@@ -199,7 +199,7 @@ def test_device_error_word_is_reported_by_the_next_call(cuda):
 
 
 def test_window_half_width_follows_the_documented_rule(cuda):
-    """The predictor on the device (spec_update_dev, steinhip.hip): the next half-width is max(4 * |this step's prediction
+    """The predictor on the device (spec_update_dev, stein_select.hip): the next half-width is max(4 * |this step's prediction
     error| + 48, 3/4 of the last half-width that was itself earned from an error) -- the 4096-key window of a predictor
     without a velocity does not count -- capped at 32767.  Replayed here from the state words of consecutive steps."""
     n, d = 2048, 32
