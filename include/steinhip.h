@@ -58,9 +58,23 @@ enum {
                                   of the radix-select histograms */
   STEIN_FLAG_TILE_DISTANCE = 64, /* stein_svgd_phi only: run the distance pass with the per-tile kernel even where the
                                     panel-resident form (STEIN_STAGE_TILES below) would be taken; for A/B measurements */
-  STEIN_FLAG_TIMING_CONTRACT = 128 /* stein_svgd_phi, with STEIN_FLAG_TIMING: record only the two events that bracket the
-                                      contraction (an event between two kernels costs the step ~3 us of GPU time: six of
-                                      them perturb what they time); stein_timing_read reports -1 for the other stages */
+  STEIN_FLAG_TIMING_CONTRACT = 128, /* stein_svgd_phi, with STEIN_FLAG_TIMING: record only the two events that bracket the
+                                       contraction (an event between two kernels costs the step ~3 us of GPU time: six of
+                                       them perturb what they time); stein_timing_read reports -1 for the other stages */
+  STEIN_FLAG_KSD = 256 /* stein_svgd_phi, stein_rank_finish, stein_rank_step (and stein_workspace_bytes / _layout, whose
+                          SQPART section then holds three partials per block): also the kernelized Stein discrepancy of
+                          the particles under the step's own RBF kernel and median bandwidth.  sqnorm_out then points to
+                          double[3] = { |phi|^2, S, S_diag } with
+                            u_ij = k_ij [ g_i.g_j + (g_i - g_j).(x_i - x_j)/h2 + d/h2 - D_ij/h2^2 ],  k_ij = exp(-D_ij / 2 h2)
+                            S = this call's rows' share of  sum_ij u_ij,   S_diag = its share of  sum_i u_ii
+                          (x = theta, g = score, h2 = *h2_out), so that  KSD^2_V = S / n^2  and
+                          KSD^2_U = (S - S_diag) / (n (n - 1)).  The share is taken per element (i, c) of the rows by an
+                          identity that uses the symmetry of K: a rank's S is NOT sum_{i in its rows, j} u_ij;
+                          only the sum over all ranks is the statistic (stein_rank_step all-reduces all three doubles).
+                          [0] keeps its meaning, so the apply calls read it unchanged; phi, h2 and |phi|^2 are
+                          bit-identical to a call without the flag.  stein_contract_finish / stein_kernel_contract have no
+                          score operand and refuse the flag (STEIN_E_BADARG).  The flag moves the workspace sections
+                          behind SQPART: pass it to every stein_rank_* segment of a step alike. */
 };
 /* flags for the staged distance / histogram calls */
 enum {
@@ -93,7 +107,8 @@ enum {
   STEIN_WS_PART_G = 4,   /* float  [split][n_local][d]      partial K.G                           */
   STEIN_WS_PART_T = 5,   /* float  [split][n_local][d]      partial K.theta                       */
   STEIN_WS_PART_RS = 6,  /* float  [split][n_local]         partial rowsum(K)                     */
-  STEIN_WS_SQPART = 7,   /* double [sq_blocks]              per-block partial |phi|^2             */
+  STEIN_WS_SQPART = 7,   /* double [sq_blocks]              per-block partial |phi|^2 (STEIN_FLAG_KSD: [3][sq_blocks],
+                                                            the S and S_diag partials behind them)  */
   STEIN_WS_SPEC = 8,     /* 16 MB  entries caught by the speculative median window (stein_svgd_phi only)  */
   STEIN_WS_PLANES = 9,   /* split-precision operand planes + scales (STEIN_FLAG_X3 only; empty otherwise), always last */
   STEIN_WS_NSECTIONS = 10
@@ -120,7 +135,8 @@ int stein_workspace_layout(int64_t n_local, int64_t n, int64_t d, int dtype, int
  *   theta_all, score_all : [n][d] of `dtype` (STEIN_F32 or STEIN_BF16)
  *   phi_local            : [n_local][d] float, rows row0..row0+n_local      (unclipped phi)
  *   h2_out               : float[1], receives bandwidth^2
- *   sqnorm_out           : double[1], receives sum(phi_local^2) (the rank-local part of |phi|_F^2)
+ *   sqnorm_out           : double[1], receives sum(phi_local^2) (the rank-local part of |phi|_F^2); with
+ *                          STEIN_FLAG_KSD double[3]: |phi|^2, S, S_diag (see the flag)
  *   K_out / dK_out       : optional (may be NULL): [n_local][n] float / [n_local][d] float
  * row0 / n_local: this is the SINGLE-RANK entry -- row0 must be 0 and n_local must equal n (one rank sees every row, so
  * the median is global), anything else returns STEIN_E_BADARG.  The two arguments stay in the signature because SURVEY.md
@@ -239,7 +255,8 @@ int stein_contract_finish(const void* theta_all, int64_t n, int64_t d, int64_t r
  * host layer issues per step only  all-gather(theta), all-gather(score) | stein_rank_begin | all-reduce | stein_rank_pick
  * (window form) or stein_rank_radix x3 with an all-reduce before each (radix form) | stein_rank_finish |
  * all-reduce(|phi|^2).  `workspace` is sized by stein_workspace_bytes(n_local, n, d, dtype, flags | STEIN_FLAG_TILED);
- * flags: STEIN_FLAG_X3 and, for the window form, STEIN_FLAG_RANK_WINDOW.  They replace, for rank p's rows, the same
+ * flags: STEIN_FLAG_X3, for the window form STEIN_FLAG_RANK_WINDOW, and STEIN_FLAG_KSD (every segment alike;
+ * stein_rank_finish then writes double[3] to sqnorm_out: all-reduce all three).  They replace, for rank p's rows, the same
  * reference lines as stein_svgd_phi.
  *   stein_rank_begin   row norms, theta's operand planes, median set-up, the [n_local, n] distance block (level-0
  *                      histogram or window counting in its epilogue) and, window form, the tally.  Then all-reduce(sum)
@@ -277,7 +294,8 @@ int stein_rank_finish(const void* theta_all, const void* score_all, int64_t n, i
  *                         (radix form: nothing waits) -> stein_rank_finish -> all-reduce(|phi|^2).
  *                         theta_all / score_all: [n, d] gather targets; h2_out, median_out, sqnorm_out: device scalars,
  *                         identical on every rank afterwards; window_hit_out (may be NULL): 1 / 0, -1 in the radix form.
- *                         flags: STEIN_FLAG_X3, STEIN_FLAG_RANK_WINDOW, STEIN_FLAG_TIMING; workspace sized by
+ *                         flags: STEIN_FLAG_X3, STEIN_FLAG_RANK_WINDOW, STEIN_FLAG_TIMING, STEIN_FLAG_KSD (sqnorm_out
+ *                         double[3], all three all-reduced); workspace sized by
  *                         stein_workspace_bytes(n / nranks, n, d, dtype, flags | STEIN_FLAG_TILED). */
 #define STEIN_COMM_ID_BYTES 128
 int stein_comm_unique_id(void* id_out, size_t id_bytes);

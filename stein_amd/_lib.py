@@ -29,6 +29,7 @@ FLAG_NO_WINDOW = 16
 FLAG_RANK_WINDOW = 32
 FLAG_TILE_DISTANCE = 64
 FLAG_TIMING_CONTRACT = 128
+FLAG_KSD = 256      # also the kernelized Stein discrepancy sums: sqnorm is double[3] = |phi|^2, S, S_diag
 GLM_LINEAR, GLM_LOGISTIC = 0, 1
 SPEC_TABLE_WORDS = 65544          # uint64 words of the rank-summed window table ...
 SPEC_TABLE_OFFSET_WORDS = 1 << 21  # ... which starts 2^21 words into the SPEC section (slots + entry buffer)

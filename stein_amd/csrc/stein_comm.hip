@@ -194,13 +194,13 @@ extern "C" int stein_rank_step(void* comm, const void* theta_local, const void* 
   const int64_t n_local = n / c->nranks, row0 = (int64_t)c->rank * n_local;
   const hipStream_t stream = static_cast<hipStream_t>(stream_v);
   const bool window = (flags & STEIN_FLAG_RANK_WINDOW) != 0;
-  const int seg_flags = flags & (STEIN_FLAG_X3 | STEIN_FLAG_RANK_WINDOW);
-  if (flags & ~(STEIN_FLAG_X3 | STEIN_FLAG_RANK_WINDOW | STEIN_FLAG_TIMING | STEIN_FLAG_TILED))
+  const int seg_flags = flags & (STEIN_FLAG_X3 | STEIN_FLAG_RANK_WINDOW | STEIN_FLAG_KSD);
+  if (flags & ~(STEIN_FLAG_X3 | STEIN_FLAG_RANK_WINDOW | STEIN_FLAG_TIMING | STEIN_FLAG_TILED | STEIN_FLAG_KSD))
     return stein_fail(STEIN_E_BADARG, "unknown flags 0x%x", flags);
 
   // the sections the collectives touch (the same layout the segments derive)
   SteinLayout L;
-  int rc = stein_make_layout(n_local, n, d, dtype, (flags & STEIN_FLAG_X3) | STEIN_FLAG_TILED, &L);
+  int rc = stein_make_layout(n_local, n, d, dtype, (flags & (STEIN_FLAG_X3 | STEIN_FLAG_KSD)) | STEIN_FLAG_TILED, &L);
   if (rc) return rc;
   if (ws_bytes < L.total) return stein_fail(STEIN_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L.total);
   const StepViews v = stein_step_views(L, workspace);
@@ -274,10 +274,10 @@ extern "C" int stein_rank_step(void* comm, const void* theta_local, const void* 
   }
   if (window_hit_out) *window_hit_out = hit;
 
-  // (4) the contraction on the local rows, phi, and the global |phi|^2
+  // (4) the contraction on the local rows, phi, and the global |phi|^2 (STEIN_FLAG_KSD: and the two Stein discrepancy sums)
   STEP_TRY(stein_rank_finish(theta_all, score_all, n, d, row0, n_local, dtype, h2_out, phi_local, sqnorm_out, dK_out,
                              workspace, ws_bytes, seg_flags | (flags & STEIN_FLAG_TIMING), stream));
-  STEP_RCCL(g_rccl.AllReduce(sqnorm_out, sqnorm_out, 1, ncclFloat64, ncclSum, c->comm, stream));
+  STEP_RCCL(g_rccl.AllReduce(sqnorm_out, sqnorm_out, (flags & STEIN_FLAG_KSD) ? 3 : 1, ncclFloat64, ncclSum, c->comm, stream));
 #undef STEP_TRY
 #undef STEP_RCCL
 #undef STEP_HIP

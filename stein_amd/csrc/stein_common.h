@@ -209,6 +209,15 @@ __device__ __forceinline__ MedianBw median_bandwidth(float lo, float hi, u32 eve
   return m;
 }
 
+// STEIN_FLAG_KSD: one element e = (i, c)'s share of sum_ij u_ij (s) and of sum_i u_ii (sd), include/steinhip.h, from the
+// fp32 sums og = (K.G)_e, ot = (K.theta)_e, rs = rowsum(K)_i; ih = 1 / h2.  In fp64, and dk is formed again here:
+// rs * th - ot cancels, and the fp32 dk of phi has lost those digits already.
+__device__ __forceinline__ void ksd_terms(float g, float og, float ot, float th, float rs, double ih, double& s, double& sd) {
+  const double gd = g, dk = ((double)rs * (double)th - (double)ot) * ih;
+  s += gd * (double)og + 2.0 * (gd - (double)th * ih) * dk + (double)rs * ih;
+  sd += gd * gd + ih;
+}
+
 __device__ __forceinline__ u64 load_fresh(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ u32 load_fresh(const u32* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 

@@ -27,6 +27,9 @@ static inline int small_chunk(int64_t n, int64_t d) {
   return (int)(ck < dr ? ck : dr);
 }
 
+// KSD (STEIN_FLAG_KSD): also this workgroup's shares of the Stein discrepancy sums S and S_diag (ksd_terms, from the K.G,
+// K.theta and rowsum(K) of its columns); their partials follow the |phi|^2 partials in sqpart ([3][gridDim.x])
+template <bool KSD>
 __global__ __launch_bounds__(SM_THREADS) void k_svgd_small(const float* __restrict__ T, const float* __restrict__ G, int n,
                                                            int d, float ln_n, float* __restrict__ phi,
                                                            float* __restrict__ h2_out, double* __restrict__ sqpart,
@@ -248,6 +251,8 @@ __global__ __launch_bounds__(SM_THREADS) void k_svgd_small(const float* __restri
   // theta entries once, for 8 RB FMAs -- one row at a time read three words per two FMAs and the stage was bound by LDS
   // bandwidth (61 k of the kernel's 144 k cycles at n = 128).
   double sq = 0.0;
+  double ks = 0.0, kd = 0.0;   // KSD: this thread's shares of S and S_diag
+  const double ih = 1.0 / (double)h2;
   const float fn = (float)n;
   // Lanes: CLW columns x 64 / CLW slices of the j range (slice starts are multiples of 4).  CLW = 32 unless the
   // workgroup has few columns (d = 1 ... 16: the reference's regression examples), where 32 column lanes would spend
@@ -302,6 +307,7 @@ __global__ __launch_bounds__(SM_THREADS) void k_svgd_small(const float* __restri
         phi[(size_t)i * d + c] = ph;
         if (dK_out) dK_out[(size_t)i * d + c] = dk;
         sq += (double)ph * (double)ph;
+        if constexpr (KSD) ksd_terms(gs[i * SM_COLS + cl], sg, st, ts[i * (SM_COLS + 1) + cl], rn[i], ih, ks, kd);
       }
     }
   };
@@ -317,6 +323,14 @@ __global__ __launch_bounds__(SM_THREADS) void k_svgd_small(const float* __restri
   static_assert(SM_MAXN <= 10 * (SM_THREADS / 64), "rows per wave");
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
+  double* s_kred = nullptr;   // KSD: S, S_diag per wave (an LDS array of that instantiation only)
+  if constexpr (KSD) {
+    __shared__ double kred[2 * (SM_THREADS / 64)];
+    s_kred = kred;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { ks += __shfl_xor(ks, o); kd += __shfl_xor(kd, o); }
+    if (lane == 0) { s_kred[wave] = ks; s_kred[SM_THREADS / 64 + wave] = kd; }
+  }
   if (lane == 0) s_red[wave] = sq;
   __syncthreads();
   if (t == 0) {
@@ -324,6 +338,14 @@ __global__ __launch_bounds__(SM_THREADS) void k_svgd_small(const float* __restri
     for (int w = 0; w < SM_THREADS / 64; ++w) s += s_red[w];
     sqpart[blockIdx.x] = s;
     if (gridDim.x == 1 && sq_total) *sq_total = s;   // d <= 32: this workgroup's partial is the whole |phi|^2
+    if constexpr (KSD) {
+      for (int k = 0; k < 2; ++k) {
+        double a = 0.0;
+        for (int w = 0; w < SM_THREADS / 64; ++w) a += s_kred[k * (SM_THREADS / 64) + w];
+        sqpart[(k + 1) * gridDim.x + blockIdx.x] = a;
+        if (gridDim.x == 1 && sq_total) sq_total[k + 1] = a;
+      }
+    }
   }
 }
 
@@ -333,23 +355,28 @@ bool stein_small_ok(int64_t n, int64_t d, int dtype) {
 }
 
 int stein_small_phi(const float* theta, const float* score, int64_t n, int64_t d, float* phi, float* h2_out,
-                    double* sqpart, float* K_out, float* dK_out, int* nparts, double* sqnorm_out, hipStream_t stream) {
+                    double* sqpart, float* K_out, float* dK_out, int* nparts, double* sqnorm_out, bool ksd,
+                    hipStream_t stream) {
   const int blocks = (int)((d + SM_COLS - 1) / SM_COLS);
   // distances | theta chunk | rowsum | histograms, later the score block [n][32] (whichever is larger)
   const size_t hist_b = 2 * STEIN_HIST_BINS * sizeof(u32), gs_b = (size_t)n * SM_COLS * sizeof(float);
   const size_t lds = ((size_t)n * ((n + 3) & ~(int64_t)3) + (size_t)n * (small_chunk(n, d) + 1) + n) * sizeof(float) + (hist_b > gs_b ? hist_b : gs_b);
   // more than the default 64 KB of dynamic LDS: the attribute belongs to the function ON ONE DEVICE, so it is set once per
   // device the library launches on (a flag per device id; racing threads at worst set it twice)
-  static bool attr_set[64] = {false};
+  static bool attr_set[2][64] = {{false}};   // per instantiation (KSD) and device
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_svgd_small), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                150 * 1024));
-    if (dev >= 0 && dev < 64) attr_set[dev] = true;
+  const void* fn = ksd ? reinterpret_cast<const void*>(k_svgd_small<true>) : reinterpret_cast<const void*>(k_svgd_small<false>);
+  if (dev < 0 || dev >= 64 || !attr_set[ksd][dev]) {
+    HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+    if (dev >= 0 && dev < 64) attr_set[ksd][dev] = true;
   }
-  hipLaunchKernelGGL(k_svgd_small, dim3((unsigned)blocks), dim3(SM_THREADS), lds, stream, theta, score, (int)n, (int)d,
-                     (float)log((double)n), phi, h2_out, sqpart, K_out, dK_out, sqnorm_out, small_chunk(n, d));
+  if (ksd)
+    hipLaunchKernelGGL(k_svgd_small<true>, dim3((unsigned)blocks), dim3(SM_THREADS), lds, stream, theta, score, (int)n, (int)d,
+                       (float)log((double)n), phi, h2_out, sqpart, K_out, dK_out, sqnorm_out, small_chunk(n, d));
+  else
+    hipLaunchKernelGGL(k_svgd_small<false>, dim3((unsigned)blocks), dim3(SM_THREADS), lds, stream, theta, score, (int)n, (int)d,
+                       (float)log((double)n), phi, h2_out, sqpart, K_out, dK_out, sqnorm_out, small_chunk(n, d));
   LAUNCH_CHECK("k_svgd_small");
   *nparts = blocks == 1 ? 0 : blocks;   // one workgroup: it has written *sqnorm_out itself
   return STEIN_OK;

@@ -27,6 +27,7 @@
 #include "stein_host.h"
 #include "stein_x3.h"
 
+#include <type_traits>
 #include <vector>
 
 // ------------------------------------------------------------------------------------------------
@@ -100,21 +101,26 @@ __device__ __forceinline__ float4 theta4(const unsigned short* p) {   // four bf
   return make_float4(__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xffff0000u), __uint_as_float(w.y << 16),
                      __uint_as_float(w.y & 0xffff0000u));
 }
-template <typename TIN>
+// KSD (STEIN_FLAG_KSD): also this call's shares of the Stein discrepancy sums S and S_diag (ksd_terms) from the score rows
+// G; their block partials follow the |phi|^2 partials in sqpart ([3][gridDim.x]) and sq_out is double[3].  The KSD = false
+// instantiation is the kernel without the statistic.
+template <typename TIN, bool KSD>
 __global__ __launch_bounds__(256) void k_phi_finish(const float* __restrict__ OG, const float* __restrict__ OT,
                                                     const float* __restrict__ RS, const TIN* __restrict__ T,
                                                     const float* __restrict__ h2p, float* __restrict__ phi,
                                                     float* __restrict__ dK, double* __restrict__ sqpart, int n, int d,
                                                     int row0, int n_local, int split, int vec, HistSync* done,
-                                                    double* __restrict__ sq_out) {
+                                                    double* __restrict__ sq_out, const TIN* __restrict__ G) {
   // done != NULL (fused call; its completion counters are zero at launch): the last workgroup out also sums the partials --
   // in the order k_sum_partials uses, so the result is the same to the last bit -- which saves that launch
-  __shared__ double red[4];
+  __shared__ double red[KSD ? 12 : 4];
   const float h2 = *h2p;
   const float fn = (float)n;
   const long total = (long)n_local * d;
   const size_t zs = (size_t)n_local * d;
   double sq = 0.0;
+  double ks = 0.0, kd = 0.0;            // KSD: this thread's shares of S and S_diag
+  const double ih = 1.0 / (double)h2;
   if (vec) {   // host: d % 4 == 0 and every pointer aligned for four columns at a time
     // four consecutive columns of one row per step, 16-byte loads and stores (one entry at a time with an integer
     // division each, the kernel moved its 68 MB at 2.8 TB/s; bf16 inputs took that path until round 4: 19 us at C2)
@@ -139,6 +145,13 @@ __global__ __launch_bounds__(256) void k_phi_finish(const float* __restrict__ OG
       *reinterpret_cast<float4*>(phi + e) = ph;
       if (dK) *reinterpret_cast<float4*>(dK + e) = dk;
       sq += ((double)ph.x * (double)ph.x + (double)ph.y * (double)ph.y) + ((double)ph.z * (double)ph.z + (double)ph.w * (double)ph.w);
+      if constexpr (KSD) {
+        const float4 g = theta4(G + (size_t)row0 * d + e);
+        ksd_terms(g.x, og.x, ot.x, th.x, rs, ih, ks, kd);
+        ksd_terms(g.y, og.y, ot.y, th.y, rs, ih, ks, kd);
+        ksd_terms(g.z, og.z, ot.z, th.z, rs, ih, ks, kd);
+        ksd_terms(g.w, og.w, ot.w, th.w, rs, ih, ks, kd);
+      }
     }
   } else {
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
@@ -155,20 +168,42 @@ __global__ __launch_bounds__(256) void k_phi_finish(const float* __restrict__ OG
       phi[e] = ph;
       if (dK) dK[e] = dk;
       sq += (double)ph * (double)ph;
+      if constexpr (KSD) ksd_terms(elem_f32(G + (size_t)row0 * d + e), og, ot, th, rs, ih, ks, kd);
     }
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
+  if constexpr (KSD) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { ks += __shfl_xor(ks, o); kd += __shfl_xor(kd, o); }
+    if ((threadIdx.x & 63) == 0) { red[4 + (threadIdx.x >> 6)] = ks; red[8 + (threadIdx.x >> 6)] = kd; }
+  }
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
   __syncthreads();
   const double part = (red[0] + red[1]) + (red[2] + red[3]);
+  double kpart[2] = {0.0, 0.0};
+  if constexpr (KSD) {
+    kpart[0] = (red[4] + red[5]) + (red[6] + red[7]);
+    kpart[1] = (red[8] + red[9]) + (red[10] + red[11]);
+  }
   if (!done) {
-    if (threadIdx.x == 0) sqpart[blockIdx.x] = part;
+    if (threadIdx.x == 0) {
+      sqpart[blockIdx.x] = part;
+      if constexpr (KSD) {
+        sqpart[gridDim.x + blockIdx.x] = kpart[0];
+        sqpart[2 * gridDim.x + blockIdx.x] = kpart[1];
+      }
+    }
     return;
   }
   // the partials cross workgroups: written with device-scope atomics, read with load_fresh (tree_report_done)
-  if (threadIdx.x == 0)
+  if (threadIdx.x == 0) {
     __hip_atomic_store(reinterpret_cast<u64*>(sqpart) + blockIdx.x, (u64)__double_as_longlong(part), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if constexpr (KSD)
+      for (int k = 0; k < 2; ++k)
+        __hip_atomic_store(reinterpret_cast<u64*>(sqpart) + (k + 1) * gridDim.x + blockIdx.x, (u64)__double_as_longlong(kpart[k]),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
   {
     __shared__ u32 s_last;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's partial has been acknowledged
@@ -181,10 +216,28 @@ __global__ __launch_bounds__(256) void k_phi_finish(const float* __restrict__ OG
   for (int i = threadIdx.x; i < (int)gridDim.x; i += 256) s2 += __longlong_as_double((long long)load_fresh(reinterpret_cast<const u64*>(sqpart) + i));
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) s2 += __shfl_xor(s2, o);
+  double t[2] = {0.0, 0.0};
+  if constexpr (KSD) {   // the S and S_diag partials, each in the same order as |phi|^2's
+    for (int k = 0; k < 2; ++k) {
+      for (int i = threadIdx.x; i < (int)gridDim.x; i += 256)
+        t[k] += __longlong_as_double((long long)load_fresh(reinterpret_cast<const u64*>(sqpart) + (k + 1) * gridDim.x + i));
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) t[k] += __shfl_xor(t[k], o);
+    }
+  }
   __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s2;
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6] = s2;
+    if constexpr (KSD) { red[4 + (threadIdx.x >> 6)] = t[0]; red[8 + (threadIdx.x >> 6)] = t[1]; }
+  }
   __syncthreads();
-  if (threadIdx.x == 0) *sq_out = (red[0] + red[1]) + (red[2] + red[3]);
+  if (threadIdx.x == 0) {
+    *sq_out = (red[0] + red[1]) + (red[2] + red[3]);
+    if constexpr (KSD) {
+      sq_out[1] = (red[4] + red[5]) + (red[6] + red[7]);
+      sq_out[2] = (red[8] + red[9]) + (red[10] + red[11]);
+    }
+  }
 }
 
 __global__ __launch_bounds__(256) void k_sum_partials(const double* __restrict__ part, int count, double* out) {
@@ -198,6 +251,28 @@ __global__ __launch_bounds__(256) void k_sum_partials(const double* __restrict__
   if (threadIdx.x == 0) *out = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// STEIN_FLAG_KSD: k_sum_partials over the partial sets [gridDim.x][count] (|phi|^2, S, S_diag): workgroup k sums set k into
+// out[k], in that kernel's order
+__global__ __launch_bounds__(256) void k_sum_partial_sets(const double* __restrict__ part, int count, double* out) {
+  __shared__ double red[4];
+  const double* p = part + (size_t)blockIdx.x * count;
+  double s = 0.0;
+  for (int i = threadIdx.x; i < count; i += 256) s += p[i];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) out[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// the |phi|^2 partials of a finish pass (and with STEIN_FLAG_KSD the S / S_diag partials behind them) -> sqnorm_out[0 (.. 2)]
+static int sum_partials(const double* part, int count, bool ksd, double* out, hipStream_t s) {
+  if (ksd) hipLaunchKernelGGL(k_sum_partial_sets, dim3(3), dim3(256), 0, s, part, count, out);
+  else hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, part, count, out);
+  LAUNCH_CHECK(ksd ? "k_sum_partial_sets" : "k_sum_partials");
+  return STEIN_OK;
+}
+
 // ================================================================================================
 // host side
 // ================================================================================================
@@ -208,7 +283,7 @@ int stein_make_layout(int64_t n_local, int64_t n, int64_t d, int dtype, int flag
   if (d < 1 || n_local < 1 || n_local > n) return fail(STEIN_E_SHAPE, "bad shape n_local=%lld n=%lld d=%lld", (long long)n_local, (long long)n, (long long)d);
   if (n > (1ll << 30) || d > (1ll << 24) || n * d > (1ll << 40)) return fail(STEIN_E_SHAPE, "shape too large");
   if (dtype != STEIN_F32 && dtype != STEIN_BF16) return fail(STEIN_E_UNSUPPORTED, "dtype %d", dtype);
-  if (flags & ~(STEIN_FLAG_X3 | STEIN_FLAG_TIMING | STEIN_FLAG_TILED | STEIN_FLAG_NO_WINDOW | STEIN_FLAG_RANK_WINDOW | STEIN_FLAG_TILE_DISTANCE | STEIN_FLAG_TIMING_CONTRACT)) return fail(STEIN_E_BADARG, "unknown flags 0x%x", flags);
+  if (flags & ~(STEIN_FLAG_X3 | STEIN_FLAG_TIMING | STEIN_FLAG_TILED | STEIN_FLAG_NO_WINDOW | STEIN_FLAG_RANK_WINDOW | STEIN_FLAG_TILE_DISTANCE | STEIN_FLAG_TIMING_CONTRACT | STEIN_FLAG_KSD)) return fail(STEIN_E_BADARG, "unknown flags 0x%x", flags);
   L->ld_dist = (int64_t)align_up((size_t)n, 64);
   L->tiles_m = (n_local + BM - 1) / BM;
   L->cblocks = (d + BN - 1) / BN;
@@ -254,9 +329,10 @@ int stein_make_layout(int64_t n_local, int64_t n, int64_t d, int dtype, int flag
   put(STEIN_WS_PART_G, (size_t)split * n_local * d * 4);
   put(STEIN_WS_PART_T, (size_t)split * n_local * d * 4);
   put(STEIN_WS_PART_RS, (size_t)split * n_local * 4);
-  {  // k_phi_finish writes sq_blocks partials, the one-kernel small path one per 32 parameter columns
+  {  // k_phi_finish writes sq_blocks partials, the one-kernel small path one per 32 parameter columns; STEIN_FLAG_KSD: three
+     // sets of them (|phi|^2, S, S_diag)
     const int64_t small = (d + 31) / 32;
-    put(STEIN_WS_SQPART, (size_t)(sqb > small ? sqb : small) * 8);
+    put(STEIN_WS_SQPART, (size_t)(sqb > small ? sqb : small) * 8 * ((flags & STEIN_FLAG_KSD) ? 3 : 1));
   }
   // slots | entries | rank-summed table.  Empty when the fused call will take the one-kernel path (stein_small.hip never
   // touches it): the reference's own example sizes then carry a few hundred KB of workspace instead of 16.5 MB
@@ -432,10 +508,12 @@ extern "C" int stein_contract_partial(const float* dist, int64_t ld_dist, const 
                                                  v.OG, v.OT, v.RS, n, d, n_local, s);
 }
 
-static int contract_finish_impl(const void* theta_all, int64_t n, int64_t d, int64_t row0, int64_t n_local,
-                                int dtype, const float* h2_dev, float* phi_local, double* sqnorm_out,
+// score_all: read only with STEIN_FLAG_KSD in flags (the statistic's score rows; sqnorm_out is then double[3])
+static int contract_finish_impl(const void* theta_all, const void* score_all, int64_t n, int64_t d, int64_t row0,
+                                int64_t n_local, int dtype, const float* h2_dev, float* phi_local, double* sqnorm_out,
                                 float* dK_out, void* workspace, size_t ws_bytes, int flags, void* stream, HistSync* fuse_done) {
-  if (!theta_all || !h2_dev || !phi_local || !sqnorm_out || !workspace) return fail(STEIN_E_BADARG, "NULL pointer");
+  const bool ksd = (flags & STEIN_FLAG_KSD) != 0;
+  if (!theta_all || !h2_dev || !phi_local || !sqnorm_out || !workspace || (ksd && !score_all)) return fail(STEIN_E_BADARG, "NULL pointer");
   if (dtype != STEIN_F32 && dtype != STEIN_BF16) return fail(STEIN_E_UNSUPPORTED, "contract: dtype %d", dtype);
   if (row0 < 0 || row0 + n_local > n) return fail(STEIN_E_SHAPE, "bad row block");
   SteinLayout L;
@@ -446,29 +524,34 @@ static int contract_finish_impl(const void* theta_all, int64_t n, int64_t d, int
   hipStream_t s = (hipStream_t)stream;
   auto al16 = [](const void* p) { return ((uintptr_t)p & 15u) == 0; };
   const size_t tsz = dtype == STEIN_BF16 ? 2 : 4;
-  const int vec = (d % 4 == 0) && al16(v.OG) && al16(v.OT) && al16(phi_local) && al16(dK_out) &&
-                  (((uintptr_t)theta_all + (size_t)row0 * d * tsz) & (4 * tsz - 1)) == 0;
-  if (dtype == STEIN_BF16)
-    hipLaunchKernelGGL(k_phi_finish<unsigned short>, dim3((unsigned)L.sq_blocks), dim3(256), 0, s, v.OG, v.OT, v.RS,
-                       (const unsigned short*)theta_all, h2_dev, phi_local, dK_out, v.SQ, (int)n, (int)d, (int)row0,
-                       (int)n_local, (int)L.split, vec, fuse_done, sqnorm_out);
-  else
-    hipLaunchKernelGGL(k_phi_finish<float>, dim3((unsigned)L.sq_blocks), dim3(256), 0, s, v.OG, v.OT, v.RS,
-                       (const float*)theta_all, h2_dev, phi_local, dK_out, v.SQ, (int)n, (int)d, (int)row0, (int)n_local,
-                       (int)L.split, vec, fuse_done, sqnorm_out);
-  LAUNCH_CHECK("k_phi_finish");
-  if (!fuse_done) {
-    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, v.SQ, (int)L.sq_blocks, sqnorm_out);
-    LAUNCH_CHECK("k_sum_partials");
+  auto rows_aligned = [&](const void* p) { return (((uintptr_t)p + (size_t)row0 * d * tsz) & (4 * tsz - 1)) == 0; };
+  const int vec = (d % 4 == 0) && al16(v.OG) && al16(v.OT) && al16(phi_local) && al16(dK_out) && rows_aligned(theta_all) &&
+                  (!ksd || rows_aligned(score_all));
+  auto launch = [&](auto tin, auto ksd_tag) {
+    using TIN = decltype(tin);
+    hipLaunchKernelGGL((k_phi_finish<TIN, decltype(ksd_tag)::value>), dim3((unsigned)L.sq_blocks), dim3(256), 0, s, v.OG,
+                       v.OT, v.RS, (const TIN*)theta_all, h2_dev, phi_local, dK_out, v.SQ, (int)n, (int)d, (int)row0,
+                       (int)n_local, (int)L.split, vec, fuse_done, sqnorm_out, (const TIN*)score_all);
+  };
+  if (dtype == STEIN_BF16) {
+    if (ksd) launch((unsigned short)0, std::true_type());
+    else launch((unsigned short)0, std::false_type());
+  } else {
+    if (ksd) launch(0.f, std::true_type());
+    else launch(0.f, std::false_type());
   }
-  return STEIN_OK;
+  LAUNCH_CHECK("k_phi_finish");
+  return fuse_done ? STEIN_OK : sum_partials(v.SQ, (int)L.sq_blocks, ksd, sqnorm_out, s);
 }
 
 extern "C" int stein_contract_finish(const void* theta_all, int64_t n, int64_t d, int64_t row0, int64_t n_local,
                                      int dtype, const float* h2_dev, float* phi_local, double* sqnorm_out,
                                      float* dK_out, void* workspace, size_t ws_bytes, int flags, void* stream) {
-  return contract_finish_impl(theta_all, n, d, row0, n_local, dtype, h2_dev, phi_local, sqnorm_out, dK_out, workspace,
-                              ws_bytes, flags, stream, nullptr);
+  if (flags & STEIN_FLAG_KSD)
+    return fail(STEIN_E_BADARG, "STEIN_FLAG_KSD: stein_contract_finish has no score operand; the statistic comes from "
+                                "stein_svgd_phi, stein_rank_finish or stein_rank_step");
+  return contract_finish_impl(theta_all, nullptr, n, d, row0, n_local, dtype, h2_dev, phi_local, sqnorm_out, dK_out,
+                              workspace, ws_bytes, flags, stream, nullptr);
 }
 
 extern "C" int stein_kernel_contract(const float* dist, int64_t ld_dist, const void* theta_all, const void* score_all,
@@ -476,6 +559,9 @@ extern "C" int stein_kernel_contract(const float* dist, int64_t ld_dist, const v
                                      const float* h2_dev, float* phi_local, double* sqnorm_out, float* dK_out,
                                      const void* x3_planes, void* workspace, size_t ws_bytes, int dist_flags,
                                      void* stream) {
+  if (dist_flags & STEIN_FLAG_KSD)
+    return fail(STEIN_E_BADARG, "STEIN_FLAG_KSD: stein_kernel_contract takes distance flags only; the statistic comes from "
+                                "stein_svgd_phi, stein_rank_finish or stein_rank_step");
   int rc = stein_contract_partial(dist, ld_dist, theta_all, score_all, n, d, row0, n_local, dtype, h2_dev, x3_planes,
                                   workspace, ws_bytes, dist_flags, stream);
   if (rc) return rc;
@@ -516,9 +602,9 @@ static int rank_views(int64_t n, int64_t d, int64_t row0, int64_t n_local, int d
                       int flags, StepViews* v) {
   if (!workspace) return fail(STEIN_E_BADARG, "NULL pointer");
   if (row0 < 0 || n_local < 1 || row0 + n_local > n) return fail(STEIN_E_SHAPE, "bad row block");
-  if (flags & ~(STEIN_FLAG_X3 | STEIN_FLAG_TILED | STEIN_FLAG_RANK_WINDOW | STEIN_FLAG_TIMING)) return fail(STEIN_E_BADARG, "unknown flags 0x%x", flags);
+  if (flags & ~(STEIN_FLAG_X3 | STEIN_FLAG_TILED | STEIN_FLAG_RANK_WINDOW | STEIN_FLAG_TIMING | STEIN_FLAG_KSD)) return fail(STEIN_E_BADARG, "unknown flags 0x%x", flags);
   SteinLayout L;
-  int rc = stein_make_layout(n_local, n, d, dtype, (flags & (STEIN_FLAG_X3 | STEIN_FLAG_TILED)) | STEIN_FLAG_TILED, &L);
+  int rc = stein_make_layout(n_local, n, d, dtype, (flags & (STEIN_FLAG_X3 | STEIN_FLAG_TILED | STEIN_FLAG_KSD)) | STEIN_FLAG_TILED, &L);
   if (rc) return rc;
   if (dtype == STEIN_BF16 && !(flags & STEIN_FLAG_X3)) return fail(STEIN_E_UNSUPPORTED, "bf16 inputs need STEIN_FLAG_X3");
   if (ws_bytes < L.total) return fail(STEIN_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L.total);
@@ -592,8 +678,8 @@ extern "C" int stein_rank_finish(const void* theta_all, const void* score_all, i
                                    workspace, ws_bytes, 0, stream)))
     return rc;
   if ((rc = clk.mark(STEIN_T_FINISH, s))) return rc;
-  rc = stein_contract_finish(theta_all, n, d, row0, n_local, dtype, h2_dev, phi_local, sqnorm_out, dK_out, workspace,
-                             ws_bytes, v.planes ? STEIN_FLAG_X3 : 0, stream);
+  rc = contract_finish_impl(theta_all, score_all, n, d, row0, n_local, dtype, h2_dev, phi_local, sqnorm_out, dK_out,
+                            workspace, ws_bytes, (v.planes ? STEIN_FLAG_X3 : 0) | (flags & STEIN_FLAG_KSD), stream, nullptr);
   return rc ? rc : clk.mark(STEIN_T_NSTAGES, s);
 }
 
@@ -728,14 +814,12 @@ extern "C" int stein_svgd_phi(const void* theta_all, const void* score_all, int6
     for (int k = STEIN_T_DISTANCE; k <= STEIN_T_CONTRACT; ++k)
       if ((rc = clk.mark(k, s))) return rc;
     int nparts = 0;
+    const bool ksd = (flags & STEIN_FLAG_KSD) != 0;
     if ((rc = stein_small_phi((const float*)theta_all, (const float*)score_all, n, d, phi_local, h2_out, v.SQ, K_out,
-                              dK_out, &nparts, sqnorm_out, s)))
+                              dK_out, &nparts, sqnorm_out, ksd, s)))
       return rc;
     if ((rc = clk.mark(STEIN_T_FINISH, s))) return rc;
-    if (nparts) {   // d > 32: several workgroups, their partials are summed here
-      hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, (const double*)v.SQ, nparts, sqnorm_out);
-      LAUNCH_CHECK("k_sum_partials");
-    }
+    if (nparts && (rc = sum_partials(v.SQ, nparts, ksd, sqnorm_out, s))) return rc;   // d > 32: several workgroups' partials
     return clk.mark(STEIN_T_NSTAGES, s);
   }
   // The prologue carries the row norms and all set-up; kernels let their last workgroup do what a one-workgroup follow-up
@@ -762,8 +846,9 @@ extern "C" int stein_svgd_phi(const void* theta_all, const void* score_all, int6
                                    workspace, ws_bytes, df, stream)))
     return rc;
   if ((rc = clk.mark(STEIN_T_FINISH, s))) return rc;
-  if ((rc = contract_finish_impl(theta_all, n, d, row0, n_local, dtype, h2_out, phi_local, sqnorm_out, dK_out, workspace,
-                                 ws_bytes, v.planes ? STEIN_FLAG_X3 : 0, stream, (HistSync*)v.table)))
+  if ((rc = contract_finish_impl(theta_all, score_all, n, d, row0, n_local, dtype, h2_out, phi_local, sqnorm_out, dK_out,
+                                 workspace, ws_bytes, (v.planes ? STEIN_FLAG_X3 : 0) | (flags & STEIN_FLAG_KSD), stream,
+                                 (HistSync*)v.table)))
     return rc;
   return clk.mark(STEIN_T_NSTAGES, s);
 }

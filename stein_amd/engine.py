@@ -187,6 +187,8 @@ class SvgdEngine:
     group   : torch.distributed process group (None -> single rank).  n must divide evenly.
     stages  : backend implementing the staged calls; the product default is HipStages.
               (tests substitute a NumPy model to exercise the collective protocol on CPU/gloo.)
+    ksd     : also compute the kernelized Stein discrepancy of the particles under the step's own kernel and bandwidth
+              (STEIN_FLAG_KSD): stein_discrepancy() after a step.  Off by default; nothing else changes with it on.
     comm    : who issues the collectives of a sharded step.  "torch" (and "auto", the default): torch.distributed
               collectives between the rank segments -- the path every multi-rank test has run.  "native": the library,
               on its own RCCL communicator, the whole step one C call (stein_rank_step; 68 us of host time per step
@@ -197,7 +199,7 @@ class SvgdEngine:
     _full_distance_image = False   # set by scratch/ab.py for -DSTEIN_NO_UPPER builds (the mirrored image of round 1)
 
     def __init__(self, n, d, device="cuda", group=None, stages=None, x3=None, dtype=torch.float32, small=True,
-                 window=True, force_collectives=False, comm="auto", tile_distance=False, dist_window=None):
+                 window=True, force_collectives=False, comm="auto", tile_distance=False, dist_window=None, ksd=False):
         self.n, self.d = int(n), int(d)
         # dtype of the theta / score tensors handed to compute_phi: float32, or bfloat16 (BASELINE config 2: the
         # values are used as they are, K is rounded to bf16, one bf16 MFMA per product, fp32 accumulation)
@@ -218,6 +220,12 @@ class SvgdEngine:
         # panel-resident kernel that large blocks with d <= 256 take by default, stein_dpanel.hip)
         self.flags = ((_lib.FLAG_X3 if self.x3 else 0) | (0 if small else _lib.FLAG_TILED) |
                       (0 if window else _lib.FLAG_NO_WINDOW) | (_lib.FLAG_TILE_DISTANCE if tile_distance else 0))
+        # ksd=True: the step also sums the kernelized Stein discrepancy (sqnorm grows to [|phi|^2, S, S_diag], see _sums);
+        # only the fused call and the rank segments compute it
+        self.ksd = bool(ksd)
+        if self.ksd:
+            self.flags |= _lib.FLAG_KSD
+        self._ksd_ready = False
         # several ranks: use the speculative median window (ONE 512 KB all-reduce and a hit-flag read-back per step
         # instead of three histogram all-reduces and two passes over the local distance block) when the block is large
         # enough for that to pay (>= 2^24 entries; every collective costs ~30 us of host time from Python, and the
@@ -236,6 +244,8 @@ class SvgdEngine:
         # force_collectives runs it on a one-rank group as well -- how the tests drive every collective through RCCL on
         # a single card.
         self.sharded = self.world > 1 or (group is not None and force_collectives)
+        if self.ksd and not hasattr(self.stages, "rank_finish"):
+            raise ValueError("ksd=True needs stages with the fused call and the rank segments (HipStages)")
         if self.n < 2:
             raise ValueError("n_particles = %d: the median-heuristic bandwidth divides by ln(n); need n >= 2" % self.n)
         if self.n % self.world:
@@ -258,7 +268,10 @@ class SvgdEngine:
         self.phi = torch.empty(self.n_local, self.d, dtype=torch.float32, device=dev)
         self.h2 = torch.zeros(1, dtype=torch.float32, device=dev)
         self.median = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.sqnorm = torch.zeros(1, dtype=torch.float64, device=dev)
+        # |phi|^2 and, with ksd, the two Stein discrepancy sums S and S_diag behind it (include/steinhip.h, STEIN_FLAG_KSD);
+        # sqnorm stays the one-element view the optimizer apply reads
+        self._sums = torch.zeros(3, dtype=torch.float64, device=dev)
+        self.sqnorm = self._sums[:1]
         if self.sharded and hasattr(self.stages, "spec_begin"):
             self.dist_window = bool(dist_window) if dist_window is not None else self.n_local * self.n >= (1 << 24)
         if self.sharded:
@@ -434,7 +447,7 @@ class SvgdEngine:
         leaves no bubble on the stream."""
         import torch.distributed as dist
         st, n, d, nl, row0, ws = self.stages, self.n, self.d, self.n_local, self.row0, self.ws
-        flags = (self.flags & _lib.FLAG_X3) | (_lib.FLAG_RANK_WINDOW if self.dist_window else 0)
+        flags = (self.flags & (_lib.FLAG_X3 | _lib.FLAG_KSD)) | (_lib.FLAG_RANK_WINDOW if self.dist_window else 0)
         T_all, G_all, planes = self.T_all, self.G_all, self.planes
         # theta first (collectives of one group run in issue order); the score rows are not needed before the
         # contraction, so their all-gather is asynchronous and runs beside the distance pass
@@ -472,8 +485,24 @@ class SvgdEngine:
             score_planes()
         st.rank_finish(T_all, G_all, n, d, row0, nl, self.h2, self.phi, self.sqnorm, dK_out, ws,
                        flags | (_lib.FLAG_TIMING if timing else 0))
-        dist.all_reduce(self.sqnorm, op=dist.ReduceOp.SUM, group=self.group)
+        dist.all_reduce(self._sums if self.ksd else self.sqnorm, op=dist.ReduceOp.SUM, group=self.group)
         return self.phi
+
+    def stein_discrepancy(self, statistic="u"):
+        """KSD^2 of the particles of the last compute_phi (ksd=True): a 0-d float64 device tensor, no host sync.
+        statistic "u": the U-statistic  sum_{i != j} u_ij / (n (n - 1))  (unbiased, may be slightly negative near
+        convergence); "v": the V-statistic  sum_ij u_ij / n^2.  u_ij is the Stein kernel of the step's RBF kernel with the
+        step's median bandwidth (include/steinhip.h, STEIN_FLAG_KSD)."""
+        if not self.ksd:
+            raise RuntimeError("the engine was built without ksd=True")
+        if not self._ksd_ready:
+            raise RuntimeError("no step has been computed yet")
+        n = float(self.n)
+        if statistic == "v":
+            return self._sums[1] / (n * n)
+        if statistic == "u":
+            return (self._sums[1] - self._sums[2]) / (n * (n - 1.0))
+        raise ValueError("statistic must be 'u' or 'v'")
 
     def compute_phi(self, theta_local, score_local, K_out=None, dK_out=None, mark=None, timing=False):
         """theta_local, score_local: [n_local, d] float32 contiguous device tensors (this rank's rows).
@@ -489,8 +518,13 @@ class SvgdEngine:
         _lib.timing_read): every stage of the fused call on a single rank, the contraction and the finish pass in a
         sharded step.  timing="contract" (single rank): only the two events around the contraction -- every event between two
         kernels costs the step ~3 us, so a loop that is itself being timed should carry as few as it can.
+        With ksd=True the step also leaves the Stein discrepancy sums (stein_discrepancy()); the staged calls (mark=, or a
+        sharded step with K_out) do not compute them and are refused.
         """
         st, n, d, nl = self.stages, self.n, self.d, self.n_local
+        if self.ksd and (mark is not None or (self.sharded and K_out is not None)):
+            raise ValueError("ksd=True: the staged calls (mark=, or K_out on a sharded engine) do not compute the Stein "
+                             "discrepancy; use the fused call / rank segments")
         for name, t in (("theta", theta_local), ("score", score_local)):
             if tuple(t.shape) != (nl, d) or t.dtype != self.dtype or not t.is_contiguous():
                 raise ValueError("%s must be a contiguous %s [%d, %d] tensor, got %s %s" %
@@ -501,16 +535,19 @@ class SvgdEngine:
                         (_lib.FLAG_TIMING_CONTRACT if timing == "contract" else 0))
             self._have_dist = not self._one_kernel
             self.dist_upper = self.x3 and self._have_dist and not SvgdEngine._full_distance_image
+            self._ksd_ready = self.ksd
             return self.phi
         if self.sharded and mark is None and K_out is None and self._comm is not None:
-            flags = ((self.flags & _lib.FLAG_X3) | (_lib.FLAG_RANK_WINDOW if self.dist_window else 0) |
+            flags = ((self.flags & (_lib.FLAG_X3 | _lib.FLAG_KSD)) | (_lib.FLAG_RANK_WINDOW if self.dist_window else 0) |
                      (_lib.FLAG_TIMING if timing else 0))
             self.window_hit = st.rank_step(self._comm, theta_local, score_local, self.T_all, self.G_all, n, d, self.phi,
                                            self.h2, self.median, self.sqnorm, dK_out, self.ws, flags)
             self._have_dist, self.dist_upper = True, False
+            self._ksd_ready = self.ksd
             return self.phi
         if self.sharded and mark is None and K_out is None and hasattr(st, "rank_begin"):
             self._have_dist, self.dist_upper = True, False
+            self._ksd_ready = self.ksd
             return self._sharded_step(theta_local, score_local, dK_out, timing)
         if mark is None:
             def mark(label):

@@ -28,7 +28,7 @@ class AbstractSteinSampler:
     INIT_SCALE = 0.01  # abstract_stein_sampler.py:72
 
     def __init__(self, n_particles, log_p, theta=None, *, model_vars=None, device="cuda", dtype=torch.float32,
-                 group=None, seed=None, kernel_dtype=torch.float32, x3=None):
+                 group=None, seed=None, kernel_dtype=torch.float32, x3=None, ksd=False):
         """
         n_particles : total number of particles n (across all ranks).
         log_p       : see SteinSampler.
@@ -42,6 +42,7 @@ class AbstractSteinSampler:
         kernel_dtype: torch.float32 (default) or torch.bfloat16 -- what theta and the score are rounded to when they
                       are fed to the kernel / contraction (the reference rounds fp64 -> fp32 at that point).
         x3          : None (default: split-fp16 GEMMs on the 16-bit matrix cores) / False (fp32-input MFMA GEMMs); see engine.SvgdEngine.
+        ksd         : also compute the kernelized Stein discrepancy in every step (stein_discrepancy()); see engine.SvgdEngine.
         """
         self.n_particles = int(n_particles)
         self.log_p = log_p
@@ -105,7 +106,7 @@ class AbstractSteinSampler:
         self.n_params = self.theta_matrix.shape[1]
         self.kernel_dtype = kernel_dtype
         self.engine = SvgdEngine(self.n_particles, self.n_params, device=self.device, group=group, x3=x3,
-                                 dtype=kernel_dtype)
+                                 dtype=kernel_dtype, ksd=ksd)
         self._theta32 = (self.theta_matrix if dtype == kernel_dtype else
                          torch.empty(self.n_local, self.n_params, dtype=kernel_dtype, device=self.device))
 
@@ -173,6 +174,18 @@ class AbstractSteinSampler:
         G = self._score_to_device(grads_array)
         phi = self.engine.compute_phi(T, G)
         return phi.double().cpu().numpy() if was_numpy else phi.clone()
+
+    def stein_discrepancy(self, statistic="u"):
+        """KSD^2 (a float) of the particles at the last step's score evaluation, i.e. before that step's update, under the
+        step's RBF kernel and median bandwidth: statistic "u" (U-statistic, the default) or "v" (V-statistic).  Needs
+        ksd=True and a step through the package's own kernel; reading it synchronises with the device.  Sharded: the
+        statistic of all n particles, the same on every rank."""
+        if not self.engine.ksd:
+            raise RuntimeError("build the sampler with ksd=True to get the Stein discrepancy")
+        if self._foreign_kernel() is not None:
+            raise RuntimeError("a user-supplied kernel computes phi on the host: the Stein discrepancy is only computed "
+                               "with the package's own RBF kernel")
+        return float(self.engine.stein_discrepancy(statistic).item())
 
     def update_particles(self, grads_array):
         """One SVGD step from the score matrix: phi, norm clip, optimizer apply
