@@ -218,6 +218,43 @@ __device__ __forceinline__ void ksd_terms(float g, float og, float ot, float th,
   sd += gd * gd + ih;
 }
 
+// ---- arithmetic that the fused call and the staged calls must do bit for bit alike: written once -------------------------
+__device__ __forceinline__ float elem_f32(const float* p) { return *p; }
+__device__ __forceinline__ float elem_f32(const unsigned short* p) { return __uint_as_float((u32)*p << 16); }   // bf16 bits
+
+// |row|^2 of one row of d elements by one wave: lane-strided fmaf chain, then the xor-shuffle sum (every lane returns it).
+// The row norms r_i of k_rownorms (staged calls) and of prologue_body (fused call).
+template <typename TIN>
+__device__ __forceinline__ float wave_row_sqnorm(const TIN* row, int d, int lane) {
+  float s = 0.f;
+  for (int k = lane; k < d; k += 64) {
+    const float x = elem_f32(row + k);
+    s = fmaf(x, x, s);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  return s;
+}
+
+// Ordered fp64 sum of N values per thread over a 256-thread workgroup: xor-shuffle over each wave, lane 0 of wave w writes
+// red[4 k + w], ONE barrier for all N, and every thread returns with v[k] = (red[4k] + red[4k+1]) + (red[4k+2] + red[4k+3]).
+// The |phi|^2 / KSD sums of k_phi_finish (block partials and its last workgroup's total) and of k_sum_partial_sets.
+// red: 4 N doubles of LDS that no thread is still reading.
+template <int N>
+__device__ __forceinline__ void block_sum256(double (&v)[N], double* red) {
+#pragma unroll
+  for (int k = 0; k < N; ++k)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) red[4 * k + (threadIdx.x >> 6)] = v[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < N; ++k) v[k] = (red[4 * k] + red[4 * k + 1]) + (red[4 * k + 2] + red[4 * k + 3]);
+}
+
 __device__ __forceinline__ u64 load_fresh(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ u32 load_fresh(const u32* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
@@ -578,7 +615,6 @@ struct SteinLayout {
   size_t off[STEIN_WS_NSECTIONS];
   size_t total;
   int64_t ld_dist, split, sq_blocks, jchunk, tiles_m, cblocks;
-  int64_t phi_wide;   // split-precision contraction: 1 = 64-row x 512-column workgroups (k_phi_x3fs<NP, 4>), 0 = 128 x 256
   // split-precision planes (flags & STEIN_FLAG_X3): 16-bit [3 slots][rows][k] each, tile-major
   int64_t x3_rows, x3_dk;   // row-major theta planes: x3_rows x x3_dk  (distance operands)
   int64_t x3_dc, x3_nk;     // transposed planes of theta and of the score: x3_dc x x3_nk  (contraction B operand)
@@ -636,8 +672,6 @@ struct PrologueArgs {
   u32* hsync; int hsync_words;   // HistSync of k_hist_all (zeroed here)
 };
 constexpr int PRO_INIT_BLOCKS = 16;   // (k_prologue's grid: one workgroup per four rows + these; any grid works)
-__device__ __forceinline__ float prologue_elem(const float* p) { return *p; }
-__device__ __forceinline__ float prologue_elem(const unsigned short* p) { return __uint_as_float((u32)*p << 16); }   // bf16 bits
 template <typename TIN>
 __device__ __forceinline__ void prologue_body(const TIN* __restrict__ T, const PrologueArgs& a, int b, int nb) {
   const int gt = b * 256 + (int)threadIdx.x, gn = nb * 256;
@@ -651,14 +685,7 @@ __device__ __forceinline__ void prologue_body(const TIN* __restrict__ T, const P
   median_init_body(gt, gn, a.st, a.sp, a.total, a.hist, a.slots, a.allow_window);
   const int lane = threadIdx.x & 63;
   for (int row = gt >> 6; row < a.n; row += gn >> 6) {
-    const TIN* rp = T + (size_t)row * a.d;
-    float s = 0.f;
-    for (int k = lane; k < a.d; k += 64) {
-      const float x = prologue_elem(rp + k);
-      s = fmaf(x, x, s);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    const float s = wave_row_sqnorm(T + (size_t)row * a.d, a.d, lane);
     if (lane == 0) a.r[row] = s;
   }
 }

@@ -247,8 +247,8 @@ __global__ __launch_bounds__(SM_THREADS) void k_svgd_small(const float* __restri
     }
   }
   __syncthreads();
-  // A wave owns the rows wave + 16 r (r < RB = ceil(n / 16)).  All RB rows advance together: per four j one 16-byte broadcast read of K per row and the staged score /
-  // theta entries once, for 8 RB FMAs -- one row at a time read three words per two FMAs and the stage was bound by LDS
+  // A wave owns the rows wave + 16 r (r < RW = ceil(n / 16)).  All RW rows advance together: per four j one 16-byte broadcast read of K per row and the staged score /
+  // theta entries once, for 8 RW FMAs -- one row at a time read three words per two FMAs and the stage was bound by LDS
   // bandwidth (61 k of the kernel's 144 k cycles at n = 128).
   double sq = 0.0;
   double ks = 0.0, kd = 0.0;   // KSD: this thread's shares of S and S_diag
@@ -257,28 +257,28 @@ __global__ __launch_bounds__(SM_THREADS) void k_svgd_small(const float* __restri
   // Lanes: CLW columns x 64 / CLW slices of the j range (slice starts are multiples of 4).  CLW = 32 unless the
   // workgroup has few columns (d = 1 ... 16: the reference's regression examples), where 32 column lanes would spend
   // the stage multiplying padding.
-  auto phi_rows = [&](auto rb_tag, auto clw_tag) {
-    constexpr int RB = decltype(rb_tag)::value, CLW = decltype(clw_tag)::value, JS = 64 / CLW;
+  auto phi_rows = [&](auto rw_tag, auto clw_tag) {
+    constexpr int RW = decltype(rw_tag)::value, CLW = decltype(clw_tag)::value, JS = 64 / CLW;
     const int cl = lane & (CLW - 1), jh = lane / CLW;
     const int jq = (((n + JS - 1) / JS) + 3) & ~3;
     const int j0 = min(n, jh * jq), j1 = min(n, j0 + jq);
-    float kg[RB], kt[RB];
-    const float* krow[RB];
+    float kg[RW], kt[RW];
+    const float* krow[RW];
 #pragma unroll
-    for (int r = 0; r < RB; ++r) {
+    for (int r = 0; r < RW; ++r) {
       kg[r] = kt[r] = 0.f;
       krow[r] = Dm + min(wave + (SM_THREADS / 64) * r, n - 1) * ldn;   // rows past n repeat row n - 1 (never stored)
     }
     int j = j0;
     for (; j + 3 < j1; j += 4) {
-      float4 k4[RB];
+      float4 k4[RW];
 #pragma unroll
-      for (int r = 0; r < RB; ++r) k4[r] = *reinterpret_cast<const float4*>(krow[r] + j);
+      for (int r = 0; r < RW; ++r) k4[r] = *reinterpret_cast<const float4*>(krow[r] + j);
 #pragma unroll
       for (int jj = 0; jj < 4; ++jj) {
         const float g = gs[(j + jj) * SM_COLS + cl], tt = ts[(j + jj) * (SM_COLS + 1) + cl];
 #pragma unroll
-        for (int r = 0; r < RB; ++r) {
+        for (int r = 0; r < RW; ++r) {
           const float k = jj == 0 ? k4[r].x : (jj == 1 ? k4[r].y : (jj == 2 ? k4[r].z : k4[r].w));
           kg[r] = fmaf(k, g, kg[r]);
           kt[r] = fmaf(k, tt, kt[r]);
@@ -288,14 +288,14 @@ __global__ __launch_bounds__(SM_THREADS) void k_svgd_small(const float* __restri
     for (; j < j1; ++j) {
       const float g = gs[j * SM_COLS + cl], tt = ts[j * (SM_COLS + 1) + cl];
 #pragma unroll
-      for (int r = 0; r < RB; ++r) {
+      for (int r = 0; r < RW; ++r) {
         const float k = krow[r][j];
         kg[r] = fmaf(k, g, kg[r]);
         kt[r] = fmaf(k, tt, kt[r]);
       }
     }
 #pragma unroll
-    for (int r = 0; r < RB; ++r) {
+    for (int r = 0; r < RW; ++r) {
       float sg = kg[r], st = kt[r];
 #pragma unroll
       for (int o = CLW; o < 64; o <<= 1) { sg += __shfl_xor(sg, o); st += __shfl_xor(st, o); }
@@ -311,10 +311,10 @@ __global__ __launch_bounds__(SM_THREADS) void k_svgd_small(const float* __restri
       }
     }
   };
-  auto phi_cols = [&](auto rb_tag) {   // workgroup-uniform choices
-    if (ncols <= 8) phi_rows(rb_tag, std::integral_constant<int, 8>());
-    else if (ncols <= 16) phi_rows(rb_tag, std::integral_constant<int, 16>());
-    else phi_rows(rb_tag, std::integral_constant<int, 32>());
+  auto phi_cols = [&](auto rw_tag) {   // workgroup-uniform choices
+    if (ncols <= 8) phi_rows(rw_tag, std::integral_constant<int, 8>());
+    else if (ncols <= 16) phi_rows(rw_tag, std::integral_constant<int, 16>());
+    else phi_rows(rw_tag, std::integral_constant<int, 32>());
   };
   if (n <= 2 * (SM_THREADS / 64)) phi_cols(std::integral_constant<int, 2>());
   else if (n <= 4 * (SM_THREADS / 64)) phi_cols(std::integral_constant<int, 4>());

@@ -239,9 +239,6 @@ __global__ __launch_bounds__(256) void k_make_scales(const u32* __restrict__ cma
 //   R  != NULL: tile-major image with rows = X rows (dk / 32 k tiles per row block), fragment order, rows < r_rows, k < dk
 //   Tt != NULL: tile-major image with rows = X columns (nk / 32 k tiles per row block), pre-swizzled, rows < dc, k < nk
 // The grid covers the padded extents; out-of-range source entries are written as zero.
-__device__ __forceinline__ float load_as_f32(const float* p) { return *p; }
-__device__ __forceinline__ float load_as_f32(const u16* p) { return __uint_as_float((u32)*p << 16); }   // bf16 bits
-
 // TIN = float (KIND 2 or 3) or u16 = bf16 bits (KIND 1).  sc_all scales the row-major image, sc_col[c] column c of the
 // transposed one (both powers of two; 1 unless KIND 2).
 // blockIdx.z = 0: theta (row-major image R and transposed image Tt0), 1: score (transposed image Tt1 only; the grid is
@@ -280,7 +277,7 @@ __global__ __launch_bounds__(256) void k_split(const TIN* __restrict__ X0, const
     const int row = row0 + lr + 16 * p, col = col0 + lc;
     float v[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) v[q] = (row < n && col + q < d) ? load_as_f32(X + (size_t)row * d + col + q) : 0.f;
+    for (int q = 0; q < 4; ++q) v[q] = (row < n && col + q < d) ? elem_f32(X + (size_t)row * d + col + q) : 0.f;
     if (R && row < r_rows && col < dk) {   // col % 4 == 0: the 4 entries stay inside one 32-wide k tile
       u32 wa[3], wb[3];
       split_pair<KIND>(v[0] * sa, v[1] * sa, wa);
@@ -470,32 +467,28 @@ constexpr int FS_THREADS = 768;
 // order per wave.  After every change here: check in the .s that no v_mov / spill touches a destination register between
 // its load and its wait.
 // (stream_load16 / stream_wait: stein_x3_dev.h)
-// k tiles per pipeline stage (even: tile parity picks the register set) and the LDS of one k tile (NP planes, packed)
-// RB = 16-row blocks of the workgroup's tile: 8 -> 128 rows x 256 columns of [G | theta]; 4 -> 64 rows x 512 columns: the
-// P tile, whose exp / split work shares the SIMDs' issue slots with the MFMAs, is then built once per 512 columns, and
-// each D tile is read by one workgroup only.  The MFMA count per k tile and wave is the same (RB x CJ x products = 48).
-template <int NP, int RB> struct FsGeom {
-  static constexpr int KT = 4;                        // 2 stages x KT x NP x 8 KB: 128 KB (NP 2), 64 KB (NP 1); half for RB 4
-  static constexpr int ROWS = RB * 16;
-  static constexpr int PLN = ROWS * XROW;             // one plane of one k tile: [ROWS][64 B]
-  static constexpr int KTB = NP * PLN;                // one k tile in LDS: NP planes
-  static constexpr int STAGE = KT * KTB;
-  static constexpr int CJ = 16 / RB;                  // 16-column blocks per matrix wave (8 waves: 256 or 512 columns)
-  static constexpr int PR = ROWS / 32;                // producer: rows lr + 32 p per thread and tile (4 columns each)
-};
+// The workgroup's tile: 128 rows x 256 columns of [G | theta].  A matrix wave owns the 8 sixteen-row blocks x 2
+// sixteen-column blocks of its 32 columns (8 x 2 x products = 48 MFMAs per k tile and wave for NP 2); a producer thread
+// holds 4 rows x 4 columns of every k tile.  (A 64-row x 512-column form, which builds the P tile once per 512 columns,
+// was measured in round 2 -- equal within 1 % -- and removed)
+constexpr int FS_KT = 4;                 // k tiles per pipeline stage (even: tile parity picks the register set)
+constexpr int FS_ROWS = 128;
+constexpr int FS_IB = FS_ROWS / 16;      // 16-row blocks of the tile
+constexpr int CJ = 2;                    // 16-column blocks per matrix wave (8 waves: 256 columns)
+constexpr int PR = FS_ROWS / 32;         // producer: rows lr + 32 p per thread and tile (4 columns each)
+constexpr int PLN = FS_ROWS * XROW;      // one plane of one k tile in LDS: [128][64 B]
 
-template <int NP, int RB>
+template <int NP>
 __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict__ D, long ldD,
                                                          const u16* __restrict__ Gt3, const u16* __restrict__ Tt3,
                                                          long ntj, const float* __restrict__ h2p,
                                                          float* __restrict__ OG, float* __restrict__ OT,
                                                          float* __restrict__ RS, int n, int d, int n_local,
-                                                         int tiles_m, int cblocks, int gblocks, int split,
-                                                         int jchunk, const float* __restrict__ sc, int dc,
-                                                         int upper) {
-  // cblocks: workgroups per row tile (grid); gblocks: 128-column blocks per matrix (G and theta each)
-  using Geo = FsGeom<NP, RB>;
-  constexpr int FS_KT = Geo::KT, FS_KTB = Geo::KTB, FS_STAGE = Geo::STAGE, PLN = Geo::PLN, CJ = Geo::CJ, PR = Geo::PR;
+                                                         int tiles_m, int cblocks, int split, int jchunk,
+                                                         const float* __restrict__ sc, int dc, int upper) {
+  // cblocks: workgroups per row tile = 128-column blocks per matrix (G and theta each; a workgroup takes one of each pair)
+  constexpr int FS_KTB = NP * PLN;            // one k tile in LDS: NP planes, packed
+  constexpr int FS_STAGE = FS_KT * FS_KTB;    // 2 stages x FS_KT x NP x 8 KB: 128 KB (NP 2), 64 KB (NP 1)
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * FS_STAGE];
 
   const int logical = xcd_remap(blockIdx.x, gridDim.x);
@@ -516,7 +509,7 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
     cb = l2 % cblocks;
     tile_m = l2 / cblocks;
   }
-  const int i0 = tile_m * Geo::ROWS;
+  const int i0 = tile_m * FS_ROWS;
   const int jbeg = z * jchunk;
   const int jend = min(n, jbeg + jchunk);
   const int ntile = jend > jbeg ? (jend - jbeg + BK - 1) / BK : 0;
@@ -539,7 +532,7 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
   // stages apart (5 on average), where the memory-side cache still holds the tile.  The row tiles of an XCD keep walking the
   // SAME block at the same time, so V is shared in their L2 as before.
   const int group = cblocks <= 32 ? 32 / cblocks : 1;
-  const bool permute = RB == 8 && upper != 0 && jbeg == 0 && jend == n && (cblocks & (cblocks - 1)) == 0 && cblocks <= 4 &&
+  const bool permute = upper != 0 && jbeg == 0 && jend == n && (cblocks & (cblocks - 1)) == 0 && cblocks <= 4 &&
                        nstage * FS_KT == ntile && (nstage & (nstage - 1)) == 0 && nstage == tiles_m && nstage >= 2 * group;
   const int xmask = permute ? (tile_m & ~(group - 1)) : 0;
   auto stage_of = [&](int v) { return v ^ xmask; };   // (v = nstage, "the stage after the last", stays out of range)
@@ -554,7 +547,7 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
   // image with the same number of 8-byte stores: the matrix waves do not know the difference.  The choice is per pipeline
   // stage (FS_KT k tiles = 128 columns; the host keeps jbeg a multiple of 128, so a stage never straddles the diagonal
   // block): the first ntr stages of the j range are mirrored ones.
-  const bool up = RB == 8 && upper != 0;
+  const bool up = upper != 0;
   const int ntr = up ? max(0, min(nstage, (i0 - jbeg) / (FS_KT * BK))) : 0;
 
   const int t = threadIdx.x;
@@ -681,51 +674,49 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
     // v_pk_add_f32, and eight packed adds per k tile beside the MFMAs cost the launch 0.07 ms -- the library is built with
     // -fno-slp-vectorize, __graft_entry__.py.)
     auto produce_tr = [&](unsigned char* buf, const f32x4g (&rd)[PR]) {
-      if constexpr (RB == 8) {
-        float q[4][4];
+      float q[4][4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u)
+      for (int u = 0; u < 4; ++u)
 #pragma unroll
-          for (int e = 0; e < 4; ++e) q[u][e] = __builtin_fmaf(cexp, rd[u][e], pofs);
+        for (int e = 0; e < 4; ++e) q[u][e] = __builtin_fmaf(cexp, rd[u][e], pofs);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) q[u][e] = __builtin_amdgcn_exp2f(q[u][e]);
+      __builtin_amdgcn_sched_barrier(0);
+      u32 hi[4][2], lo[4][2];   // [row e][j pair]
+      if (NP >= 2) {
+        float r[4][4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) rst[e] += (q[0][e] + q[1][e]) + (q[2][e] + q[3][e]);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { hi[e][0] = cvt_pk_f16(q[0][e], q[1][e]); hi[e][1] = cvt_pk_f16(q[2][e], q[3][e]); }
         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) q[u][e] = __builtin_amdgcn_exp2f(q[u][e]);
-        __builtin_amdgcn_sched_barrier(0);
-        u32 hi[4][2], lo[4][2];   // [row e][j pair]
-        if (NP >= 2) {
-          float r[4][4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) rst[e] += (q[0][e] + q[1][e]) + (q[2][e] + q[3][e]);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { hi[e][0] = cvt_pk_f16(q[0][e], q[1][e]); hi[e][1] = cvt_pk_f16(q[2][e], q[3][e]); }
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            r[e][0] = f16_resid_lo(hi[e][0], q[0][e]); r[e][1] = f16_resid_hi(hi[e][0], q[1][e]);
-            r[e][2] = f16_resid_lo(hi[e][1], q[2][e]); r[e][3] = f16_resid_hi(hi[e][1], q[3][e]);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { lo[e][0] = cvt_pk_f16(r[e][0], r[e][1]); lo[e][1] = cvt_pk_f16(r[e][2], r[e][3]); }
-          __builtin_amdgcn_sched_barrier(0);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {   // bf16: the row sums see the ROUNDED values, as in the natural tiles
-            hi[e][0] = cvt_pk_bf16(q[0][e], q[1][e]); hi[e][1] = cvt_pk_bf16(q[2][e], q[3][e]);
-            lo[e][0] = lo[e][1] = 0u;
-            rst[e] += (__uint_as_float(hi[e][0] << 16) + __uint_as_float(hi[e][0] & 0xffff0000u)) +
-                      (__uint_as_float(hi[e][1] << 16) + __uint_as_float(hi[e][1] & 0xffff0000u));
-          }
-        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const int row = 4 * ig + e;   // (row >> 2) & 3 == ig & 3
-          unsigned char* dst = buf + row * XROW + pswz(row, jq >> 1) + (jq & 1) * 8;
-          *reinterpret_cast<uint2*>(dst) = make_uint2(hi[e][0], hi[e][1]);
-          if (NP >= 2) *reinterpret_cast<uint2*>(dst + PLN) = make_uint2(lo[e][0], lo[e][1]);
+          r[e][0] = f16_resid_lo(hi[e][0], q[0][e]); r[e][1] = f16_resid_hi(hi[e][0], q[1][e]);
+          r[e][2] = f16_resid_lo(hi[e][1], q[2][e]); r[e][3] = f16_resid_hi(hi[e][1], q[3][e]);
         }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { lo[e][0] = cvt_pk_f16(r[e][0], r[e][1]); lo[e][1] = cvt_pk_f16(r[e][2], r[e][3]); }
+        __builtin_amdgcn_sched_barrier(0);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {   // bf16: the row sums see the ROUNDED values, as in the natural tiles
+          hi[e][0] = cvt_pk_bf16(q[0][e], q[1][e]); hi[e][1] = cvt_pk_bf16(q[2][e], q[3][e]);
+          lo[e][0] = lo[e][1] = 0u;
+          rst[e] += (__uint_as_float(hi[e][0] << 16) + __uint_as_float(hi[e][0] & 0xffff0000u)) +
+                    (__uint_as_float(hi[e][1] << 16) + __uint_as_float(hi[e][1] & 0xffff0000u));
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int row = 4 * ig + e;   // (row >> 2) & 3 == ig & 3
+        unsigned char* dst = buf + row * XROW + pswz(row, jq >> 1) + (jq & 1) * 8;
+        *reinterpret_cast<uint2*>(dst) = make_uint2(hi[e][0], hi[e][1]);
+        if (NP >= 2) *reinterpret_cast<uint2*>(dst + PLN) = make_uint2(lo[e][0], lo[e][1]);
       }
     };
     auto jt = [&](int tile) { return jbeg + tile * BK; };   // tile index -> first column (jbeg % 32 == 0)
@@ -763,7 +754,7 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
       float* red = reinterpret_cast<float*>(smem);   // [128] natural sums | [128] mirrored sums
 #pragma unroll
       for (int p = 0; p < 4; ++p) {
-        float a = rs[p < PR ? p : 0], b = rst[p];
+        float a = rs[p], b = rst[p];
         a += __shfl_xor(a, 1); b += __shfl_xor(b, 8);
         a += __shfl_xor(a, 2); b += __shfl_xor(b, 16);
         a += __shfl_xor(a, 4); b += __shfl_xor(b, 32);
@@ -791,12 +782,12 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
     const int ct = t - 256, lane = ct & 63, cw = ct >> 6;
     const int l15 = lane & 15, lq = lane >> 4;
     // this wave's 128-column block of [G | theta] and its CJ 16-column blocks inside it
-    const int g = RB == 8 ? 2 * cb + (cw >> 2) : 4 * cb + (cw >> 1);
-    const int wcol = RB == 8 ? (cw & 3) * 32 : (cw & 1) * 64;   // first column inside the block (16 CJ columns)
+    const int g = 2 * cb + (cw >> 2);
+    const int wcol = (cw & 3) * 32;   // first column inside the block (16 CJ columns)
     // B fragment of (k tile kt, plane s, 16-column block jb): vb + ((kt * 3 + s) * 4096 + jb * 512) elements
     // (wave-uniform part, made provably so for the "s" operand of the streamed loads; per-lane byte offsets boff below)
-    const u16* vb_wave = (g < gblocks ? Gt3 + (size_t)g * ntj * 3 * XTILE_E
-                                      : Tt3 + (size_t)(g - gblocks) * ntj * 3 * XTILE_E) +
+    const u16* vb_wave = (g < cblocks ? Gt3 + (size_t)g * ntj * 3 * XTILE_E
+                                      : Tt3 + (size_t)(g - cblocks) * ntj * 3 * XTILE_E) +
                          (size_t)(jbeg >> 5) * 3 * XTILE_E + wcol * 32;
     const u16* __restrict__ vb = reinterpret_cast<const u16*>(
         ((unsigned long long)(u32)__builtin_amdgcn_readfirstlane((int)((unsigned long long)vb_wave >> 32)) << 32) |
@@ -807,9 +798,9 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
 #pragma unroll
       for (int s = 0; s < 3; ++s) boff[j][s] = (u32)(lane * 8 + s * XTILE_E + j * 512) * 2u;
     const int aoff = l15 * XROW + pswz(l15, lq);   // A fragment of 16-row block ib, plane s: + ib * 1024 + s * PLN
-    f32x4 acc[RB][CJ];
+    f32x4 acc[FS_IB][CJ];
 #pragma unroll
-    for (int i = 0; i < RB; ++i)
+    for (int i = 0; i < FS_IB; ++i)
 #pragma unroll
       for (int j = 0; j < CJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     // two B register sets: the fragments of tile it+1 are requested at the top of tile it.  Held as 32-bit vectors
@@ -839,8 +830,8 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
       u32x4 a[2][3];
       read_a(As, 0, a[0]);
 #pragma unroll
-      for (int i = 0; i < RB; ++i) {
-        if (i + 1 < RB) read_a(As, i + 1, a[(i + 1) & 1]);
+      for (int i = 0; i < FS_IB; ++i) {
+        if (i + 1 < FS_IB) read_a(As, i + 1, a[(i + 1) & 1]);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int j = 0; j < CJ; ++j) acc[i][j] = x3_products16<NP>(a[i & 1], b[j], acc[i][j]);
@@ -875,17 +866,20 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
       __syncthreads();
     }
     if (up) __syncthreads();   // the producers' row-sum exchange (same barrier count in both roles)
-    if (g >= 2 * gblocks) return;   // (an odd block count leaves the last workgroup's upper waves without columns)
-    float* __restrict__ Oz = (g < gblocks ? OG : OT) + (size_t)z * n_local * d;
-    const int cbase = (g < gblocks ? g : g - gblocks) * BN + wcol + l15;
-    const float* __restrict__ osc = sc + (g < gblocks ? 2 : 3) * dc;   // out-scales of this wave's matrix
+    // Never taken (cb < cblocks, so g <= 2 cblocks - 1).  It stays on measurement: without it the compiler places the
+    // matrix-wave loops 16 bytes lower, and the launch is 0.4 - 1.2 % slower at 8192 x 2001 (C3 and C2 do not move;
+    // profiles/contraction_one_geometry_ab.txt).
+    if (g >= 2 * cblocks) return;
+    float* __restrict__ Oz = (g < cblocks ? OG : OT) + (size_t)z * n_local * d;
+    const int cbase = (g < cblocks ? g : g - cblocks) * BN + wcol + l15;
+    const float* __restrict__ osc = sc + (g < cblocks ? 2 : 3) * dc;   // out-scales of this wave's matrix
 #pragma unroll
     for (int j = 0; j < CJ; ++j) {
       const int col = cbase + j * 16;
       if (col >= d) continue;
       const float os = osc[col];
 #pragma unroll
-      for (int i = 0; i < RB; ++i)
+      for (int i = 0; i < FS_IB; ++i)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int row = i0 + i * 16 + 4 * lq + e;
@@ -1001,16 +995,11 @@ int stein_x3_contract_partial(const float* dist, int64_t ld_dist, const char* pl
   const u16* Tt3 = reinterpret_cast<const u16*>(planes + L.x3_tt3);
   const u16* Gt3 = reinterpret_cast<const u16*>(planes + L.x3_gt3);
   const float* sc = reinterpret_cast<const float*>(planes + L.x3_sc);
-  // 64-row x 512-column workgroups when the 128-column blocks of [G | theta] fill them (an even block count per matrix)
-  const bool wide = L.phi_wide != 0 && !upper;   // the 64-row form has no mirrored-tile path
-  const long tm = wide ? (n_local + 63) / 64 : L.tiles_m, cbk = wide ? L.cblocks / 2 : L.cblocks;
-  const long nblk = tm * cbk * L.split;
-#define X3_PHI(NP, RB) hipLaunchKernelGGL((k_phi_x3fs<NP, RB>), dim3((unsigned)nblk), dim3(FS_THREADS), 0, stream, dist, (long)ld_dist, Gt3, Tt3, (long)(L.x3_nk / 32), h2_dev, OG, OT, RS, (int)n, (int)d, (int)n_local, (int)tm, (int)cbk, (int)L.cblocks, (int)L.split, (int)L.jchunk, sc, (int)L.x3_dc, upper ? 1 : 0)
-  switch (split_kind(dtype) * 2 + (wide ? 1 : 0)) {
-    case 2: X3_PHI(1, 8); break;
-    case 3: X3_PHI(1, 4); break;
-    case 5: X3_PHI(2, 4); break;
-    default: X3_PHI(2, 8); break;
+  const long nblk = (long)L.tiles_m * L.cblocks * L.split;
+#define X3_PHI(NP) hipLaunchKernelGGL((k_phi_x3fs<NP>), dim3((unsigned)nblk), dim3(FS_THREADS), 0, stream, dist, (long)ld_dist, Gt3, Tt3, (long)(L.x3_nk / 32), h2_dev, OG, OT, RS, (int)n, (int)d, (int)n_local, (int)L.tiles_m, (int)L.cblocks, (int)L.split, (int)L.jchunk, sc, (int)L.x3_dc, upper ? 1 : 0)
+  switch (split_kind(dtype)) {
+    case 1: X3_PHI(1); break;
+    default: X3_PHI(2); break;
   }
 #undef X3_PHI
   LAUNCH_CHECK("k_phi_x3fs");

@@ -8,7 +8,7 @@
 //   k_phi_partial   P = exp(-D/2h^2) built on the fly from the D tile, O += P.[G|theta] (fp32 MFMA),
 //                   rowsum(P) on the VALU -- K is never materialised (stein_fp32.hip)
 //   k_phi_finish    phi = (O_G + (rowsum*theta - O_T)/h^2)/n, per-block partial |phi|^2 (fp64)
-//   k_sum_partials  deterministic reduction of the partials
+//   k_sum_partial_sets  deterministic reduction of the partials
 //   k_apply_*       clip + Adagrad/Adam + theta += step, one streaming pass (stein_apply.hip)
 // Reference formulae: see include/steinhip.h for the file:line of each stage.
 // This file holds the workspace layout, the fused single-rank call, the staged distance / contraction entry points, the
@@ -49,22 +49,12 @@ extern "C" const char* stein_last_error(void) { return g_err; }
 // ------------------------------------------------------------------------------------------------
 // k_rownorms: one wave per row
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float elem_f32(const float* p) { return *p; }
-__device__ __forceinline__ float elem_f32(const unsigned short* p) { return __uint_as_float((u32)*p << 16); }  // bf16 bits
-
 template <typename TIN>
 __global__ __launch_bounds__(256) void k_rownorms(const TIN* __restrict__ T, int n, int d, float* __restrict__ r) {
   const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
   const int lane = threadIdx.x & 63;
   if (wave >= n) return;
-  const TIN* row = T + (size_t)wave * d;
-  float s = 0.f;
-  for (int k = lane; k < d; k += 64) {
-    const float x = elem_f32(row + k);
-    s = fmaf(x, x, s);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  const float s = wave_row_sqnorm(T + (size_t)wave * d, d, lane);
   if (lane == 0) r[wave] = s;
 }
 
@@ -112,8 +102,9 @@ __global__ __launch_bounds__(256) void k_phi_finish(const float* __restrict__ OG
                                                     int row0, int n_local, int split, int vec, HistSync* done,
                                                     double* __restrict__ sq_out, const TIN* __restrict__ G) {
   // done != NULL (fused call; its completion counters are zero at launch): the last workgroup out also sums the partials --
-  // in the order k_sum_partials uses, so the result is the same to the last bit -- which saves that launch
-  __shared__ double red[KSD ? 12 : 4];
+  // as k_sum_partial_sets does (block_sum256), so the result is the same to the last bit -- which saves that launch
+  constexpr int NS = KSD ? 3 : 1;       // sums: |phi|^2 (, S, S_diag)
+  __shared__ double red[4 * NS];
   const float h2 = *h2p;
   const float fn = (float)n;
   const long total = (long)n_local * d;
@@ -171,39 +162,20 @@ __global__ __launch_bounds__(256) void k_phi_finish(const float* __restrict__ OG
       if constexpr (KSD) ksd_terms(elem_f32(G + (size_t)row0 * d + e), og, ot, th, rs, ih, ks, kd);
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
-  if constexpr (KSD) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { ks += __shfl_xor(ks, o); kd += __shfl_xor(kd, o); }
-    if ((threadIdx.x & 63) == 0) { red[4 + (threadIdx.x >> 6)] = ks; red[8 + (threadIdx.x >> 6)] = kd; }
-  }
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
-  __syncthreads();
-  const double part = (red[0] + red[1]) + (red[2] + red[3]);
-  double kpart[2] = {0.0, 0.0};
-  if constexpr (KSD) {
-    kpart[0] = (red[4] + red[5]) + (red[6] + red[7]);
-    kpart[1] = (red[8] + red[9]) + (red[10] + red[11]);
-  }
+  double part[NS];                      // this workgroup's partials, set k at sqpart[k * gridDim.x + blockIdx.x]
+  part[0] = sq;
+  if constexpr (KSD) { part[1] = ks; part[2] = kd; }
+  block_sum256(part, red);
   if (!done) {
-    if (threadIdx.x == 0) {
-      sqpart[blockIdx.x] = part;
-      if constexpr (KSD) {
-        sqpart[gridDim.x + blockIdx.x] = kpart[0];
-        sqpart[2 * gridDim.x + blockIdx.x] = kpart[1];
-      }
-    }
+    if (threadIdx.x == 0)
+      for (int k = 0; k < NS; ++k) sqpart[k * gridDim.x + blockIdx.x] = part[k];
     return;
   }
   // the partials cross workgroups: written with device-scope atomics, read with load_fresh (tree_report_done)
-  if (threadIdx.x == 0) {
-    __hip_atomic_store(reinterpret_cast<u64*>(sqpart) + blockIdx.x, (u64)__double_as_longlong(part), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if constexpr (KSD)
-      for (int k = 0; k < 2; ++k)
-        __hip_atomic_store(reinterpret_cast<u64*>(sqpart) + (k + 1) * gridDim.x + blockIdx.x, (u64)__double_as_longlong(kpart[k]),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  if (threadIdx.x == 0)
+    for (int k = 0; k < NS; ++k)
+      __hip_atomic_store(reinterpret_cast<u64*>(sqpart) + k * gridDim.x + blockIdx.x, (u64)__double_as_longlong(part[k]),
+                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   {
     __shared__ u32 s_last;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's partial has been acknowledged
@@ -212,64 +184,33 @@ __global__ __launch_bounds__(256) void k_phi_finish(const float* __restrict__ OG
     __syncthreads();
     if (!s_last) return;
   }
-  double s2 = 0.0;
-  for (int i = threadIdx.x; i < (int)gridDim.x; i += 256) s2 += __longlong_as_double((long long)load_fresh(reinterpret_cast<const u64*>(sqpart) + i));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s2 += __shfl_xor(s2, o);
-  double t[2] = {0.0, 0.0};
-  if constexpr (KSD) {   // the S and S_diag partials, each in the same order as |phi|^2's
-    for (int k = 0; k < 2; ++k) {
-      for (int i = threadIdx.x; i < (int)gridDim.x; i += 256)
-        t[k] += __longlong_as_double((long long)load_fresh(reinterpret_cast<const u64*>(sqpart) + (k + 1) * gridDim.x + i));
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) t[k] += __shfl_xor(t[k], o);
-    }
+  double tot[NS];                       // every set in the same order: thread t takes partials t, t + 256, ...
+  for (int k = 0; k < NS; ++k) {
+    tot[k] = 0.0;
+    for (int i = threadIdx.x; i < (int)gridDim.x; i += 256)
+      tot[k] += __longlong_as_double((long long)load_fresh(reinterpret_cast<const u64*>(sqpart) + k * gridDim.x + i));
   }
   __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-    red[threadIdx.x >> 6] = s2;
-    if constexpr (KSD) { red[4 + (threadIdx.x >> 6)] = t[0]; red[8 + (threadIdx.x >> 6)] = t[1]; }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    *sq_out = (red[0] + red[1]) + (red[2] + red[3]);
-    if constexpr (KSD) {
-      sq_out[1] = (red[4] + red[5]) + (red[6] + red[7]);
-      sq_out[2] = (red[8] + red[9]) + (red[10] + red[11]);
-    }
-  }
+  block_sum256(tot, red);
+  if (threadIdx.x == 0)
+    for (int k = 0; k < NS; ++k) sq_out[k] = tot[k];
 }
 
-__global__ __launch_bounds__(256) void k_sum_partials(const double* __restrict__ part, int count, double* out) {
-  __shared__ double red[4];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < count; i += 256) s += part[i];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) *out = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// STEIN_FLAG_KSD: k_sum_partials over the partial sets [gridDim.x][count] (|phi|^2, S, S_diag): workgroup k sums set k into
-// out[k], in that kernel's order
+// the partial sets [gridDim.x][count] of a finish pass (|phi|^2; STEIN_FLAG_KSD: S and S_diag behind it): workgroup k sums
+// set k into out[k]
 __global__ __launch_bounds__(256) void k_sum_partial_sets(const double* __restrict__ part, int count, double* out) {
   __shared__ double red[4];
   const double* p = part + (size_t)blockIdx.x * count;
-  double s = 0.0;
-  for (int i = threadIdx.x; i < count; i += 256) s += p[i];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) out[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  double s[1] = {0.0};
+  for (int i = threadIdx.x; i < count; i += 256) s[0] += p[i];
+  block_sum256(s, red);
+  if (threadIdx.x == 0) out[blockIdx.x] = s[0];
 }
 
 // the |phi|^2 partials of a finish pass (and with STEIN_FLAG_KSD the S / S_diag partials behind them) -> sqnorm_out[0 (.. 2)]
 static int sum_partials(const double* part, int count, bool ksd, double* out, hipStream_t s) {
-  if (ksd) hipLaunchKernelGGL(k_sum_partial_sets, dim3(3), dim3(256), 0, s, part, count, out);
-  else hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, part, count, out);
-  LAUNCH_CHECK(ksd ? "k_sum_partial_sets" : "k_sum_partials");
+  hipLaunchKernelGGL(k_sum_partial_sets, dim3(ksd ? 3 : 1), dim3(256), 0, s, part, count, out);
+  LAUNCH_CHECK("k_sum_partial_sets");
   return STEIN_OK;
 }
 
@@ -290,10 +231,6 @@ int stein_make_layout(int64_t n_local, int64_t n, int64_t d, int dtype, int flag
   // workgroups per unit of split and resident workgroups per round: the fp32 kernel tiles [G | theta] in 128-column
   // blocks at 3 workgroups per CU; the split-precision kernel pairs the blocks up (256 columns) at 1 workgroup per CU
   const bool x3 = (flags & STEIN_FLAG_X3) != 0;
-  // the split kernel's 64-row x 512-column form (k_phi_x3fs<NP, 4>: P built once per 512 columns, every D tile read by one
-  // workgroup; needs an even number of 128-column blocks per matrix; same workgroup count and partial layout).  Measured
-  // equal to the 128 x 256 form within +-1 % at C3 and C4 (scratch/README.md), so the shipped library keeps one form.
-  L->phi_wide = 0;
   const int64_t base = x3 ? L->tiles_m * L->cblocks : L->tiles_m * 2 * L->cblocks;
   const int64_t jt = (n + BK - 1) / BK;  // j tiles
   // k_phi_partial runs 3 workgroups per CU (156 registers): 768 resident blocks.  Every block does the same

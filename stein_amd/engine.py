@@ -196,8 +196,6 @@ class SvgdEngine:
               cross-check: so far it has only ever seen one-rank groups, where every collective is a self-copy.
     """
 
-    _full_distance_image = False   # set by scratch/ab.py for -DSTEIN_NO_UPPER builds (the mirrored image of round 1)
-
     def __init__(self, n, d, device="cuda", group=None, stages=None, x3=None, dtype=torch.float32, small=True,
                  window=True, force_collectives=False, comm="auto", tile_distance=False, dist_window=None, ksd=False):
         self.n, self.d = int(n), int(d)
@@ -534,7 +532,7 @@ class SvgdEngine:
                         self.flags | (_lib.FLAG_TIMING if timing else 0) |
                         (_lib.FLAG_TIMING_CONTRACT if timing == "contract" else 0))
             self._have_dist = not self._one_kernel
-            self.dist_upper = self.x3 and self._have_dist and not SvgdEngine._full_distance_image
+            self.dist_upper = self.x3 and self._have_dist
             self._ksd_ready = self.ksd
             return self.phi
         if self.sharded and mark is None and K_out is None and self._comm is not None:
@@ -583,8 +581,6 @@ class SvgdEngine:
             mark("median")
             self._radix_levels(0)
         upper = sym and planes is not None     # what the symmetric distance pass of the split path stores
-        if SvgdEngine._full_distance_image:     # A/B scripts against -DSTEIN_NO_UPPER builds of the library only
-            upper = False
         self.dist_upper, self._have_dist = upper, True
         if K_out is not None:
             st.kernel_matrix(D, ld, nl, n, self.h2, K_out, upper)
