@@ -128,7 +128,8 @@ def test_kernel_matrix_output(cuda):
 
 def test_clustered_particles_with_offset(cuda):
     """Tight cluster far from the origin: r + r^T - 2TT^T cancels badly in fp32 (reference behaviour too).
-    The GPU must agree with the fp32-faithful oracle's own conditioning, not with fp64."""
+    The GPU must agree with the fp32-faithful oracle's own conditioning, not with fp64.
+    (The split path: test_offset_cluster_on_the_split_path in test_gpu_conditioning.py.)"""
     n, d = 300, 20
     rng = np.random.default_rng(9)
     T64 = 0.5 + 0.01 * rng.normal(size=(n, d))
@@ -146,6 +147,8 @@ def test_clustered_particles_with_offset(cuda):
 
 
 def test_translation_and_permutation_properties(cuda):
+    """(fp32-MFMA path; the translation property on the split path: test_translation_property_on_the_split_path in
+    test_gpu_conditioning.py)"""
     n, d = 384, 40
     T64, G64 = _inputs(n, d, seed=11)
     T = torch.tensor(T64, dtype=torch.float32, device=cuda)
