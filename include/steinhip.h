@@ -61,6 +61,18 @@ enum {
   STEIN_FLAG_TIMING_CONTRACT = 128, /* stein_svgd_phi, with STEIN_FLAG_TIMING: record only the two events that bracket the
                                        contraction (an event between two kernels costs the step ~3 us of GPU time: six of
                                        them perturb what they time); stein_timing_read reports -1 for the other stages */
+  STEIN_FLAG_FOLD = 512, /* stein_svgd_phi (and stein_workspace_bytes / _layout): take the folded contraction wherever it is
+                            eligible, whatever the size.  Eligible: STEIN_FLAG_X3, fp32 inputs, not the one-kernel path.  The
+                            contraction then multiplies K with W = G - theta / h2 alone (phi = (K.W + rowsum(K) theta / h2) / n:
+                            half the matrix-core work; W's planes are built behind the median); with dK_out or
+                            STEIN_FLAG_KSD, with [W | theta] -- phi, h2 and |phi|^2 are the same to the bit either way.
+                            Without either flag the library takes the form where it pays (large blocks).  The staged calls
+                            and the rank segments never do.  The fold's partial sums reuse PART_G, PART_T and theta's row-major
+                            planes; where they do not fit, this flag appends them to the PLANES section (no other offset
+                            moves) and the default leaves the call unfolded.  Every tiled fused call records what it did in
+                            the workspace: the uint32 at byte 140 of the SELECT section is 1 after a folded call, else 0. */
+  STEIN_FLAG_NO_FOLD = 1024, /* the same calls: never take the folded contraction (A/B measurements; a workspace that only
+                                ever serves the staged calls does not need the fold's partial sums either) */
   STEIN_FLAG_KSD = 256 /* stein_svgd_phi, stein_rank_finish, stein_rank_step (and stein_workspace_bytes / _layout, whose
                           SQPART section then holds three partials per block): also the kernelized Stein discrepancy of
                           the particles under the step's own RBF kernel and median bandwidth.  sqnorm_out then points to
@@ -126,6 +138,9 @@ const char* stein_last_error(void);
 int stein_workspace_bytes(int64_t n_local, int64_t n, int64_t d, int dtype, int flags, size_t* out_bytes);
 int stein_workspace_layout(int64_t n_local, int64_t n, int64_t d, int dtype, int flags,
                            size_t* offsets /*[STEIN_WS_NSECTIONS]*/, int64_t* extra /*[STEIN_WSX_N]*/);
+
+/* *out = 1 if stein_svgd_phi with these arguments takes the folded contraction (STEIN_FLAG_FOLD), else 0.  Host arithmetic. */
+int stein_layout_folds(int64_t n_local, int64_t n, int64_t d, int dtype, int flags, int* out);
 
 /* ---- fused single-rank path ------------------------------------------------------------------
  * Replaces AbstractSteinSampler.compute_phi (stein/samplers/abstract_stein_sampler.py:100-105)

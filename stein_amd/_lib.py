@@ -29,12 +29,15 @@ FLAG_NO_WINDOW = 16
 FLAG_RANK_WINDOW = 32
 FLAG_TILE_DISTANCE = 64
 FLAG_TIMING_CONTRACT = 128
+FLAG_FOLD = 512     # the fused call takes the folded contraction (K.W, W = G - theta / h2) wherever it is eligible
+FLAG_NO_FOLD = 1024  # ... never takes it
 FLAG_KSD = 256      # also the kernelized Stein discrepancy sums: sqnorm is double[3] = |phi|^2, S, S_diag
 GLM_LINEAR, GLM_LOGISTIC = 0, 1
 SPEC_TABLE_WORDS = 65544          # uint64 words of the rank-summed window table ...
 SPEC_TABLE_OFFSET_WORDS = 1 << 21  # ... which starts 2^21 words into the SPEC section (slots + entry buffer)
 SPEC_HIT_OFFSET, SPEC_SKIP_L0_OFFSET = 64 + 28, 64 + 52   # uint32 state words inside the SELECT section
 SPEC_NSTEPS_OFFSET, SPEC_NHITS_OFFSET = 64 + 56, 64 + 60   # medians recorded since the predictor started / window hits
+FUSE_FOLDED_OFFSET = 128 + 12     # uint32 in the SELECT section: 1 after a fused call that took the folded contraction
 SELECT_BYTES = 192                                        # SelState + SpecState + FuseState
 COMM_ID_BYTES = 128                                       # STEIN_COMM_ID_BYTES
 T_STAGES = ("prepare", "distance", "median", "contract", "finish")   # STEIN_T_* of include/steinhip.h
@@ -46,6 +49,7 @@ _vp, _i64, _int, _dbl, _sz = _c.c_void_p, _c.c_int64, _c.c_int, _c.c_double, _c.
 _SIGNATURES = {
     "stein_workspace_bytes": [_i64, _i64, _i64, _int, _int, _c.POINTER(_sz)],
     "stein_workspace_layout": [_i64, _i64, _i64, _int, _int, _c.POINTER(_sz), _c.POINTER(_i64)],
+    "stein_layout_folds": [_i64, _i64, _i64, _int, _int, _c.POINTER(_int)],
     "stein_spec_begin": [_vp, _vp, _vp, _i64, _vp],
     "stein_distance_block_spec": [_vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _i64, _vp, _vp, _int, _vp, _vp, _vp],
     "stein_spec_tally": [_vp, _vp, _vp],
@@ -150,6 +154,13 @@ def workspace_layout(n_local, n, d, dtype=F32, flags=0):
     extra = (_i64 * WSX_N)()
     call("stein_workspace_layout", n_local, n, d, dtype, flags, offs, extra)
     return int(total.value), [int(o) for o in offs], [int(e) for e in extra]
+
+
+def layout_folds(n_local, n, d, dtype=F32, flags=0):
+    """Does the fused call with these arguments take the folded contraction (FLAG_FOLD)?  Host arithmetic."""
+    out = _int(0)
+    call("stein_layout_folds", n_local, n, d, dtype, flags, ctypes.byref(out))
+    return bool(out.value)
 
 
 def version():

@@ -200,7 +200,7 @@ extern "C" int stein_rank_step(void* comm, const void* theta_local, const void* 
 
   // the sections the collectives touch (the same layout the segments derive)
   SteinLayout L;
-  int rc = stein_make_layout(n_local, n, d, dtype, (flags & (STEIN_FLAG_X3 | STEIN_FLAG_KSD)) | STEIN_FLAG_TILED, &L);
+  int rc = stein_make_layout(n_local, n, d, dtype, (flags & (STEIN_FLAG_X3 | STEIN_FLAG_KSD)) | STEIN_FLAG_TILED | STEIN_FLAG_NO_FOLD, &L);
   if (rc) return rc;
   if (ws_bytes < L.total) return stein_fail(STEIN_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L.total);
   const StepViews v = stein_step_views(L, workspace);

@@ -136,7 +136,8 @@ static_assert(sizeof(SpecState) == 64, "SpecState must stay 64 bytes");
 struct FuseState {
   u32 pad0[2];
   u32 gave_up;     // k_hist_all: a bounded wait ran out (cannot happen by construction; the bandwidth becomes NaN and the host is told)
-  u32 pad[13];
+  u32 folded;      // this fused call takes the folded contraction (written by the prologue; include/steinhip.h, STEIN_FLAG_FOLD)
+  u32 pad[12];
 };
 static_assert(sizeof(FuseState) == 64, "FuseState must stay 64 bytes");
 // Synchronisation state of k_hist_all (the fused call's chained radix select in one launch, stein_select.hip): lives in the
@@ -212,9 +213,10 @@ __device__ __forceinline__ MedianBw median_bandwidth(float lo, float hi, u32 eve
 // STEIN_FLAG_KSD: one element e = (i, c)'s share of sum_ij u_ij (s) and of sum_i u_ii (sd), include/steinhip.h, from the
 // fp32 sums og = (K.G)_e, ot = (K.theta)_e, rs = rowsum(K)_i; ih = 1 / h2.  In fp64, and dk is formed again here:
 // rs * th - ot cancels, and the fp32 dk of phi has lost those digits already.
-__device__ __forceinline__ void ksd_terms(float g, float og, float ot, float th, float rs, double ih, double& s, double& sd) {
+// (og is a double: the folded contraction holds K.W and K.theta and hands over og = ow + ot / h2 formed in fp64)
+__device__ __forceinline__ void ksd_terms(float g, double og, float ot, float th, float rs, double ih, double& s, double& sd) {
   const double gd = g, dk = ((double)rs * (double)th - (double)ot) * ih;
-  s += gd * (double)og + 2.0 * (gd - (double)th * ih) * dk + (double)rs * ih;
+  s += gd * og + 2.0 * (gd - (double)th * ih) * dk + (double)rs * ih;
   sd += gd * gd + ih;
 }
 
@@ -620,6 +622,10 @@ struct SteinLayout {
   int64_t x3_dc, x3_nk;     // transposed planes of theta and of the score: x3_dc x x3_nk  (contraction B operand)
   size_t x3_t3, x3_tt3, x3_gt3;  // byte offsets inside the PLANES section
   size_t x3_sc;                  // power-of-two operand scales (stein_x3.hip: "scales area"), inside the PLANES section
+  // folded contraction (the fused call contracts K with W = G - theta / h2 alone; stein_x3.hip, "folded operand"): its own
+  // j split and where its partial sums go, as byte offsets from the workspace base (stein_make_layout).  fold = 0: none.
+  int64_t fold, fsplit, fjchunk;
+  size_t fold_ow, fold_ot, fold_rs;   // float OW [fsplit][n][d] (K.W), OT [n][d] (K.theta, dK / KSD calls), RS [fsplit][n]
 };
 int stein_make_layout(int64_t n_local, int64_t n, int64_t d, int dtype, int flags, SteinLayout* L);
 
@@ -670,6 +676,7 @@ struct PrologueArgs {
   int allow_window;
   float* neutral_sc; int dc;
   u32* hsync; int hsync_words;   // HistSync of k_hist_all (zeroed here)
+  u32 folded;                    // -> FuseState::folded
 };
 constexpr int PRO_INIT_BLOCKS = 16;   // (k_prologue's grid: one workgroup per four rows + these; any grid works)
 template <typename TIN>
@@ -680,7 +687,7 @@ __device__ __forceinline__ void prologue_body(const TIN* __restrict__ T, const P
     for (int i = gt; i < 4 * a.dc; i += gn) a.neutral_sc[i] = 1.f;
     if (gt == 0) { a.neutral_sc[4 * a.dc] = 1.f; a.neutral_sc[4 * a.dc + 1] = 2.f; a.neutral_sc[4 * a.dc + 2] = 1.f; }
   }
-  if (gt < 16) reinterpret_cast<u32*>(a.fs)[gt] = 0u;
+  if (gt < 16) reinterpret_cast<u32*>(a.fs)[gt] = gt == 3 ? a.folded : 0u;   // (word 3 = FuseState::folded)
   for (int i = gt; i < a.hsync_words; i += gn) a.hsync[i] = 0u;
   median_init_body(gt, gn, a.st, a.sp, a.total, a.hist, a.slots, a.allow_window);
   const int lane = threadIdx.x & 63;

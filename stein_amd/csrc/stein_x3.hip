@@ -16,6 +16,7 @@
 //
 //   k_colmax, k_make_scales   column maxima -> power-of-two scales (KIND 2; all ones otherwise)
 //   k_split         theta, score -> 16-bit operand tiles ("planes", layout below)
+//   k_split_w       theta, score, h2 -> the planes of W = score - theta / h2 (the fused call's folded operand, behind the median)
 //   k_distance_x3   S = T T^T from the planes; shares the fp32 kernel's epilogue (D, level-0 histogram or window counting).
 //                   Single rank: only the 128 x 128 tiles on and above the diagonal are computed AND stored
 //   k_phi_x3fs      warp-specialised contraction: producer waves build P = exp2(c D) (split on the fly) in LDS -- a k tile
@@ -318,6 +319,72 @@ __global__ __launch_bounds__(256) void k_split(const TIN* __restrict__ X0, const
   }
 }
 
+// The folded operand (fused call, fp32 inputs; stein_fold_pays): phi_i = (sum_j K_ij w_j + rowsum_i theta_i / h2) / n with
+// w_j = g_j - theta_j / h2, so the contraction multiplies K with ONE matrix.  W depends on h2: this kernel runs between the
+// median and the contraction.  One 64 x 64 tile of W per workgroup, written like k_split's transposed image into Wt (the
+// score's plane storage).  Column c's in-scale puts the bound max_c|g| + max_c|theta| / h2 (from k_colmax's maxima: no
+// pass over the inputs) into [2^13, 2^14); it replaces the score's scales ([0, dc) and [2dc, 3dc) of the scales area).  The
+// bound can be twice the true maximum of |w| and more where the terms cancel: the absolute error stays 2^-38 of the bound,
+// which is what K.G and K.theta / h2 carry separately on the unfolded path.  h2 = 0: 1 / h2 = inf, the bound is inf or NaN,
+// the scale 1, W holds inf / NaN and phi comes out NaN as on every other path.
+__global__ __launch_bounds__(256) void k_split_w(const float* __restrict__ T, const float* __restrict__ G, int n, int d,
+                                                 u16* __restrict__ Wt, int dc, long nk, float* __restrict__ sc,
+                                                 const u32* __restrict__ cmax, const float* __restrict__ h2p) {
+  __shared__ u16 tile[2][64][66];
+  const int t = threadIdx.x;
+  const int row0 = blockIdx.y * 64, col0 = blockIdx.x * 64;
+  const int lr = t >> 4, lc = (t & 15) * 4;
+  const long ntk_t = nk >> 5;
+  const float ih = 1.f / *h2p;
+  float scq[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int c = col0 + lc + q;
+    int se = 0;
+    if (c < dc) se = scale_exp(__float_as_uint(__builtin_fmaf(__uint_as_float(cmax[dc + c]), ih, __uint_as_float(cmax[c]))), 100);
+    scq[q] = pow2i(se);
+    if (blockIdx.y == 0 && lr == 0 && c < dc) {
+      sc[c] = scq[q];
+      sc[2 * dc + c] = pow2i(-se - PEXP_H2);
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const int row = row0 + lr + 16 * p, col = col0 + lc;
+    float v[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const size_t at = (size_t)row * d + col + q;
+      v[q] = (row < n && col + q < d) ? __builtin_fmaf(-T[at], ih, G[at]) : 0.f;
+    }
+    u32 wa[3], wb[3];
+    split_pair<2>(v[0] * scq[0], v[1] * scq[1], wa);
+    split_pair<2>(v[2] * scq[2], v[3] * scq[3], wb);
+    const int rr = lr + 16 * p;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      tile[s][lc + 0][rr] = (u16)wa[s]; tile[s][lc + 1][rr] = (u16)(wa[s] >> 16);
+      tile[s][lc + 2][rr] = (u16)wb[s]; tile[s][lc + 3][rr] = (u16)(wb[s] >> 16);
+    }
+  }
+  __syncthreads();
+  // transposed store, as in k_split
+  const int c = col0 + (t >> 2), j = row0 + (t & 3) * 16;
+  if (c < dc && j < nk) {
+    const int rowc = c & 127, ch0 = (j & 31) >> 3;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      u32 w[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q)
+        w[q] = (u32)tile[s][t >> 2][(t & 3) * 16 + 2 * q] | ((u32)tile[s][t >> 2][(t & 3) * 16 + 2 * q + 1] << 16);
+      u16* base = Wt + (((size_t)(c >> 7) * ntk_t + (j >> 5)) * 3 + s) * XTILE_E;
+      *reinterpret_cast<uint4*>(base + vfrag_offset(rowc, ch0)) = make_uint4(w[0], w[1], w[2], w[3]);
+      *reinterpret_cast<uint4*>(base + vfrag_offset(rowc, ch0 + 1)) = make_uint4(w[4], w[5], w[6], w[7]);
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // k_distance_x3
 //   Thread t stages chunk t and chunk t + 256 (row += 64) of every plane.  The tile's rows may straddle two row
@@ -478,7 +545,13 @@ constexpr int CJ = 2;                    // 16-column blocks per matrix wave (8 
 constexpr int PR = FS_ROWS / 32;         // producer: rows lr + 32 p per thread and tile (4 columns each)
 constexpr int PLN = FS_ROWS * XROW;      // one plane of one k tile in LDS: [128][64 B]
 
-template <int NP>
+//   FOLD (the fused call's folded operand, fp32 inputs): the column space is ONE matrix of `cblocks` 128-column blocks,
+//   W = G - theta / h2 (Gt3 holds its planes), paired into wpm = ceil(cblocks / 2) workgroups per row tile (an odd count
+//   leaves the last with one block: its second half of matrix waves repeats the first block and stores nothing), times
+//   `split` j ranges.  When dK or the Stein discrepancy is asked for, the grid carries tiles_m x wpm more workgroups behind
+//   those: the same for theta (Tt3 -> OT), each over the whole j range.  The workgroups of W do not know whether they are
+//   there: same ids, same k order, so phi is the same to the bit with and without dK_out.
+template <int NP, bool FOLD = false>
 __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict__ D, long ldD,
                                                          const u16* __restrict__ Gt3, const u16* __restrict__ Tt3,
                                                          long ntj, const float* __restrict__ h2p,
@@ -486,7 +559,9 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
                                                          float* __restrict__ RS, int n, int d, int n_local,
                                                          int tiles_m, int cblocks, int split, int jchunk,
                                                          const float* __restrict__ sc, int dc, int upper) {
-  // cblocks: workgroups per row tile = 128-column blocks per matrix (G and theta each; a workgroup takes one of each pair)
+  // cblocks: 128-column blocks per matrix; wpm: workgroups per row tile and j range (not FOLD: = cblocks, a workgroup takes
+  // one block pair of [G | theta])
+  const int wpm = FOLD ? (cblocks + 1) >> 1 : cblocks;
   constexpr int FS_KTB = NP * PLN;            // one k tile in LDS: NP planes, packed
   constexpr int FS_STAGE = FS_KT * FS_KTB;    // 2 stages x FS_KT x NP x 8 KB: 128 KB (NP 2), 64 KB (NP 1)
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * FS_STAGE];
@@ -499,19 +574,22 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
   // anyway; a wide [G | theta] (C4: 16 column blocks) dealt that way made an XCD 2 row tiles x 16 blocks -- V, 134 MB, came
   // in 32 times (4.8 GB of HBM traffic per launch by the counters); 8 row tiles x 4 blocks asks for both four to eight times.
   int cb, tile_m;
-  const int plane = cblocks * tiles_m, l2 = logical % plane;
-  const int z = logical / plane;
-  if (cblocks > 4 && (cblocks & 3) == 0 && (tiles_m & 7) == 0) {
-    const int sb = l2 >> 5, in = l2 & 31, cgroups = cblocks >> 2;
+  const int plane = wpm * tiles_m;
+  const int half = FOLD && logical >= plane * split ? 1 : 0;   // FOLD: the workgroups behind W's are theta's (one j range)
+  const int lw = FOLD ? logical - half * plane * split : logical;
+  const int l2 = lw % plane;
+  const int z = lw / plane;
+  if (wpm > 4 && (wpm & 3) == 0 && (tiles_m & 7) == 0) {
+    const int sb = l2 >> 5, in = l2 & 31, cgroups = wpm >> 2;
     cb = (sb % cgroups) * 4 + (in & 3);
     tile_m = (sb / cgroups) * 8 + (in >> 2);
   } else {
-    cb = l2 % cblocks;
-    tile_m = l2 / cblocks;
+    cb = l2 % wpm;
+    tile_m = l2 / wpm;
   }
   const int i0 = tile_m * FS_ROWS;
   const int jbeg = z * jchunk;
-  const int jend = min(n, jbeg + jchunk);
+  const int jend = half ? n : min(n, jbeg + jchunk);
   const int ntile = jend > jbeg ? (jend - jbeg + BK - 1) / BK : 0;
   // Visit order of the k tiles inside a pipeline stage.  The `cblocks` workgroups of a row tile all stream the same D row
   // block.  Walking it in step, each of them waits out the full HBM latency of every tile (a request that arrives while
@@ -523,7 +601,7 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
   // the partial last stage keeps its order.  (The order of the k tiles inside the fp32 accumulation changes with it --
   // deterministically.)
   const int nstage = (ntile + FS_KT - 1) / FS_KT;
-  const int rot = (cb % FS_KT) * (cblocks >= FS_KT ? 1 : FS_KT / cblocks) % FS_KT;
+  const int rot = (cb % FS_KT) * (wpm >= FS_KT ? 1 : FS_KT / wpm) % FS_KT;
   // Visit order of the STAGES (upper, one workgroup per row tile and column block over the whole j range, a power-of-two number
   // of row tiles): stage v of the row tiles that share an XCD (`group` consecutive ones: 32 logical ids / cblocks) is the
   // 128-column block v ^ (tile_m & ~(group - 1)).  Every stored tile D[I][J] is read twice, by row tile I as itself and by
@@ -531,10 +609,13 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
   // 16 MB of D traffic per stage: the second read comes from HBM again), in this order |I % group - J % group| < group
   // stages apart (5 on average), where the memory-side cache still holds the tile.  The row tiles of an XCD keep walking the
   // SAME block at the same time, so V is shared in their L2 as before.
-  const int group = cblocks <= 32 ? 32 / cblocks : 1;
-  const bool permute = upper != 0 && jbeg == 0 && jend == n && (cblocks & (cblocks - 1)) == 0 && cblocks <= 4 &&
-                       nstage * FS_KT == ntile && (nstage & (nstage - 1)) == 0 && nstage == tiles_m && nstage >= 2 * group;
-  const int xmask = permute ? (tile_m & ~(group - 1)) : 0;
+  // FOLD: the halved grid is split over j to fill the chip (C3: two ranges of 64 stages), and every range is walked this way:
+  // stage v of a range is its block v ^ (tile_m & ~(group - 1) & (nstage - 1)).  The two reads of a stored tile, by row tiles
+  // I and J in whichever ranges, are then (I ^ J) & (group - 1) < group stages apart as before, all ranges running at once.
+  const int group = wpm <= 32 ? 32 / wpm : 1;
+  const bool permute = upper != 0 && (FOLD || (jbeg == 0 && jend == n && nstage == tiles_m)) && (wpm & (wpm - 1)) == 0 &&
+                       wpm <= 4 && nstage * FS_KT == ntile && (nstage & (nstage - 1)) == 0 && nstage >= 2 * group;
+  const int xmask = permute ? (tile_m & ~(group - 1) & (nstage - 1)) : 0;
   auto stage_of = [&](int v) { return v ^ xmask; };   // (v = nstage, "the stage after the last", stays out of range)
   auto tile_at = [&](int stage, int u) {     // u may run past the stage: u >= FS_KT continues in the next stage
     const int st2 = stage_of(stage + u / FS_KT), u2 = u % FS_KT;
@@ -763,8 +844,8 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
       }
       __syncthreads();
       const int row = i0 + pt;
-      if (cb == 0 && pt < 128 && row < n_local) RS[(size_t)z * n_local + row] = (red[pt] + red[128 + pt]) * sc[4 * dc + 2];
-    } else if (cb == 0) {   // rowsum: the 8 threads of a row are 8 consecutive lanes
+      if (cb == 0 && !half && pt < 128 && row < n_local) RS[(size_t)z * n_local + row] = (red[pt] + red[128 + pt]) * sc[4 * dc + 2];
+    } else if (cb == 0 && !half) {   // rowsum: the 8 threads of a row are 8 consecutive lanes
 #pragma unroll
       for (int p = 0; p < PR; ++p) {
         float sum = rs[p];
@@ -782,12 +863,15 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
     const int ct = t - 256, lane = ct & 63, cw = ct >> 6;
     const int l15 = lane & 15, lq = lane >> 4;
     // this wave's 128-column block of [G | theta] and its CJ 16-column blocks inside it
+    // (FOLD: block g of matrix `half`; a block past the matrix's last is computed as that last one and not stored)
     const int g = 2 * cb + (cw >> 2);
+    const int gl = FOLD ? min(g, cblocks - 1) : g;
     const int wcol = (cw & 3) * 32;   // first column inside the block (16 CJ columns)
     // B fragment of (k tile kt, plane s, 16-column block jb): vb + ((kt * 3 + s) * 4096 + jb * 512) elements
     // (wave-uniform part, made provably so for the "s" operand of the streamed loads; per-lane byte offsets boff below)
-    const u16* vb_wave = (g < cblocks ? Gt3 + (size_t)g * ntj * 3 * XTILE_E
-                                      : Tt3 + (size_t)(g - cblocks) * ntj * 3 * XTILE_E) +
+    const u16* vb_wave = (FOLD ? (half ? Tt3 : Gt3) + (size_t)gl * ntj * 3 * XTILE_E
+                               : (g < cblocks ? Gt3 + (size_t)g * ntj * 3 * XTILE_E
+                                              : Tt3 + (size_t)(g - cblocks) * ntj * 3 * XTILE_E)) +
                          (size_t)(jbeg >> 5) * 3 * XTILE_E + wcol * 32;
     const u16* __restrict__ vb = reinterpret_cast<const u16*>(
         ((unsigned long long)(u32)__builtin_amdgcn_readfirstlane((int)((unsigned long long)vb_wave >> 32)) << 32) |
@@ -869,10 +953,11 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
     // Never taken (cb < cblocks, so g <= 2 cblocks - 1).  It stays on measurement: without it the compiler places the
     // matrix-wave loops 16 bytes lower, and the launch is 0.4 - 1.2 % slower at 8192 x 2001 (C3 and C2 do not move;
     // profiles/contraction_one_geometry_ab.txt).
-    if (g >= 2 * cblocks) return;
-    float* __restrict__ Oz = (g < cblocks ? OG : OT) + (size_t)z * n_local * d;
-    const int cbase = (g < cblocks ? g : g - cblocks) * BN + wcol + l15;
-    const float* __restrict__ osc = sc + (g < cblocks ? 2 : 3) * dc;   // out-scales of this wave's matrix
+    if (FOLD ? g >= cblocks : g >= 2 * cblocks) return;
+    const bool first = FOLD ? half == 0 : g < cblocks;   // this wave's matrix: G (FOLD: W) or theta
+    float* __restrict__ Oz = (first ? OG : OT) + (size_t)z * n_local * d;
+    const int cbase = (FOLD || first ? g : g - cblocks) * BN + wcol + l15;
+    const float* __restrict__ osc = sc + (first ? 2 : 3) * dc;   // out-scales of this wave's matrix
 #pragma unroll
     for (int j = 0; j < CJ; ++j) {
       const int col = cbase + j * 16;
@@ -919,7 +1004,7 @@ static void launch_split(hipStream_t stream, const TIN* theta, const TIN* score,
 // the column-maxima kernel's last workgroup writes the scales itself
 int stein_x3_split(const void* theta_all, const void* score_all, int dtype, int64_t n, int64_t d,
                    const SteinLayout& L, char* planes, hipStream_t stream, HistSync* fuse_done, bool scales_written,
-                   const PrologueArgs* prologue) {
+                   const PrologueArgs* prologue, int fold) {
   u16* T3 = reinterpret_cast<u16*>(planes + L.x3_t3);
   u16* Tt3 = reinterpret_cast<u16*>(planes + L.x3_tt3);
   u16* Gt3 = reinterpret_cast<u16*>(planes + L.x3_gt3);
@@ -953,8 +1038,31 @@ int stein_x3_split(const void* theta_all, const void* score_all, int dtype, int6
     LAUNCH_CHECK("k_make_scales");
   }
   if (kind == 1) launch_split<u16, 1>(stream, (const u16*)theta_all, (const u16*)score_all, n, d, L, T3, Tt3, Gt3, sc, prologue);
+  else if (fold)   // the score's planes are built behind the median (stein_x3_split_w); theta^T only if its product is asked for
+    launch_split<float, 2>(stream, (const float*)theta_all, (const float*)nullptr, n, d, L, T3, fold == 2 ? Tt3 : nullptr, Gt3, sc);
   else launch_split<float, 2>(stream, (const float*)theta_all, (const float*)score_all, n, d, L, T3, Tt3, Gt3, sc);
   LAUNCH_CHECK("k_split");
+  return STEIN_OK;
+}
+
+// Where the folded operand pays by default.  It halves the contraction's MFMAs only when W has at least two 128-column
+// blocks: with one (d <= 128) the unfolded kernel already pairs G's block with theta's in one workgroup and the folded one
+// would run half its matrix waves for nothing -- measured 2.5 % SLOWER at 8192 x 128 (one more dependent launch, nothing
+// saved).  With d > 128 the fused step, fold forced on against off (ms): 4096 x 256 0.129 -> 0.119,
+// 8192 x 256 0.275 -> 0.211, 8192 x 2001 1.77 -> 1.22, 16384 x 256 0.87 -> 0.61; run-to-run spread 0.5 %.  The threshold sits
+// at the smallest block measured to gain (4096 x 256: n^2 d = 4.3e9); below it the step is a chain of latency-bound launches.
+constexpr double FOLD_MIN_WORK = 4.0e9;   // n * n * d
+bool stein_fold_pays(int64_t n, int64_t d) { return d > 128 && (double)n * (double)n * (double)d >= FOLD_MIN_WORK; }
+
+int stein_x3_split_w(const float* theta_all, const float* score_all, int64_t n, int64_t d, const SteinLayout& L,
+                     char* planes, const float* h2_dev, hipStream_t stream) {
+  float* sc = reinterpret_cast<float*>(planes + L.x3_sc);
+  const int dc = (int)L.x3_dc;
+  const dim3 grid((unsigned)((L.x3_dc + 63) / 64), (unsigned)((L.x3_nk + 63) / 64));
+  hipLaunchKernelGGL(k_split_w, grid, dim3(256), 0, stream, theta_all, score_all, (int)n, (int)d,
+                     reinterpret_cast<u16*>(planes + L.x3_gt3), dc, (long)L.x3_nk, sc,
+                     reinterpret_cast<const u32*>(sc + 4 * dc + 4), h2_dev);
+  LAUNCH_CHECK("k_split_w");
   return STEIN_OK;
 }
 
@@ -1002,6 +1110,26 @@ int stein_x3_contract_partial(const float* dist, int64_t ld_dist, const char* pl
     default: X3_PHI(2); break;
   }
 #undef X3_PHI
+  LAUNCH_CHECK("k_phi_x3fs");
+  return STEIN_OK;
+}
+
+// the folded contraction of the fused call: K.W in fsplit j ranges (with_theta: and K.theta in one) into the fold's
+// partial sums (SteinLayout::fold_ow / fold_ot / fold_rs)
+int stein_x3_contract_fold(const float* dist, int64_t ld_dist, char* workspace, const SteinLayout& L, const float* h2_dev,
+                           int64_t n, int64_t d, bool with_theta, hipStream_t stream) {
+  const char* planes = workspace + L.off[STEIN_WS_PLANES];
+  const u16* Tt3 = reinterpret_cast<const u16*>(planes + L.x3_tt3);
+  const u16* Wt3 = reinterpret_cast<const u16*>(planes + L.x3_gt3);
+  const float* sc = reinterpret_cast<const float*>(planes + L.x3_sc);
+  const long per_range = (long)L.tiles_m * ((L.cblocks + 1) / 2);
+  const long nblk = per_range * (L.fsplit + (with_theta ? 1 : 0));
+  if (nblk > 0x7fffffffl) return stein_fail(STEIN_E_SHAPE, "too many tiles");
+  hipLaunchKernelGGL((k_phi_x3fs<2, true>), dim3((unsigned)nblk), dim3(FS_THREADS), 0, stream, dist, (long)ld_dist, Wt3,
+                     with_theta ? Tt3 : (const u16*)nullptr, (long)(L.x3_nk / 32), h2_dev,
+                     reinterpret_cast<float*>(workspace + L.fold_ow), reinterpret_cast<float*>(workspace + L.fold_ot),
+                     reinterpret_cast<float*>(workspace + L.fold_rs), (int)n, (int)d, (int)n, (int)L.tiles_m, (int)L.cblocks,
+                     (int)L.fsplit, (int)L.fjchunk, sc, (int)L.x3_dc, 1);
   LAUNCH_CHECK("k_phi_x3fs");
   return STEIN_OK;
 }

@@ -94,12 +94,15 @@ __device__ __forceinline__ float4 theta4(const unsigned short* p) {   // four bf
 // KSD (STEIN_FLAG_KSD): also this call's shares of the Stein discrepancy sums S and S_diag (ksd_terms) from the score rows
 // G; their block partials follow the |phi|^2 partials in sqpart ([3][gridDim.x]) and sq_out is double[3].  The KSD = false
 // instantiation is the kernel without the statistic.
-template <typename TIN, bool KSD>
+// FOLD (the fused call's folded operand, stein_x3.hip): OG holds the partials of K.W, W = G - theta / h2, and
+// phi = (ow + rs theta / h2) / n.  OT (K.theta) exists and is read only when dK or the statistic is asked for; phi never
+// touches it, so it is the same to the bit with and without them.  The statistic gets og = ow + ot / h2 formed in fp64.
+template <typename TIN, bool KSD, bool FOLD = false>
 __global__ __launch_bounds__(256) void k_phi_finish(const float* __restrict__ OG, const float* __restrict__ OT,
                                                     const float* __restrict__ RS, const TIN* __restrict__ T,
                                                     const float* __restrict__ h2p, float* __restrict__ phi,
                                                     float* __restrict__ dK, double* __restrict__ sqpart, int n, int d,
-                                                    int row0, int n_local, int split, int vec, HistSync* done,
+                                                    int row0, int n_local, int split, int tsplit, int vec, HistSync* done,
                                                     double* __restrict__ sq_out, const TIN* __restrict__ G) {
   // done != NULL (fused call; its completion counters are zero at launch): the last workgroup out also sums the partials --
   // as k_sum_partial_sets does (block_sum256), so the result is the same to the last bit -- which saves that launch
@@ -112,6 +115,8 @@ __global__ __launch_bounds__(256) void k_phi_finish(const float* __restrict__ OG
   double sq = 0.0;
   double ks = 0.0, kd = 0.0;            // KSD: this thread's shares of S and S_diag
   const double ih = 1.0 / (double)h2;
+  const bool need_t = !FOLD || KSD || dK != nullptr;
+  auto kg = [&](float o, float t) { return FOLD ? (double)o + (double)t * ih : (double)o; };   // (K.G)_e for the statistic
   if (vec) {   // host: d % 4 == 0 and every pointer aligned for four columns at a time
     // four consecutive columns of one row per step, 16-byte loads and stores (one entry at a time with an integer
     // division each, the kernel moved its 68 MB at 2.8 TB/s; bf16 inputs took that path until round 4: 19 us at C2)
@@ -124,24 +129,32 @@ __global__ __launch_bounds__(256) void k_phi_finish(const float* __restrict__ OG
       float rs = 0.f;
 #pragma unroll 8
       for (int z = 0; z < split; ++z) {   // unrolled: the loads of eight slices in flight, the sums in the same order
-        const float4 a = *reinterpret_cast<const float4*>(OG + z * zs + e), b = *reinterpret_cast<const float4*>(OT + z * zs + e);
+        const float4 a = *reinterpret_cast<const float4*>(OG + z * zs + e);
         og.x += a.x; og.y += a.y; og.z += a.z; og.w += a.w;
-        ot.x += b.x; ot.y += b.y; ot.z += b.z; ot.w += b.w;
+        if (FOLD ? need_t && z < tsplit : true) {   // (FOLD: K.theta comes in tsplit = 1 range)
+          const float4 b = *reinterpret_cast<const float4*>(OT + z * zs + e);
+          ot.x += b.x; ot.y += b.y; ot.z += b.z; ot.w += b.w;
+        }
         rs += RS[(size_t)z * n_local + i];
       }
       const float4 th = theta4(T + (size_t)row0 * d + e);
       float4 dk, ph;
       dk.x = (rs * th.x - ot.x) / h2; dk.y = (rs * th.y - ot.y) / h2; dk.z = (rs * th.z - ot.z) / h2; dk.w = (rs * th.w - ot.w) / h2;
-      ph.x = (og.x + dk.x) / fn; ph.y = (og.y + dk.y) / fn; ph.z = (og.z + dk.z) / fn; ph.w = (og.w + dk.w) / fn;
+      if constexpr (FOLD) {
+        ph.x = (og.x + rs * th.x / h2) / fn; ph.y = (og.y + rs * th.y / h2) / fn;
+        ph.z = (og.z + rs * th.z / h2) / fn; ph.w = (og.w + rs * th.w / h2) / fn;
+      } else {
+        ph.x = (og.x + dk.x) / fn; ph.y = (og.y + dk.y) / fn; ph.z = (og.z + dk.z) / fn; ph.w = (og.w + dk.w) / fn;
+      }
       *reinterpret_cast<float4*>(phi + e) = ph;
       if (dK) *reinterpret_cast<float4*>(dK + e) = dk;
       sq += ((double)ph.x * (double)ph.x + (double)ph.y * (double)ph.y) + ((double)ph.z * (double)ph.z + (double)ph.w * (double)ph.w);
       if constexpr (KSD) {
         const float4 g = theta4(G + (size_t)row0 * d + e);
-        ksd_terms(g.x, og.x, ot.x, th.x, rs, ih, ks, kd);
-        ksd_terms(g.y, og.y, ot.y, th.y, rs, ih, ks, kd);
-        ksd_terms(g.z, og.z, ot.z, th.z, rs, ih, ks, kd);
-        ksd_terms(g.w, og.w, ot.w, th.w, rs, ih, ks, kd);
+        ksd_terms(g.x, kg(og.x, ot.x), ot.x, th.x, rs, ih, ks, kd);
+        ksd_terms(g.y, kg(og.y, ot.y), ot.y, th.y, rs, ih, ks, kd);
+        ksd_terms(g.z, kg(og.z, ot.z), ot.z, th.z, rs, ih, ks, kd);
+        ksd_terms(g.w, kg(og.w, ot.w), ot.w, th.w, rs, ih, ks, kd);
       }
     }
   } else {
@@ -150,16 +163,16 @@ __global__ __launch_bounds__(256) void k_phi_finish(const float* __restrict__ OG
       float og = 0.f, ot = 0.f, rs = 0.f;
       for (int z = 0; z < split; ++z) {
         og += OG[z * zs + e];
-        ot += OT[z * zs + e];
+        if (FOLD ? need_t && z < tsplit : true) ot += OT[z * zs + e];
         rs += RS[(size_t)z * n_local + i];
       }
       const float th = elem_f32(T + (size_t)row0 * d + e);
       const float dk = (rs * th - ot) / h2;
-      const float ph = (og + dk) / fn;
+      const float ph = FOLD ? (og + rs * th / h2) / fn : (og + dk) / fn;
       phi[e] = ph;
       if (dK) dK[e] = dk;
       sq += (double)ph * (double)ph;
-      if constexpr (KSD) ksd_terms(elem_f32(G + (size_t)row0 * d + e), og, ot, th, rs, ih, ks, kd);
+      if constexpr (KSD) ksd_terms(elem_f32(G + (size_t)row0 * d + e), kg(og, ot), ot, th, rs, ih, ks, kd);
     }
   }
   double part[NS];                      // this workgroup's partials, set k at sqpart[k * gridDim.x + blockIdx.x]
@@ -224,7 +237,8 @@ int stein_make_layout(int64_t n_local, int64_t n, int64_t d, int dtype, int flag
   if (d < 1 || n_local < 1 || n_local > n) return fail(STEIN_E_SHAPE, "bad shape n_local=%lld n=%lld d=%lld", (long long)n_local, (long long)n, (long long)d);
   if (n > (1ll << 30) || d > (1ll << 24) || n * d > (1ll << 40)) return fail(STEIN_E_SHAPE, "shape too large");
   if (dtype != STEIN_F32 && dtype != STEIN_BF16) return fail(STEIN_E_UNSUPPORTED, "dtype %d", dtype);
-  if (flags & ~(STEIN_FLAG_X3 | STEIN_FLAG_TIMING | STEIN_FLAG_TILED | STEIN_FLAG_NO_WINDOW | STEIN_FLAG_RANK_WINDOW | STEIN_FLAG_TILE_DISTANCE | STEIN_FLAG_TIMING_CONTRACT | STEIN_FLAG_KSD)) return fail(STEIN_E_BADARG, "unknown flags 0x%x", flags);
+  if (flags & ~(STEIN_FLAG_X3 | STEIN_FLAG_TIMING | STEIN_FLAG_TILED | STEIN_FLAG_NO_WINDOW | STEIN_FLAG_RANK_WINDOW | STEIN_FLAG_TILE_DISTANCE | STEIN_FLAG_TIMING_CONTRACT | STEIN_FLAG_KSD | STEIN_FLAG_FOLD | STEIN_FLAG_NO_FOLD)) return fail(STEIN_E_BADARG, "unknown flags 0x%x", flags);
+  if ((flags & STEIN_FLAG_FOLD) && (flags & STEIN_FLAG_NO_FOLD)) return fail(STEIN_E_BADARG, "STEIN_FLAG_FOLD and STEIN_FLAG_NO_FOLD exclude each other");
   L->ld_dist = (int64_t)align_up((size_t)n, 64);
   L->tiles_m = (n_local + BM - 1) / BM;
   L->cblocks = (d + BN - 1) / BN;
@@ -239,18 +253,21 @@ int stein_make_layout(int64_t n_local, int64_t n, int64_t d, int dtype, int flag
   const double resident = x3 ? 256.0 : 768.0;
   int64_t max_split = jt / 8 > 0 ? jt / 8 : 1;
   if (max_split > 16) max_split = 16;
-  int64_t split = 1;
-  double best = -1.0;
-  for (int64_t s = 1; s <= max_split; ++s) {
-    const double rounds = (double)(base * s) / resident;
-    const double eff = rounds / ceil(rounds) - 0.004 * (double)(s - 1);
-    if (eff > best + 1e-9) { best = eff; split = s; }
-  }
-  int64_t tiles_per = (jt + split - 1) / split;
-  if (x3) tiles_per = (tiles_per + 3) / 4 * 4;   // a j range of the split kernel starts on a multiple of 128 columns (its
-                                                 // pipeline stages then never straddle a row tile's diagonal block)
-  L->jchunk = tiles_per * BK;
-  split = (jt + tiles_per - 1) / tiles_per;  // drop empty tails
+  auto choose_split = [&](int64_t base_wgs, int64_t* jchunk_out) {
+    int64_t split = 1;
+    double best = -1.0;
+    for (int64_t s = 1; s <= max_split; ++s) {
+      const double rounds = (double)(base_wgs * s) / resident;
+      const double eff = rounds / ceil(rounds) - 0.004 * (double)(s - 1);
+      if (eff > best + 1e-9) { best = eff; split = s; }
+    }
+    int64_t tiles_per = (jt + split - 1) / split;
+    if (x3) tiles_per = (tiles_per + 3) / 4 * 4;   // a j range of the split kernel starts on a multiple of 128 columns (its
+                                                   // pipeline stages then never straddle a row tile's diagonal block)
+    *jchunk_out = tiles_per * BK;
+    return (jt + tiles_per - 1) / tiles_per;  // drop empty tails
+  };
+  const int64_t split = choose_split(base, &L->jchunk);
   L->split = split;
   const int64_t elems = n_local * d;
   int64_t sqb = (elems + 1023) / 1024;
@@ -287,7 +304,38 @@ int stein_make_layout(int64_t n_local, int64_t n, int64_t d, int dtype, int flag
   L->x3_gt3 = t3 + tt3;
   L->x3_sc = t3 + 2 * tt3;   // scales area: float[4 dc + 4] + u32[2 dc]
   const size_t scb = align_up((size_t)(6 * L->x3_dc + 4) * 4, 256);
-  put(STEIN_WS_PLANES, (flags & STEIN_FLAG_X3) ? t3 + 2 * tt3 + scb : 0);
+  // The folded operand (stein_x3.hip): the fused single-rank call on the split path with fp32 inputs, where it pays or is
+  // forced.  Its contraction has half the workgroups per row tile (the 128-column blocks of ONE matrix, paired), so it gets a
+  // j split of its own by the same rule -- C3: 128 row tiles x 1 workgroup x 2 ranges = one round of the 256 CUs; C5: 1024 x 1
+  // = four rounds; C4: 64 x 8 = two.  Its partial sums reuse storage that is dead by then, so a workspace does not grow with
+  // the default gate: K.W takes PART_G and PART_T together (half the workgroups per range: rarely more than twice the
+  // ranges), K.theta (dK / KSD calls; one range, so that the W half never depends on it) and the row sums take theta's
+  // row-major planes, which only the distance pass reads.  Where that does not fit, a forced fold appends the three to the
+  // PLANES section and the default gate leaves the call unfolded.
+  const bool fold_forced = (flags & STEIN_FLAG_FOLD) != 0;
+  L->fold = x3 && dtype == STEIN_F32 && n_local == n && !small_path && !(flags & STEIN_FLAG_NO_FOLD) &&
+            (fold_forced || stein_fold_pays(n, d));
+  L->fsplit = L->fjchunk = 0;
+  size_t fold_extra = 0;
+  if (L->fold) {
+    L->fsplit = choose_split(L->tiles_m * ((L->cblocks + 1) / 2), &L->fjchunk);
+    const size_t ow = align_up((size_t)L->fsplit * n_local * d * 4, 256), ot = align_up((size_t)n_local * d * 4, 256),
+                 rs = align_up((size_t)L->fsplit * n_local * 4, 256);
+    if (ow <= L->off[STEIN_WS_PART_RS] - L->off[STEIN_WS_PART_G] && ot + rs <= t3) {
+      L->fold_ow = L->off[STEIN_WS_PART_G];
+      L->fold_ot = at + L->x3_t3;   // (`at`: where the PLANES section is about to be put)
+      L->fold_rs = L->fold_ot + ot;
+    } else if (fold_forced) {
+      L->fold_ow = at + t3 + 2 * tt3 + scb;
+      L->fold_ot = L->fold_ow + ow;
+      L->fold_rs = L->fold_ot + ot;
+      fold_extra = ow + ot + rs;
+    } else {
+      L->fold = 0;
+      L->fsplit = L->fjchunk = 0;
+    }
+  }
+  put(STEIN_WS_PLANES, (flags & STEIN_FLAG_X3) ? t3 + 2 * tt3 + scb + fold_extra : 0);
   L->total = at;
   return STEIN_OK;
 }
@@ -335,11 +383,20 @@ extern "C" int stein_workspace_layout(int64_t n_local, int64_t n, int64_t d, int
   return STEIN_OK;
 }
 
+extern "C" int stein_layout_folds(int64_t n_local, int64_t n, int64_t d, int dtype, int flags, int* out) {
+  if (!out) return fail(STEIN_E_BADARG, "out is NULL");
+  SteinLayout L;
+  int rc = stein_make_layout(n_local, n, d, dtype, flags, &L);
+  if (rc) return rc;
+  *out = (int)L.fold;
+  return STEIN_OK;
+}
+
 extern "C" int stein_x3_prepare(const void* theta_all, const void* score_all, int64_t n, int64_t d, int dtype,
                                 void* x3_planes, size_t planes_bytes, void* stream) {
   if ((!theta_all && !score_all) || !x3_planes) return fail(STEIN_E_BADARG, "NULL pointer");
   SteinLayout L;
-  int rc = stein_make_layout(n, n, d, dtype, STEIN_FLAG_X3, &L);
+  int rc = stein_make_layout(n, n, d, dtype, STEIN_FLAG_X3 | STEIN_FLAG_NO_FOLD, &L);
   if (rc) return rc;
   if (planes_bytes < L.total - L.off[STEIN_WS_PLANES])
     return fail(STEIN_E_WORKSPACE, "planes buffer %zu < %zu bytes", planes_bytes, L.total - L.off[STEIN_WS_PLANES]);
@@ -380,7 +437,7 @@ static int distance_block_impl(const void* theta_all, const float* r_all, int64_
   u64* h0 = (u64*)hist_level0;
   if (x3_planes) {
     SteinLayout L;
-    int rc = stein_make_layout(n_local, n, d, dtype, STEIN_FLAG_X3, &L);
+    int rc = stein_make_layout(n_local, n, d, dtype, STEIN_FLAG_X3 | STEIN_FLAG_NO_FOLD, &L);
     if (rc) return rc;
     return stein_x3_distance((const char*)x3_planes, L, dtype, r_all, dist_out, n, d, row0, n_local, ld_dist, h0, sym, s,
                              spec, spec_buf, (flags & STEIN_STAGE_TILES) ? -1 : ((flags & STEIN_STAGE_PANEL) ? 1 : 0));
@@ -431,7 +488,7 @@ extern "C" int stein_contract_partial(const float* dist, int64_t ld_dist, const 
     return fail(STEIN_E_UNSUPPORTED, "contract: dtype %d (bf16 inputs need the operand planes)", dtype);
   if (row0 < 0 || row0 + n_local > n) return fail(STEIN_E_SHAPE, "bad row block");
   SteinLayout L;
-  int rc = stein_make_layout(n_local, n, d, dtype, x3_planes ? STEIN_FLAG_X3 : 0, &L);
+  int rc = stein_make_layout(n_local, n, d, dtype, x3_planes ? STEIN_FLAG_X3 | STEIN_FLAG_NO_FOLD : 0, &L);
   if (rc) return rc;
   if (ws_bytes < L.off[STEIN_WS_PLANES]) return fail(STEIN_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L.off[STEIN_WS_PLANES]);
   if (ld_dist != L.ld_dist) return fail(STEIN_E_SHAPE, "ld_dist %lld != %lld", (long long)ld_dist, (long long)L.ld_dist);
@@ -457,25 +514,35 @@ static int contract_finish_impl(const void* theta_all, const void* score_all, in
   int rc = stein_make_layout(n_local, n, d, dtype, flags, &L);
   if (rc) return rc;
   if (ws_bytes < L.off[STEIN_WS_PLANES]) return fail(STEIN_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L.off[STEIN_WS_PLANES]);
-  const StepViews v = stein_step_views(L, workspace);
+  StepViews v = stein_step_views(L, workspace);
+  if (L.fold) {   // (fused call only: the staged entry points ask for STEIN_FLAG_NO_FOLD) the folded contraction's partials
+    if (ws_bytes < L.total) return fail(STEIN_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L.total);
+    v.OG = (float*)((char*)workspace + L.fold_ow);
+    v.OT = (float*)((char*)workspace + L.fold_ot);
+    v.RS = (float*)((char*)workspace + L.fold_rs);
+  }
+  const int nsplit = (int)(L.fold ? L.fsplit : L.split);
   hipStream_t s = (hipStream_t)stream;
   auto al16 = [](const void* p) { return ((uintptr_t)p & 15u) == 0; };
   const size_t tsz = dtype == STEIN_BF16 ? 2 : 4;
   auto rows_aligned = [&](const void* p) { return (((uintptr_t)p + (size_t)row0 * d * tsz) & (4 * tsz - 1)) == 0; };
   const int vec = (d % 4 == 0) && al16(v.OG) && al16(v.OT) && al16(phi_local) && al16(dK_out) && rows_aligned(theta_all) &&
                   (!ksd || rows_aligned(score_all));
-  auto launch = [&](auto tin, auto ksd_tag) {
+  auto launch = [&](auto tin, auto ksd_tag, auto fold_tag) {
     using TIN = decltype(tin);
-    hipLaunchKernelGGL((k_phi_finish<TIN, decltype(ksd_tag)::value>), dim3((unsigned)L.sq_blocks), dim3(256), 0, s, v.OG,
-                       v.OT, v.RS, (const TIN*)theta_all, h2_dev, phi_local, dK_out, v.SQ, (int)n, (int)d, (int)row0,
-                       (int)n_local, (int)L.split, vec, fuse_done, sqnorm_out, (const TIN*)score_all);
+    hipLaunchKernelGGL((k_phi_finish<TIN, decltype(ksd_tag)::value, decltype(fold_tag)::value>), dim3((unsigned)L.sq_blocks),
+                       dim3(256), 0, s, v.OG, v.OT, v.RS, (const TIN*)theta_all, h2_dev, phi_local, dK_out, v.SQ, (int)n, (int)d,
+                       (int)row0, (int)n_local, nsplit, L.fold ? 1 : nsplit, vec, fuse_done, sqnorm_out, (const TIN*)score_all);
   };
-  if (dtype == STEIN_BF16) {
-    if (ksd) launch((unsigned short)0, std::true_type());
-    else launch((unsigned short)0, std::false_type());
+  if (L.fold) {   // fp32 inputs by construction
+    if (ksd) launch(0.f, std::true_type(), std::true_type());
+    else launch(0.f, std::false_type(), std::true_type());
+  } else if (dtype == STEIN_BF16) {
+    if (ksd) launch((unsigned short)0, std::true_type(), std::false_type());
+    else launch((unsigned short)0, std::false_type(), std::false_type());
   } else {
-    if (ksd) launch(0.f, std::true_type());
-    else launch(0.f, std::false_type());
+    if (ksd) launch(0.f, std::true_type(), std::false_type());
+    else launch(0.f, std::false_type(), std::false_type());
   }
   LAUNCH_CHECK("k_phi_finish");
   return fuse_done ? STEIN_OK : sum_partials(v.SQ, (int)L.sq_blocks, ksd, sqnorm_out, s);
@@ -487,8 +554,9 @@ extern "C" int stein_contract_finish(const void* theta_all, int64_t n, int64_t d
   if (flags & STEIN_FLAG_KSD)
     return fail(STEIN_E_BADARG, "STEIN_FLAG_KSD: stein_contract_finish has no score operand; the statistic comes from "
                                 "stein_svgd_phi, stein_rank_finish or stein_rank_step");
+  // (a staged call finishes what stein_contract_partial left: K.[G | theta], never the folded form)
   return contract_finish_impl(theta_all, nullptr, n, d, row0, n_local, dtype, h2_dev, phi_local, sqnorm_out, dK_out,
-                              workspace, ws_bytes, flags, stream, nullptr);
+                              workspace, ws_bytes, (flags & ~STEIN_FLAG_FOLD) | STEIN_FLAG_NO_FOLD, stream, nullptr);
 }
 
 extern "C" int stein_kernel_contract(const float* dist, int64_t ld_dist, const void* theta_all, const void* score_all,
@@ -541,7 +609,9 @@ static int rank_views(int64_t n, int64_t d, int64_t row0, int64_t n_local, int d
   if (row0 < 0 || n_local < 1 || row0 + n_local > n) return fail(STEIN_E_SHAPE, "bad row block");
   if (flags & ~(STEIN_FLAG_X3 | STEIN_FLAG_TILED | STEIN_FLAG_RANK_WINDOW | STEIN_FLAG_TIMING | STEIN_FLAG_KSD)) return fail(STEIN_E_BADARG, "unknown flags 0x%x", flags);
   SteinLayout L;
-  int rc = stein_make_layout(n_local, n, d, dtype, (flags & (STEIN_FLAG_X3 | STEIN_FLAG_TILED | STEIN_FLAG_KSD)) | STEIN_FLAG_TILED, &L);
+  // (the rank segments keep K.[G | theta]: the score's planes are built while its all-gather overlaps the distance pass,
+  // before h2 exists.  The workspace may have been sized with the fold area -- it only adds bytes at the end.)
+  int rc = stein_make_layout(n_local, n, d, dtype, (flags & (STEIN_FLAG_X3 | STEIN_FLAG_TILED | STEIN_FLAG_KSD)) | STEIN_FLAG_TILED | STEIN_FLAG_NO_FOLD, &L);
   if (rc) return rc;
   if (dtype == STEIN_BF16 && !(flags & STEIN_FLAG_X3)) return fail(STEIN_E_UNSUPPORTED, "bf16 inputs need STEIN_FLAG_X3");
   if (ws_bytes < L.total) return fail(STEIN_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L.total);
@@ -616,7 +686,8 @@ extern "C" int stein_rank_finish(const void* theta_all, const void* score_all, i
     return rc;
   if ((rc = clk.mark(STEIN_T_FINISH, s))) return rc;
   rc = contract_finish_impl(theta_all, score_all, n, d, row0, n_local, dtype, h2_dev, phi_local, sqnorm_out, dK_out,
-                            workspace, ws_bytes, (v.planes ? STEIN_FLAG_X3 : 0) | (flags & STEIN_FLAG_KSD), stream, nullptr);
+                            workspace, ws_bytes, (v.planes ? STEIN_FLAG_X3 : 0) | (flags & STEIN_FLAG_KSD) | STEIN_FLAG_NO_FOLD,
+                            stream, nullptr);
   return rc ? rc : clk.mark(STEIN_T_NSTAGES, s);
 }
 
@@ -706,7 +777,7 @@ extern "C" int stein_timing_read(float* ms_out, int max_calls, int* calls_out) {
 // (k_split's grid gets a third slice that does the prologue's work) -- one launch less on the latency-bound sizes this
 // dtype is for.
 static int fused_prologue(const StepViews& v, const void* theta_all, const void* score_all, int64_t n, int64_t d, int dtype,
-                          int flags, hipStream_t s) {
+                          int flags, hipStream_t s, int fold) {
   const SteinLayout& L = v.L;
   PrologueArgs pa;
   pa.n = (int)n; pa.d = (int)d; pa.r = v.r; pa.st = v.sel; pa.sp = v.spec; pa.fs = v.fuse; pa.total = (u64)(n * n);
@@ -717,6 +788,7 @@ static int fused_prologue(const StepViews& v, const void* theta_all, const void*
   pa.hsync = (u32*)v.table; pa.hsync_words = (int)(sizeof(HistSync) / 4);
   pa.neutral_sc = (dtype == STEIN_BF16 && v.planes) ? (float*)(v.planes + L.x3_sc) : (float*)nullptr;
   pa.dc = (int)L.x3_dc;
+  pa.folded = fold ? 1u : 0u;
   if (dtype == STEIN_BF16 && v.planes)
     return stein_x3_split(theta_all, score_all, dtype, n, d, L, v.planes, s, (HistSync*)v.table, true, &pa);
   const dim3 grid((unsigned)((n + 3) / 4 + PRO_INIT_BLOCKS));
@@ -725,7 +797,7 @@ static int fused_prologue(const StepViews& v, const void* theta_all, const void*
   else
     hipLaunchKernelGGL(k_prologue<float>, grid, dim3(256), 0, s, (const float*)theta_all, pa);
   LAUNCH_CHECK("k_prologue");
-  return v.planes ? stein_x3_split(theta_all, score_all, dtype, n, d, L, v.planes, s, (HistSync*)v.table, false, nullptr)
+  return v.planes ? stein_x3_split(theta_all, score_all, dtype, n, d, L, v.planes, s, (HistSync*)v.table, false, nullptr, fold)
                   : STEIN_OK;
 }
 
@@ -765,7 +837,10 @@ extern "C" int stein_svgd_phi(const void* theta_all, const void* score_all, int6
   // launch.  fp32 inputs: k_prologue, k_colmax, k_split, distance, k_spec_select, k_hist_all, contraction, k_phi_finish:
   // eight launches whatever n (the last workgroups of k_colmax and k_phi_finish are found with two-level completion counts,
   // HistSync, so no grid is too large for them); bf16 inputs: six.
-  if ((rc = fused_prologue(v, theta_all, score_all, n, d, dtype, flags, s))) return rc;
+  // folded operand (L.fold: split path, fp32 inputs, where it pays or is forced): the contraction multiplies K with
+  // W = G - theta / h2 alone; with dK_out or the Stein discrepancy, with [W | theta] -- phi comes from the W half either way
+  const bool fold_theta = L.fold && (dK_out || (flags & STEIN_FLAG_KSD));
+  if ((rc = fused_prologue(v, theta_all, score_all, n, d, dtype, flags, s, L.fold ? (fold_theta ? 2 : 1) : 0))) return rc;
   if ((rc = clk.mark(STEIN_T_DISTANCE, s))) return rc;
   // single rank: the block is the whole symmetric matrix -> upper-triangle distance pass with mirrored stores,
   // level-0 histogram taken in its epilogue, levels 1-2 read the upper triangle only
@@ -778,13 +853,16 @@ extern "C" int stein_svgd_phi(const void* theta_all, const void* score_all, int6
   // the split path's symmetric distance pass stores only the tiles on and above the diagonal
   const int df = v.planes ? (STEIN_STAGE_SYMMETRIC | STEIN_STAGE_UPPER) : STEIN_STAGE_SYMMETRIC;
   if (K_out && (rc = stein_kernel_matrix(v.D, L.ld_dist, n_local, n, h2_out, K_out, n, df, stream))) return rc;
+  if (L.fold && (rc = stein_x3_split_w((const float*)theta_all, (const float*)score_all, n, d, L, v.planes, h2_out, s))) return rc;
   if ((rc = clk.mark(STEIN_T_CONTRACT, s))) return rc;
-  if ((rc = stein_contract_partial(v.D, L.ld_dist, theta_all, score_all, n, d, row0, n_local, dtype, h2_out, v.planes,
-                                   workspace, ws_bytes, df, stream)))
-    return rc;
+  if (L.fold) rc = stein_x3_contract_fold(v.D, L.ld_dist, (char*)workspace, L, h2_out, n, d, fold_theta, s);
+  else rc = stein_contract_partial(v.D, L.ld_dist, theta_all, score_all, n, d, row0, n_local, dtype, h2_out, v.planes,
+                                   workspace, ws_bytes, df, stream);
+  if (rc) return rc;
   if ((rc = clk.mark(STEIN_T_FINISH, s))) return rc;
+  const int keep = STEIN_FLAG_KSD | STEIN_FLAG_TILED | STEIN_FLAG_FOLD | STEIN_FLAG_NO_FOLD;   // what the layout depends on
   if ((rc = contract_finish_impl(theta_all, score_all, n, d, row0, n_local, dtype, h2_out, phi_local, sqnorm_out, dK_out,
-                                 workspace, ws_bytes, (v.planes ? STEIN_FLAG_X3 : 0) | (flags & STEIN_FLAG_KSD), stream,
+                                 workspace, ws_bytes, (v.planes ? STEIN_FLAG_X3 : 0) | (flags & keep), stream,
                                  (HistSync*)v.table)))
     return rc;
   return clk.mark(STEIN_T_NSTAGES, s);

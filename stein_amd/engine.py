@@ -189,6 +189,8 @@ class SvgdEngine:
               (tests substitute a NumPy model to exercise the collective protocol on CPU/gloo.)
     ksd     : also compute the kernelized Stein discrepancy of the particles under the step's own kernel and bandwidth
               (STEIN_FLAG_KSD): stein_discrepancy() after a step.  Off by default; nothing else changes with it on.
+    fold    : None (default): the single-rank fused call takes the folded contraction where it pays; True / False force
+              and forbid it (STEIN_FLAG_FOLD / STEIN_FLAG_NO_FOLD).
     comm    : who issues the collectives of a sharded step.  "torch" (and "auto", the default): torch.distributed
               collectives between the rank segments -- the path every multi-rank test has run.  "native": the library,
               on its own RCCL communicator, the whole step one C call (stein_rank_step; 68 us of host time per step
@@ -197,7 +199,8 @@ class SvgdEngine:
     """
 
     def __init__(self, n, d, device="cuda", group=None, stages=None, x3=None, dtype=torch.float32, small=True,
-                 window=True, force_collectives=False, comm="auto", tile_distance=False, dist_window=None, ksd=False):
+                 window=True, force_collectives=False, comm="auto", tile_distance=False, dist_window=None, ksd=False,
+                 fold=None):
         self.n, self.d = int(n), int(d)
         # dtype of the theta / score tensors handed to compute_phi: float32, or bfloat16 (BASELINE config 2: the
         # values are used as they are, K is rounded to bf16, one bf16 MFMA per product, fp32 accumulation)
@@ -218,6 +221,11 @@ class SvgdEngine:
         # panel-resident kernel that large blocks with d <= 256 take by default, stein_dpanel.hip)
         self.flags = ((_lib.FLAG_X3 if self.x3 else 0) | (0 if small else _lib.FLAG_TILED) |
                       (0 if window else _lib.FLAG_NO_WINDOW) | (_lib.FLAG_TILE_DISTANCE if tile_distance else 0))
+        # fold: the fused call's folded contraction (K with W = G - theta / h2 alone: half the matrix-core work; include/
+        # steinhip.h, STEIN_FLAG_FOLD).  None = where the library finds it pays (large blocks), True = wherever it is
+        # eligible (split path, fp32 inputs), False = never.  self.fold (below) says what this engine's fused call does.
+        if fold is not None:
+            self.flags |= _lib.FLAG_FOLD if fold else _lib.FLAG_NO_FOLD
         # ksd=True: the step also sums the kernelized Stein discrepancy (sqnorm grows to [|phi|^2, S, S_diag], see _sums);
         # only the fused call and the rank segments compute it
         self.ksd = bool(ksd)
@@ -257,6 +265,9 @@ class SvgdEngine:
                                                           _lib.BF16 if dtype == torch.bfloat16 else _lib.F32)
         self.ws_bytes, self._offs = total, offs
         self.ld_dist, self.split = extra[_lib.WSX_LD_DIST], extra[_lib.WSX_SPLIT]
+        # does the fused call contract K with W = G - theta / h2 alone?  (the library's decision, not this module's)
+        self.fold = (not self.sharded) and isinstance(self.stages, HipStages) and _lib.layout_folds(
+            self.n_local, self.n, self.d, _lib.BF16 if dtype == torch.bfloat16 else _lib.F32, self.flags)
         dev = self.device
         self.ws = torch.empty(total, dtype=torch.uint8, device=dev)
         # the SELECT section carries the median predictor from call to call and is trusted once its magic word matches:
@@ -376,6 +387,10 @@ class SvgdEngine:
     def select_state(self):
         """radix-select state (64 bytes) followed by the speculative-window state (64 bytes)"""
         return self._section(_lib.WS_SELECT, 128, torch.uint8)
+
+    def select_state_bytes(self, offset, count):
+        """`count` bytes of the SELECT section from `offset` on (the words of _lib.*_OFFSET)"""
+        return self._section(_lib.WS_SELECT, _lib.SELECT_BYTES, torch.uint8)[offset:offset + count]
 
     def window_stats(self):
         """(medians recorded since the predictor started, how many of them the speculative window delivered) --
