@@ -194,16 +194,12 @@ extern "C" int stein_rank_step(void* comm, const void* theta_local, const void* 
   const int64_t n_local = n / c->nranks, row0 = (int64_t)c->rank * n_local;
   const hipStream_t stream = static_cast<hipStream_t>(stream_v);
   const bool window = (flags & STEIN_FLAG_RANK_WINDOW) != 0;
-  const int seg_flags = flags & (STEIN_FLAG_X3 | STEIN_FLAG_RANK_WINDOW | STEIN_FLAG_KSD);
-  if (flags & ~(STEIN_FLAG_X3 | STEIN_FLAG_RANK_WINDOW | STEIN_FLAG_TIMING | STEIN_FLAG_TILED | STEIN_FLAG_KSD))
-    return stein_fail(STEIN_E_BADARG, "unknown flags 0x%x", flags);
 
-  // the sections the collectives touch (the same layout the segments derive)
-  SteinLayout L;
-  int rc = stein_make_layout(n_local, n, d, dtype, (flags & (STEIN_FLAG_X3 | STEIN_FLAG_KSD)) | STEIN_FLAG_TILED | STEIN_FLAG_NO_FOLD, &L);
+  // the step's one layout and views: the segments below run on them, and the collectives touch their sections
+  const BlockShape b{n, d, row0, n_local, dtype};
+  StepViews v;
+  int rc = stein_rank_views(b, workspace, ws_bytes, flags, &v);
   if (rc) return rc;
-  if (ws_bytes < L.total) return stein_fail(STEIN_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L.total);
-  const StepViews v = stein_step_views(L, workspace);
 
   // Everything a rank can get wrong by itself has been checked above, before its first collective.  From here on a failure
   // goes through fail_in_step: the communicator is aborted, so the peers' collectives fail instead of waiting for ever.
@@ -230,12 +226,12 @@ extern "C" int stein_rank_step(void* comm, const void* theta_local, const void* 
   STEP_HIP(hipEventRecord(c->join, c->side));
 
   // (2) row norms, theta's planes, the [n_local, n] distance block with the median's first counts
-  STEP_TRY(stein_rank_begin(theta_all, n, d, row0, n_local, dtype, workspace, ws_bytes, seg_flags, stream));
+  STEP_TRY(stein_rank_begin_on(v, b, theta_all, window, stream));
 
   auto score_planes = [&]() -> int {   // first reader of the gathered score rows: the caller's stream joins the side stream
     if (hipStreamWaitEvent(stream, c->join, 0) != hipSuccess) return stein_fail(STEIN_E_HIP, "hipStreamWaitEvent failed");
     if (!(flags & STEIN_FLAG_X3)) return STEIN_OK;
-    return stein_x3_split(nullptr, score_all, dtype, n, d, L, v.planes, stream);
+    return stein_x3_split(v, nullptr, score_all, dtype, n, d, stream, nullptr);
   };
   auto level_sum = [&](int level) -> int {   // hist[level] summed over the ranks, in place
     u64* h = v.hist + (size_t)level * 2 * STEIN_HIST_BINS;
@@ -245,13 +241,10 @@ extern "C" int stein_rank_step(void* comm, const void* theta_local, const void* 
   };
   auto radix = [&](bool need_level0_pass) -> int {
     int rr;
-    if (need_level0_pass &&
-        (rr = stein_rank_radix(0, 1, n, d, row0, n_local, dtype, workspace, ws_bytes, seg_flags, h2_out, median_out, stream)))
-      return rr;
+    if (need_level0_pass && (rr = stein_rank_radix_on(v, b, 0, 1, h2_out, median_out, stream))) return rr;
     for (int level = 0; level < STEIN_HIST_LEVELS; ++level) {
       if ((rr = level_sum(level))) return rr;
-      if ((rr = stein_rank_radix(level, 0, n, d, row0, n_local, dtype, workspace, ws_bytes, seg_flags, h2_out, median_out, stream)))
-        return rr;
+      if ((rr = stein_rank_radix_on(v, b, level, 0, h2_out, median_out, stream))) return rr;
     }
     return STEIN_OK;
   };
@@ -260,8 +253,7 @@ extern "C" int stein_rank_step(void* comm, const void* theta_local, const void* 
   int hit = -1;
   if (window) {
     STEP_RCCL(g_rccl.AllReduce(v.table, v.table, SPEC_TABLE, ncclUint64, ncclSum, c->comm, stream));
-    STEP_TRY(stein_rank_pick(n, d, row0, n_local, dtype, workspace, ws_bytes, seg_flags, h2_out, median_out, c->flags_host,
-                             stream));
+    STEP_TRY(stein_rank_pick_on(v, n, h2_out, median_out, c->flags_host, stream));
     STEP_HIP(hipEventRecord(c->flags_ready, stream));
     STEP_TRY(score_planes());   // work that does not depend on the flag: covers the host's wake-up
     STEP_HIP(hipEventSynchronize(c->flags_ready));
@@ -275,8 +267,7 @@ extern "C" int stein_rank_step(void* comm, const void* theta_local, const void* 
   if (window_hit_out) *window_hit_out = hit;
 
   // (4) the contraction on the local rows, phi, and the global |phi|^2 (STEIN_FLAG_KSD: and the two Stein discrepancy sums)
-  STEP_TRY(stein_rank_finish(theta_all, score_all, n, d, row0, n_local, dtype, h2_out, phi_local, sqnorm_out, dK_out,
-                             workspace, ws_bytes, seg_flags | (flags & STEIN_FLAG_TIMING), stream));
+  STEP_TRY(stein_rank_finish_on(v, b, theta_all, score_all, h2_out, phi_local, sqnorm_out, dK_out, flags, stream));
   STEP_RCCL(g_rccl.AllReduce(sqnorm_out, sqnorm_out, (flags & STEIN_FLAG_KSD) ? 3 : 1, ncclFloat64, ncclSum, c->comm, stream));
 #undef STEP_TRY
 #undef STEP_RCCL

@@ -623,11 +623,9 @@ __global__ __launch_bounds__(DP_THREADS, 2) void k_distance_panel_deep(const u16
 // ================================================================================================
 // host side
 // ================================================================================================
-bool stein_dpanel_ok(const SteinLayout& L, int dtype, int64_t n, int64_t row0, int64_t n_local, bool level0_only,
-                     bool any_size) {
-  const int np = stein_x3_kind(dtype);
-  const int64_t ntk = L.x3_dk / 32;
-  (void)level0_only;                                               // (round 4: the epilogue takes the level-0 histogram too)
+bool stein_dpanel_ok(const StepViews& v, const BlockShape& b, bool any_size) {
+  const int np = stein_x3_kind(b.dtype);
+  const int64_t ntk = v.L.x3_dk / 32, n = b.n, row0 = b.row0, n_local = b.n_local;
   if ((n & 127) || (n_local & 127) || (row0 & 127)) return false;
   // (np * ntk > 16: the panel does not fit 128 KB of LDS -> k_distance_panel_deep walks K in chunks)
   // Small blocks: the launch has a floor of ~20 us (one 157 KB workgroup per CU, a panel load, a barrier) where the per-tile
@@ -638,22 +636,20 @@ bool stein_dpanel_ok(const SteinLayout& L, int dtype, int64_t n, int64_t row0, i
   return any_size || strips >= 256 * 8 * 8 || (strips >= 256 * 8 * 2 && np * ntk >= 16);
 }
 
-int stein_dpanel_distance(const char* planes, const SteinLayout& L, int dtype, const float* r_all, float* dist_out,
-                          int64_t n, int64_t row0, int64_t n_local, int64_t ld_dist, bool symmetric, hipStream_t stream,
-                          SpecState* spec, u64* spec_buf, u64* hist0) {
-  const u16* T3 = reinterpret_cast<const u16*>(planes + L.x3_t3);
-  const float* two_s = reinterpret_cast<const float*>(planes + L.x3_sc) + 4 * L.x3_dc + 1;
-  const int ntk = (int)(L.x3_dk / 32);
-  const int tiles_m = (int)(n_local / 128), tiles_n = (int)(n / 128);
+int stein_dpanel_distance(const StepViews& v, const BlockShape& b, bool symmetric, bool window, hipStream_t stream) {
+  const int ntk = (int)(v.L.x3_dk / 32);
+  const int tiles_m = (int)(b.n_local / 128), tiles_n = (int)(b.n / 128);
+  SpecState* spec = window ? v.spec : nullptr;
+  u64* spec_buf = window ? v.spec_buf : nullptr;
   static int ncu = 0;
   if (!ncu) {
-    int dev = 0, v = 0;
+    int dev = 0, cus = 0;
     HIP_TRY(hipGetDevice(&dev));
-    HIP_TRY(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev));
-    ncu = v > 0 ? v : 256;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    ncu = cus > 0 ? cus : 256;
   }
-  const int np = stein_x3_kind(dtype);
-#define DP_LAUNCH(KERNEL, SYM, NP) hipLaunchKernelGGL((KERNEL<SYM, NP>), dim3((unsigned)ncu), dim3(DP_THREADS), 0, stream, T3, ntk, r_all, dist_out, (int)row0, tiles_m, tiles_n, (long)ld_dist, two_s, spec, spec_buf, hist0)
+  const int np = stein_x3_kind(b.dtype);
+#define DP_LAUNCH(KERNEL, SYM, NP) hipLaunchKernelGGL((KERNEL<SYM, NP>), dim3((unsigned)ncu), dim3(DP_THREADS), 0, stream, v.T3, ntk, v.r, v.D, (int)b.row0, tiles_m, tiles_n, (long)v.L.ld_dist, v.two_s, spec, spec_buf, v.hist)
   if (np * ntk <= 16) {
     if (np == 1) { if (symmetric) DP_LAUNCH(k_distance_panel, true, 1); else DP_LAUNCH(k_distance_panel, false, 1); }
     else { if (symmetric) DP_LAUNCH(k_distance_panel, true, 2); else DP_LAUNCH(k_distance_panel, false, 2); }

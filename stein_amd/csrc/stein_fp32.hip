@@ -247,34 +247,35 @@ static void launch_distance(long nblk, hipStream_t s, const float* T, const floa
                      ld, tiles_m, tiles_n, hist0, spec, spec_buf);
 }
 
-
-int stein_fp32_distance(const float* T, const float* r_all, float* dist_out, int64_t n, int64_t d, int64_t row0,
-                        int64_t n_local, int64_t ld_dist, u64* h0, bool sym, hipStream_t s, SpecState* spec,
-                        u64* spec_buf) {
-  const int tiles_m = (int)((n_local + BM - 1) / BM), tiles_n = (int)((n + BN - 1) / BN);
+int stein_fp32_distance(const StepViews& v, const BlockShape& b, const float* T, bool sym, bool window, hipStream_t s) {
+  const int tiles_m = (int)((b.n_local + BM - 1) / BM), tiles_n = (int)((b.n + BN - 1) / BN);
   const long nblk = distance_grid(sym, tiles_m, tiles_n);
-  const bool vec = (d % 4 == 0) && (((uintptr_t)T & 15) == 0);
-  if (vec && sym) launch_distance<true, true>(nblk, s, T, r_all, dist_out, (int)n, (int)d, (int)row0, (int)n_local, (long)ld_dist, tiles_m, tiles_n, h0, spec, spec_buf);
-  else if (vec) launch_distance<true, false>(nblk, s, T, r_all, dist_out, (int)n, (int)d, (int)row0, (int)n_local, (long)ld_dist, tiles_m, tiles_n, h0, spec, spec_buf);
-  else if (sym) launch_distance<false, true>(nblk, s, T, r_all, dist_out, (int)n, (int)d, (int)row0, (int)n_local, (long)ld_dist, tiles_m, tiles_n, h0, spec, spec_buf);
-  else launch_distance<false, false>(nblk, s, T, r_all, dist_out, (int)n, (int)d, (int)row0, (int)n_local, (long)ld_dist, tiles_m, tiles_n, h0, spec, spec_buf);
+  if (nblk > 0x7fffffffl) return stein_fail(STEIN_E_SHAPE, "too many tiles");
+  const bool vec = (b.d % 4 == 0) && (((uintptr_t)T & 15) == 0);
+  SpecState* spec = window ? v.spec : nullptr;
+  u64* spec_buf = window ? v.spec_buf : nullptr;
+#define FP32_DIST(VEC, SYM) launch_distance<VEC, SYM>(nblk, s, T, v.r, v.D, (int)b.n, (int)b.d, (int)b.row0, (int)b.n_local, (long)v.L.ld_dist, tiles_m, tiles_n, v.hist, spec, spec_buf)
+  if (vec && sym) FP32_DIST(true, true);
+  else if (vec) FP32_DIST(true, false);
+  else if (sym) FP32_DIST(false, true);
+  else FP32_DIST(false, false);
+#undef FP32_DIST
   LAUNCH_CHECK("k_distance");
   return STEIN_OK;
 }
 
-int stein_fp32_contract_partial(const float* dist, int64_t ld_dist, const float* T, const float* G, const SteinLayout& L,
-                                const float* h2_dev, float* OG, float* OT, float* RS, int64_t n, int64_t d,
-                                int64_t n_local, hipStream_t s) {
-  const long nblk = (long)L.tiles_m * 2 * L.cblocks * L.split;
-  const bool vec = (d % 4 == 0) && (((uintptr_t)T & 15) == 0) && (((uintptr_t)G & 15) == 0);
+int stein_fp32_contract_partial(const StepViews& v, const BlockShape& b, const float* T, const float* G, const float* h2_dev,
+                                hipStream_t s) {
+  const SteinLayout& L = v.L;
+  const long nblk = (long)L.tiles_m * 2 * L.cblocks * v.nsplit;
+  if (nblk > 0x7fffffffl) return stein_fail(STEIN_E_SHAPE, "too many tiles");
+  const bool vec = (b.d % 4 == 0) && (((uintptr_t)T & 15) == 0) && (((uintptr_t)G & 15) == 0);
   if (vec)
-    hipLaunchKernelGGL(k_phi_partial<true>, dim3((unsigned)nblk), dim3(NTHREADS), 0, s, dist, (long)ld_dist, G, T,
-                       h2_dev, OG, OT, RS, (int)n, (int)d, (int)n_local, (int)L.tiles_m, (int)L.cblocks, (int)L.split,
-                       (int)L.jchunk);
+    hipLaunchKernelGGL(k_phi_partial<true>, dim3((unsigned)nblk), dim3(NTHREADS), 0, s, v.D, (long)L.ld_dist, G, T, h2_dev,
+                       v.OG, v.OT, v.RS, (int)b.n, (int)b.d, (int)b.n_local, (int)L.tiles_m, (int)L.cblocks, v.nsplit, v.jchunk);
   else
-    hipLaunchKernelGGL(k_phi_partial<false>, dim3((unsigned)nblk), dim3(NTHREADS), 0, s, dist, (long)ld_dist, G, T,
-                       h2_dev, OG, OT, RS, (int)n, (int)d, (int)n_local, (int)L.tiles_m, (int)L.cblocks, (int)L.split,
-                       (int)L.jchunk);
+    hipLaunchKernelGGL(k_phi_partial<false>, dim3((unsigned)nblk), dim3(NTHREADS), 0, s, v.D, (long)L.ld_dist, G, T, h2_dev,
+                       v.OG, v.OT, v.RS, (int)b.n, (int)b.d, (int)b.n_local, (int)L.tiles_m, (int)L.cblocks, v.nsplit, v.jchunk);
   LAUNCH_CHECK("k_phi_partial");
   return STEIN_OK;
 }

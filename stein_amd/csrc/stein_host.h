@@ -1,4 +1,5 @@
-// stein_host.h -- host-side declarations shared by the library's translation units (internal: the ABI is include/steinhip.h)
+// stein_host.h -- host-side declarations shared by the library's translation units (internal: the ABI is include/steinhip.h):
+// the views of one call (StepViews), the layout flags of each family of entry point, and the stage functions that take them
 #pragma once
 
 #include "stein_common.h"
@@ -19,16 +20,55 @@ static inline SpecState* spec_of(void* select_state) { return (SpecState*)((char
 static inline FuseState* fuse_of(void* select_state) { return (FuseState*)((char*)spec_of(select_state) + sizeof(SpecState)); }
 static inline u64* spec_table_of(void* spec_buf) { return (u64*)spec_buf + SPEC_TABLE_AT; }
 
-// every section of one workspace (stein_workspace_layout) as a pointer; planes is NULL when the layout has none
+// rows [row0, row0 + n_local) of n particles with d parameters, inputs of dtype (STEIN_F32 / STEIN_BF16)
+struct BlockShape { int64_t n, d, row0, n_local; int dtype; };
+
+// The scales area at SteinLayout::x3_sc of the planes buffer (stein_x3.hip): float sc[4 dc + 4], then the u32 column
+// maxima [score | theta] the scales are made from.  As float indices from sc:
+static inline size_t x3_sc_two_s(int64_t dc) { return (size_t)(4 * dc + 1); }   // the distance pass's scale, 2^(1 - 2 sa)
+static inline size_t x3_sc_cmax(int64_t dc) { return (size_t)(4 * dc + 4); }    // where the column maxima start
+
+// Every address one C call uses, formed once (stein_step_views) from the one layout that call derives: the workspace's
+// sections, the split planes with their parts typed, and the partial sums of the contraction in use with its plan.
+// An entry point validates, derives its layout, builds these and hands them to the stage functions, which never derive a
+// layout themselves.  Layout flags by family of entry point:
+//   fused call (stein_svgd_phi)                 the caller's flags
+//   staged calls (stein_distance_block*, stein_contract_partial, stein_kernel_contract, stein_x3_prepare)
+//                                               stein_staged_flags: (planes ? X3 : 0) | NO_FOLD
+//   rank segments (stein_rank_*)                stein_rank_flags: (flags & (X3 | KSD)) | TILED | NO_FOLD
+// (stein_contract_finish has no planes argument: it takes the caller's layout flags with NO_FOLD in place of FOLD.)
 struct StepViews {
   SteinLayout L;
   float* r; float* D; u64* hist;
   SelState* sel; SpecState* spec; FuseState* fuse;
   u64* spec_buf; u64* table;   // the SPEC section and its rank-summed window table (k_hist_all's HistSync in the fused call)
+  // the split planes: the workspace's PLANES section, or the staged ABI's separately allocated buffer.  All NULL without them.
   char* planes;
+  unsigned short* T3; unsigned short* Tt3; unsigned short* Gt3;   // theta row-major | theta^T | score^T (folded: W^T)
+  float* sc; u32* cmax; float* two_s;   // the scales area, its column maxima and the distance pass's scale
+  // partial sums of the contraction: PART_G / PART_T / PART_RS; with L.fold the fold's storage, K.W in OG
   float* OG; float* OT; float* RS; double* SQ;
+  int nsplit, jchunk, tsplit;           // j ranges of OG and RS, columns per range, ranges of OT (folded: one)
 };
-StepViews stein_step_views(const SteinLayout& L, void* workspace);
+// workspace == NULL (a staged call without one): no section pointers.  planes_override: the staged ABI's planes buffer; the
+// plane pointers then come from it and never from the workspace, which need not reach its PLANES section.
+StepViews stein_step_views(const SteinLayout& L, void* workspace, void* planes_override = nullptr);
+static inline int stein_staged_flags(bool x3) { return (x3 ? STEIN_FLAG_X3 : 0) | STEIN_FLAG_NO_FOLD; }
+// (the rank segments keep K.[G | theta]: the score's planes are built while its all-gather overlaps the distance pass,
+// before h2 exists.  The workspace may have been sized with the fold area -- it only adds bytes at the end.)
+static inline int stein_rank_flags(int flags) {
+  return (flags & (STEIN_FLAG_X3 | STEIN_FLAG_KSD)) | STEIN_FLAG_TILED | STEIN_FLAG_NO_FOLD;
+}
+
+// steinhip.hip: the rank segments on views (the public stein_rank_* wrap them; stein_rank_step derives once and calls them)
+int stein_rank_views(const BlockShape& b, void* workspace, size_t ws_bytes, int flags, StepViews* v);   // validates too
+int stein_rank_begin_on(const StepViews& v, const BlockShape& b, const void* theta_all, bool window, hipStream_t stream);
+int stein_rank_pick_on(const StepViews& v, int64_t n, float* h2_out, float* median_out, void* flags_host, hipStream_t stream);
+int stein_rank_radix_on(const StepViews& v, const BlockShape& b, int level, int need_pass, float* h2_out, float* median_out,
+                        hipStream_t stream);
+int stein_rank_finish_on(const StepViews& v, const BlockShape& b, const void* theta_all, const void* score_all,
+                         const float* h2_dev, float* phi_local, double* sqnorm_out, float* dK_out, int flags,
+                         hipStream_t stream);
 
 // steinhip.hip: the device error word (one u32 per device in page-locked host memory that a kernel raises when it gave up)
 int stein_device_error_word(u32** out);
@@ -38,13 +78,11 @@ int stein_take_device_error(void);
 int stein_fused_select(const StepViews& v, int64_t n, float* h2_out, hipStream_t stream);
 
 // stein_fp32.hip: the fp32-input MFMA kernels, for calls without the split planes (what stein_x3_distance and
-// stein_x3_contract_partial are for the split path)
-int stein_fp32_distance(const float* theta_all, const float* r_all, float* dist_out, int64_t n, int64_t d, int64_t row0,
-                        int64_t n_local, int64_t ld_dist, u64* hist0, bool symmetric, hipStream_t stream, SpecState* spec,
-                        u64* spec_buf);
-int stein_fp32_contract_partial(const float* dist, int64_t ld_dist, const float* theta_all, const float* score_all,
-                                const SteinLayout& L, const float* h2_dev, float* OG, float* OT, float* RS, int64_t n,
-                                int64_t d, int64_t n_local, hipStream_t stream);
+// stein_x3_contract_partial are for the split path).  window: also feed the speculative median window (v.spec, v.spec_buf)
+int stein_fp32_distance(const StepViews& v, const BlockShape& b, const float* theta_all, bool symmetric, bool window,
+                        hipStream_t stream);
+int stein_fp32_contract_partial(const StepViews& v, const BlockShape& b, const float* theta_all, const float* score_all,
+                                const float* h2_dev, hipStream_t stream);
 
 // stein_small.hip: the whole phi computation in one kernel for n <= 160 (the reference's own example sizes)
 bool stein_small_ok(int64_t n, int64_t d, int dtype);

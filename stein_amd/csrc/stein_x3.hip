@@ -1000,23 +1000,18 @@ static void launch_split(hipStream_t stream, const TIN* theta, const TIN* score,
                      (long)L.x3_rows, (int)L.x3_dk, Tt3, Gt3, (int)L.x3_dc, (long)L.x3_nk, sc, zbase, PrologueArgs{});
 }
 
-// fuse_done != NULL (fused call): the caller has zeroed the column maxima and the ticket, both matrices are given, and
-// the column-maxima kernel's last workgroup writes the scales itself
-int stein_x3_split(const void* theta_all, const void* score_all, int dtype, int64_t n, int64_t d,
-                   const SteinLayout& L, char* planes, hipStream_t stream, HistSync* fuse_done, bool scales_written,
-                   const PrologueArgs* prologue, int fold) {
-  u16* T3 = reinterpret_cast<u16*>(planes + L.x3_t3);
-  u16* Tt3 = reinterpret_cast<u16*>(planes + L.x3_tt3);
-  u16* Gt3 = reinterpret_cast<u16*>(planes + L.x3_gt3);
-  float* sc = reinterpret_cast<float*>(planes + L.x3_sc);
+int stein_x3_split(const StepViews& v, const void* theta_all, const void* score_all, int dtype, int64_t n, int64_t d,
+                   hipStream_t stream, const SplitFused* fused) {
+  const SteinLayout& L = v.L;
   const int dc = (int)L.x3_dc;
-  u32* cmax = reinterpret_cast<u32*>(sc + 4 * dc + 4);
   const int kind = split_kind(dtype);
-  if (fuse_done && !(theta_all && score_all)) fuse_done = nullptr;
+  HistSync* fuse_done = fused && theta_all && score_all ? fused->done : nullptr;
+  const PrologueArgs* prologue = fused ? fused->prologue : nullptr;
+  const int fold = fused ? fused->fold : 0;
   if (kind == 2) {   // column maxima of the matrices given (cmax = [score | theta]); the other half keeps its values
     const int zbase = score_all ? 0 : 1;
     const unsigned nz = (score_all ? 1u : 0u) + (theta_all ? 1u : 0u);
-    if (!fuse_done) HIP_TRY(hipMemsetAsync(cmax + (size_t)zbase * dc, 0, (size_t)nz * dc * sizeof(u32), stream));
+    if (!fuse_done) HIP_TRY(hipMemsetAsync(v.cmax + (size_t)zbase * dc, 0, (size_t)nz * dc * sizeof(u32), stream));
     int gy = (int)((n + 63) / 64);
     if (gy > 256) gy = 256;
     const bool v4 = d % 4 == 0 && (!score_all || ((uintptr_t)score_all & 15) == 0) && (!theta_all || ((uintptr_t)theta_all & 15) == 0);
@@ -1024,23 +1019,23 @@ int stein_x3_split(const void* theta_all, const void* score_all, int dtype, int6
       const int gy4 = gy > 64 ? 64 : gy;
       const dim3 grid((unsigned)((d + 255) / 256), (unsigned)gy4, nz);
       hipLaunchKernelGGL((k_colmax<float, true>), grid, dim3(1024), 0, stream, (const float*)score_all, (const float*)theta_all,
-                         (int)n, (int)d, cmax, dc, zbase, sc, PEXP_H2, fuse_done);
+                         (int)n, (int)d, v.cmax, dc, zbase, v.sc, PEXP_H2, fuse_done);
     } else {
       const dim3 grid((unsigned)((d + 63) / 64), (unsigned)gy, nz);
       hipLaunchKernelGGL((k_colmax<float, false>), grid, dim3(256), 0, stream, (const float*)score_all, (const float*)theta_all,
-                         (int)n, (int)d, cmax, dc, zbase, sc, PEXP_H2, fuse_done);
+                         (int)n, (int)d, v.cmax, dc, zbase, v.sc, PEXP_H2, fuse_done);
     }
     LAUNCH_CHECK("k_colmax");
   }
-  if ((kind != 2 && !scales_written) || (kind == 2 && !fuse_done)) {
-    hipLaunchKernelGGL(k_make_scales, dim3(1), dim3(256), 0, stream, cmax, dc, sc, kind == 2 ? PEXP_H2 : 0,
+  if (kind == 2 ? !fuse_done : !prologue) {   // (bf16 inputs: the fused call's prologue writes the neutral scales)
+    hipLaunchKernelGGL(k_make_scales, dim3(1), dim3(256), 0, stream, v.cmax, dc, v.sc, kind == 2 ? PEXP_H2 : 0,
                        kind == 2 ? 1 : 0);
     LAUNCH_CHECK("k_make_scales");
   }
-  if (kind == 1) launch_split<u16, 1>(stream, (const u16*)theta_all, (const u16*)score_all, n, d, L, T3, Tt3, Gt3, sc, prologue);
+  if (kind == 1) launch_split<u16, 1>(stream, (const u16*)theta_all, (const u16*)score_all, n, d, L, v.T3, v.Tt3, v.Gt3, v.sc, prologue);
   else if (fold)   // the score's planes are built behind the median (stein_x3_split_w); theta^T only if its product is asked for
-    launch_split<float, 2>(stream, (const float*)theta_all, (const float*)nullptr, n, d, L, T3, fold == 2 ? Tt3 : nullptr, Gt3, sc);
-  else launch_split<float, 2>(stream, (const float*)theta_all, (const float*)score_all, n, d, L, T3, Tt3, Gt3, sc);
+    launch_split<float, 2>(stream, (const float*)theta_all, (const float*)nullptr, n, d, L, v.T3, fold == 2 ? v.Tt3 : nullptr, v.Gt3, v.sc);
+  else launch_split<float, 2>(stream, (const float*)theta_all, (const float*)score_all, n, d, L, v.T3, v.Tt3, v.Gt3, v.sc);
   LAUNCH_CHECK("k_split");
   return STEIN_OK;
 }
@@ -1054,14 +1049,12 @@ int stein_x3_split(const void* theta_all, const void* score_all, int dtype, int6
 constexpr double FOLD_MIN_WORK = 4.0e9;   // n * n * d
 bool stein_fold_pays(int64_t n, int64_t d) { return d > 128 && (double)n * (double)n * (double)d >= FOLD_MIN_WORK; }
 
-int stein_x3_split_w(const float* theta_all, const float* score_all, int64_t n, int64_t d, const SteinLayout& L,
-                     char* planes, const float* h2_dev, hipStream_t stream) {
-  float* sc = reinterpret_cast<float*>(planes + L.x3_sc);
-  const int dc = (int)L.x3_dc;
+int stein_x3_split_w(const StepViews& v, const float* theta_all, const float* score_all, int64_t n, int64_t d,
+                     const float* h2_dev, hipStream_t stream) {
+  const SteinLayout& L = v.L;
   const dim3 grid((unsigned)((L.x3_dc + 63) / 64), (unsigned)((L.x3_nk + 63) / 64));
-  hipLaunchKernelGGL(k_split_w, grid, dim3(256), 0, stream, theta_all, score_all, (int)n, (int)d,
-                     reinterpret_cast<u16*>(planes + L.x3_gt3), dc, (long)L.x3_nk, sc,
-                     reinterpret_cast<const u32*>(sc + 4 * dc + 4), h2_dev);
+  hipLaunchKernelGGL(k_split_w, grid, dim3(256), 0, stream, theta_all, score_all, (int)n, (int)d, v.Gt3, (int)L.x3_dc,
+                     (long)L.x3_nk, v.sc, (const u32*)v.cmax, h2_dev);
   LAUNCH_CHECK("k_split_w");
   return STEIN_OK;
 }
@@ -1074,21 +1067,18 @@ static void launch_distance_x3(long nblk, hipStream_t stream, const u16* T3, int
                      n_local, ld, tiles_m, tiles_n, hist0, two_s, spec, spec_buf);
 }
 
-int stein_x3_distance(const char* planes, const SteinLayout& L, int dtype, const float* r_all, float* dist_out,
-                      int64_t n, int64_t d, int64_t row0, int64_t n_local, int64_t ld_dist, u64* hist0, bool symmetric,
-                      hipStream_t stream, SpecState* spec, u64* spec_buf, int panel) {
-  (void)d;
-  if (panel >= 0 && stein_dpanel_ok(L, dtype, n, row0, n_local, hist0 != nullptr && spec == nullptr, panel > 0))
-    return stein_dpanel_distance(planes, L, dtype, r_all, dist_out, n, row0, n_local, ld_dist, symmetric, stream, spec,
-                                 spec_buf, hist0);
-  const u16* T3 = reinterpret_cast<const u16*>(planes + L.x3_t3);
-  const float* two_s = reinterpret_cast<const float*>(planes + L.x3_sc) + 4 * L.x3_dc + 1;
+int stein_x3_distance(const StepViews& v, const BlockShape& b, bool symmetric, bool window, hipStream_t stream, int panel) {
+  if (panel >= 0 && stein_dpanel_ok(v, b, panel > 0)) return stein_dpanel_distance(v, b, symmetric, window, stream);
+  const SteinLayout& L = v.L;
   const int ntk = (int)(L.x3_dk / 32);
-  const int tiles_m = (int)((n_local + BM - 1) / BM), tiles_n = (int)((n + BN - 1) / BN);
-  if (row0 + (int64_t)tiles_m * BM > L.x3_rows) return stein_fail(STEIN_E_SHAPE, "row block exceeds the padded planes");
+  const int tiles_m = (int)((b.n_local + BM - 1) / BM), tiles_n = (int)((b.n + BN - 1) / BN);
+  if (b.row0 + (int64_t)tiles_m * BM > L.x3_rows) return stein_fail(STEIN_E_SHAPE, "row block exceeds the padded planes");
   const long nblk = distance_grid(symmetric, tiles_m, tiles_n);
-#define X3_DIST(SYM, NP) launch_distance_x3<SYM, NP>(nblk, stream, T3, ntk, r_all, dist_out, (int)n, (int)row0, (int)n_local, (long)ld_dist, tiles_m, tiles_n, hist0, two_s, spec, spec_buf)
-  switch (split_kind(dtype)) {
+  if (nblk > 0x7fffffffl) return stein_fail(STEIN_E_SHAPE, "too many tiles");
+  SpecState* spec = window ? v.spec : nullptr;
+  u64* spec_buf = window ? v.spec_buf : nullptr;
+#define X3_DIST(SYM, NP) launch_distance_x3<SYM, NP>(nblk, stream, v.T3, ntk, v.r, v.D, (int)b.n, (int)b.row0, (int)b.n_local, (long)L.ld_dist, tiles_m, tiles_n, v.hist, v.two_s, spec, spec_buf)
+  switch (split_kind(b.dtype)) {
     case 1: if (symmetric) X3_DIST(true, 1); else X3_DIST(false, 1); break;
     default: if (symmetric) X3_DIST(true, 2); else X3_DIST(false, 2); break;
   }
@@ -1097,15 +1087,12 @@ int stein_x3_distance(const char* planes, const SteinLayout& L, int dtype, const
   return STEIN_OK;
 }
 
-int stein_x3_contract_partial(const float* dist, int64_t ld_dist, const char* planes, const SteinLayout& L, int dtype,
-                              const float* h2_dev, float* OG, float* OT, float* RS, int64_t n, int64_t d,
-                              int64_t n_local, hipStream_t stream, bool upper) {
-  const u16* Tt3 = reinterpret_cast<const u16*>(planes + L.x3_tt3);
-  const u16* Gt3 = reinterpret_cast<const u16*>(planes + L.x3_gt3);
-  const float* sc = reinterpret_cast<const float*>(planes + L.x3_sc);
-  const long nblk = (long)L.tiles_m * L.cblocks * L.split;
-#define X3_PHI(NP) hipLaunchKernelGGL((k_phi_x3fs<NP>), dim3((unsigned)nblk), dim3(FS_THREADS), 0, stream, dist, (long)ld_dist, Gt3, Tt3, (long)(L.x3_nk / 32), h2_dev, OG, OT, RS, (int)n, (int)d, (int)n_local, (int)L.tiles_m, (int)L.cblocks, (int)L.split, (int)L.jchunk, sc, (int)L.x3_dc, upper ? 1 : 0)
-  switch (split_kind(dtype)) {
+int stein_x3_contract_partial(const StepViews& v, const BlockShape& b, const float* h2_dev, hipStream_t stream, bool upper) {
+  const SteinLayout& L = v.L;
+  const long nblk = (long)L.tiles_m * L.cblocks * v.nsplit;
+  if (nblk > 0x7fffffffl) return stein_fail(STEIN_E_SHAPE, "too many tiles");
+#define X3_PHI(NP) hipLaunchKernelGGL((k_phi_x3fs<NP>), dim3((unsigned)nblk), dim3(FS_THREADS), 0, stream, v.D, (long)L.ld_dist, v.Gt3, v.Tt3, (long)(L.x3_nk / 32), h2_dev, v.OG, v.OT, v.RS, (int)b.n, (int)b.d, (int)b.n_local, (int)L.tiles_m, (int)L.cblocks, v.nsplit, v.jchunk, v.sc, (int)L.x3_dc, upper ? 1 : 0)
+  switch (split_kind(b.dtype)) {
     case 1: X3_PHI(1); break;
     default: X3_PHI(2); break;
   }
@@ -1114,22 +1101,17 @@ int stein_x3_contract_partial(const float* dist, int64_t ld_dist, const char* pl
   return STEIN_OK;
 }
 
-// the folded contraction of the fused call: K.W in fsplit j ranges (with_theta: and K.theta in one) into the fold's
-// partial sums (SteinLayout::fold_ow / fold_ot / fold_rs)
-int stein_x3_contract_fold(const float* dist, int64_t ld_dist, char* workspace, const SteinLayout& L, const float* h2_dev,
-                           int64_t n, int64_t d, bool with_theta, hipStream_t stream) {
-  const char* planes = workspace + L.off[STEIN_WS_PLANES];
-  const u16* Tt3 = reinterpret_cast<const u16*>(planes + L.x3_tt3);
-  const u16* Wt3 = reinterpret_cast<const u16*>(planes + L.x3_gt3);
-  const float* sc = reinterpret_cast<const float*>(planes + L.x3_sc);
+// the folded contraction of the fused call: K.W in v.nsplit j ranges (with_theta: and K.theta in one) into the fold's
+// partial sums (v.OG / v.OT / v.RS of a folding layout)
+int stein_x3_contract_fold(const StepViews& v, const float* h2_dev, int64_t n, int64_t d, bool with_theta,
+                           hipStream_t stream) {
+  const SteinLayout& L = v.L;
   const long per_range = (long)L.tiles_m * ((L.cblocks + 1) / 2);
-  const long nblk = per_range * (L.fsplit + (with_theta ? 1 : 0));
+  const long nblk = per_range * (v.nsplit + (with_theta ? 1 : 0));
   if (nblk > 0x7fffffffl) return stein_fail(STEIN_E_SHAPE, "too many tiles");
-  hipLaunchKernelGGL((k_phi_x3fs<2, true>), dim3((unsigned)nblk), dim3(FS_THREADS), 0, stream, dist, (long)ld_dist, Wt3,
-                     with_theta ? Tt3 : (const u16*)nullptr, (long)(L.x3_nk / 32), h2_dev,
-                     reinterpret_cast<float*>(workspace + L.fold_ow), reinterpret_cast<float*>(workspace + L.fold_ot),
-                     reinterpret_cast<float*>(workspace + L.fold_rs), (int)n, (int)d, (int)n, (int)L.tiles_m, (int)L.cblocks,
-                     (int)L.fsplit, (int)L.fjchunk, sc, (int)L.x3_dc, 1);
+  hipLaunchKernelGGL((k_phi_x3fs<2, true>), dim3((unsigned)nblk), dim3(FS_THREADS), 0, stream, v.D, (long)L.ld_dist, v.Gt3,
+                     with_theta ? v.Tt3 : (const u16*)nullptr, (long)(L.x3_nk / 32), h2_dev, v.OG, v.OT, v.RS, (int)n, (int)d,
+                     (int)n, (int)L.tiles_m, (int)L.cblocks, v.nsplit, v.jchunk, v.sc, (int)L.x3_dc, 1);
   LAUNCH_CHECK("k_phi_x3fs");
   return STEIN_OK;
 }

@@ -11,8 +11,11 @@
 //   k_sum_partial_sets  deterministic reduction of the partials
 //   k_apply_*       clip + Adagrad/Adam + theta += step, one streaming pass (stein_apply.hip)
 // Reference formulae: see include/steinhip.h for the file:line of each stage.
-// This file holds the workspace layout, the fused single-rank call, the staged distance / contraction entry points, the
-// rank-step segments, the stage timing and the device error word.
+// This file holds the workspace layout and its views, the fused single-rank call, the staged distance / contraction entry
+// points, the rank-step segments, the stage timing and the device error word.
+// Every extern "C" entry point validates its arguments, derives ONE layout (stein_make_layout, with the flags of its family:
+// stein_host.h), builds the call's views from it (stein_step_views) and runs stage functions on them; a stage function or a
+// launcher never derives a layout, never forms an address from an offset, and checks the grid it computes.
 //
 // Everything is launched on the caller's stream; nothing here synchronises with the host.
 
@@ -340,23 +343,44 @@ int stein_make_layout(int64_t n_local, int64_t n, int64_t d, int dtype, int flag
   return STEIN_OK;
 }
 
-StepViews stein_step_views(const SteinLayout& L, void* workspace) {
+StepViews stein_step_views(const SteinLayout& L, void* workspace, void* planes_override) {
   char* ws = (char*)workspace;
-  StepViews v;
+  StepViews v{};
   v.L = L;
-  v.r = (float*)(ws + L.off[STEIN_WS_ROWNORM]);
-  v.D = (float*)(ws + L.off[STEIN_WS_DIST]);
-  v.hist = (u64*)(ws + L.off[STEIN_WS_HIST]);
-  v.sel = (SelState*)(ws + L.off[STEIN_WS_SELECT]);
-  v.spec = spec_of(v.sel);
-  v.fuse = fuse_of(v.sel);
-  v.spec_buf = (u64*)(ws + L.off[STEIN_WS_SPEC]);
-  v.table = spec_table_of(v.spec_buf);
-  v.planes = L.total > L.off[STEIN_WS_PLANES] ? ws + L.off[STEIN_WS_PLANES] : nullptr;   // (empty without STEIN_FLAG_X3)
-  v.OG = (float*)(ws + L.off[STEIN_WS_PART_G]);
-  v.OT = (float*)(ws + L.off[STEIN_WS_PART_T]);
-  v.RS = (float*)(ws + L.off[STEIN_WS_PART_RS]);
-  v.SQ = (double*)(ws + L.off[STEIN_WS_SQPART]);
+  v.nsplit = (int)L.split; v.jchunk = (int)L.jchunk; v.tsplit = (int)L.split;
+  if (ws) {
+    v.r = (float*)(ws + L.off[STEIN_WS_ROWNORM]);
+    v.D = (float*)(ws + L.off[STEIN_WS_DIST]);
+    v.hist = (u64*)(ws + L.off[STEIN_WS_HIST]);
+    v.sel = (SelState*)(ws + L.off[STEIN_WS_SELECT]);
+    v.spec = spec_of(v.sel);
+    v.fuse = fuse_of(v.sel);
+    v.spec_buf = (u64*)(ws + L.off[STEIN_WS_SPEC]);
+    v.table = spec_table_of(v.spec_buf);
+    v.OG = (float*)(ws + L.off[STEIN_WS_PART_G]);
+    v.OT = (float*)(ws + L.off[STEIN_WS_PART_T]);
+    v.RS = (float*)(ws + L.off[STEIN_WS_PART_RS]);
+    v.SQ = (double*)(ws + L.off[STEIN_WS_SQPART]);
+  }
+  if (planes_override) v.planes = (char*)planes_override;
+  else if (ws && L.total > L.off[STEIN_WS_PLANES]) v.planes = ws + L.off[STEIN_WS_PLANES];   // (empty without STEIN_FLAG_X3)
+  if (v.planes) {   // x3_* are offsets inside the planes buffer
+    v.T3 = (unsigned short*)(v.planes + L.x3_t3);
+    v.Tt3 = (unsigned short*)(v.planes + L.x3_tt3);
+    v.Gt3 = (unsigned short*)(v.planes + L.x3_gt3);
+    v.sc = (float*)(v.planes + L.x3_sc);
+    v.cmax = (u32*)(v.sc + x3_sc_cmax(L.x3_dc));
+    v.two_s = v.sc + x3_sc_two_s(L.x3_dc);
+  }
+  // The folded contraction (fused call only: every other family asks for STEIN_FLAG_NO_FOLD) keeps its partial sums in
+  // storage of its own -- fold_* are offsets from the workspace base, part of them inside its PLANES section -- and has its
+  // own plan.  OT there holds one range, written and read only when dK or the Stein discrepancy is asked for.
+  if (L.fold && ws && !planes_override) {
+    v.OG = (float*)(ws + L.fold_ow);
+    v.OT = (float*)(ws + L.fold_ot);
+    v.RS = (float*)(ws + L.fold_rs);
+    v.nsplit = (int)L.fsplit; v.jchunk = (int)L.fjchunk; v.tsplit = 1;
+  }
   return v;
 }
 
@@ -396,11 +420,11 @@ extern "C" int stein_x3_prepare(const void* theta_all, const void* score_all, in
                                 void* x3_planes, size_t planes_bytes, void* stream) {
   if ((!theta_all && !score_all) || !x3_planes) return fail(STEIN_E_BADARG, "NULL pointer");
   SteinLayout L;
-  int rc = stein_make_layout(n, n, d, dtype, STEIN_FLAG_X3 | STEIN_FLAG_NO_FOLD, &L);
+  int rc = stein_make_layout(n, n, d, dtype, stein_staged_flags(true), &L);
   if (rc) return rc;
   if (planes_bytes < L.total - L.off[STEIN_WS_PLANES])
     return fail(STEIN_E_WORKSPACE, "planes buffer %zu < %zu bytes", planes_bytes, L.total - L.off[STEIN_WS_PLANES]);
-  return stein_x3_split(theta_all, score_all, dtype, n, d, L, (char*)x3_planes, (hipStream_t)stream);
+  return stein_x3_split(stein_step_views(L, nullptr, x3_planes), theta_all, score_all, dtype, n, d, (hipStream_t)stream, nullptr);
 }
 
 extern "C" int stein_rownorms(const void* theta_all, int64_t n, int64_t d, int dtype, float* r_out, void* stream) {
@@ -418,38 +442,95 @@ extern "C" int stein_rownorms(const void* theta_all, int64_t n, int64_t d, int d
   return STEIN_OK;
 }
 
-// spec != NULL (single-rank fused call only, needs hist_level0): also feed the speculative median window
-static int distance_block_impl(const void* theta_all, const float* r_all, int64_t n, int64_t d, int64_t row0,
-                               int64_t n_local, int dtype, float* dist_out, int64_t ld_dist, void* hist_level0,
-                               const void* x3_planes, int flags, void* stream, SpecState* spec, u64* spec_buf) {
+// The dtype and row-block checks of the entry points that work on a row block.  bf16_ok: the call has what bf16 inputs run
+// on (the split operand planes / STEIN_FLAG_X3), or cannot tell (the finish pass only reads the rows).
+static int check_block(const char* stage, const BlockShape& b, bool bf16_ok) {
+  if (b.dtype != STEIN_F32 && b.dtype != STEIN_BF16) return fail(STEIN_E_UNSUPPORTED, "%s: dtype %d", stage, b.dtype);
+  if (b.dtype == STEIN_BF16 && !bf16_ok)
+    return fail(STEIN_E_UNSUPPORTED, "%s: bf16 inputs need the operand planes (STEIN_FLAG_X3)", stage);
+  if (b.row0 < 0 || b.n_local < 1 || b.row0 + b.n_local > b.n) return fail(STEIN_E_SHAPE, "bad row block");
+  return STEIN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// stage functions: one stage of a step on the call's views.  None derives a layout or validates.
+// ------------------------------------------------------------------------------------------------
+// v.r -> v.D (leading dimension v.L.ld_dist) and the level-0 counts in v.hist; stage_flags: STEIN_STAGE_*.
+// window (needs v.hist): also feed the speculative median window
+static int distance_stage(const StepViews& v, const BlockShape& b, const void* theta_all, int stage_flags, bool window,
+                          hipStream_t s) {
+  const bool sym = (stage_flags & STEIN_STAGE_SYMMETRIC) != 0;
+  if (v.planes)
+    return stein_x3_distance(v, b, sym, window, s, (stage_flags & STEIN_STAGE_TILES) ? -1 : ((stage_flags & STEIN_STAGE_PANEL) ? 1 : 0));
+  return stein_fp32_distance(v, b, (const float*)theta_all, sym, window, s);
+}
+
+// K.[G | theta] of the block in v.D into v.OG / v.OT / v.RS
+static int contract_stage(const StepViews& v, const BlockShape& b, const void* theta_all, const void* score_all,
+                          const float* h2_dev, bool upper, hipStream_t s) {
+  return v.planes ? stein_x3_contract_partial(v, b, h2_dev, s, upper)
+                  : stein_fp32_contract_partial(v, b, (const float*)theta_all, (const float*)score_all, h2_dev, s);
+}
+
+// phi and |phi|^2 from the partial sums.  ksd (STEIN_FLAG_KSD): also the statistic from the score rows; sqnorm_out is then
+// double[3].  done: the fused call's completion counters (its prologue zeroed them; the last workgroup sums the partials);
+// NULL: k_sum_partial_sets does.
+static int finish_stage(const StepViews& v, const BlockShape& b, const void* theta_all, const void* score_all,
+                        const float* h2_dev, float* phi_local, double* sqnorm_out, float* dK_out, bool ksd, HistSync* done,
+                        hipStream_t s) {
+  const SteinLayout& L = v.L;
+  auto al16 = [](const void* p) { return ((uintptr_t)p & 15u) == 0; };
+  const size_t tsz = b.dtype == STEIN_BF16 ? 2 : 4;
+  auto rows_aligned = [&](const void* p) { return (((uintptr_t)p + (size_t)b.row0 * b.d * tsz) & (4 * tsz - 1)) == 0; };
+  const int vec = (b.d % 4 == 0) && al16(v.OG) && al16(v.OT) && al16(phi_local) && al16(dK_out) && rows_aligned(theta_all) &&
+                  (!ksd || rows_aligned(score_all));
+  auto launch = [&](auto tin, auto ksd_tag, auto fold_tag) {
+    using TIN = decltype(tin);
+    hipLaunchKernelGGL((k_phi_finish<TIN, decltype(ksd_tag)::value, decltype(fold_tag)::value>), dim3((unsigned)L.sq_blocks),
+                       dim3(256), 0, s, v.OG, v.OT, v.RS, (const TIN*)theta_all, h2_dev, phi_local, dK_out, v.SQ, (int)b.n, (int)b.d,
+                       (int)b.row0, (int)b.n_local, v.nsplit, v.tsplit, vec, done, sqnorm_out, (const TIN*)score_all);
+  };
+  auto launch_ksd = [&](auto tin, auto fold_tag) {
+    if (ksd) launch(tin, std::true_type(), fold_tag);
+    else launch(tin, std::false_type(), fold_tag);
+  };
+  if (L.fold) launch_ksd(0.f, std::true_type());   // fp32 inputs by construction
+  else if (b.dtype == STEIN_BF16) launch_ksd((unsigned short)0, std::false_type());
+  else launch_ksd(0.f, std::false_type());
+  LAUNCH_CHECK("k_phi_finish");
+  return done ? STEIN_OK : sum_partials(v.SQ, (int)L.sq_blocks, ksd, sqnorm_out, s);
+}
+
+// ------------------------------------------------------------------------------------------------
+// staged entry points: the caller owns the buffers (and the planes, a separate allocation), so their views are the layout's
+// plan and planes with the caller's buffers in place of the workspace's sections
+// ------------------------------------------------------------------------------------------------
+// spec != NULL (needs hist_level0): also feed the speculative median window
+static int distance_block(const void* theta_all, const float* r_all, const BlockShape& b, float* dist_out, int64_t ld_dist,
+                          void* hist_level0, const void* x3_planes, int flags, void* stream, SpecState* spec, u64* spec_buf) {
   if ((!theta_all && !x3_planes) || !r_all || !dist_out) return fail(STEIN_E_BADARG, "NULL pointer");
-  if (n < 1 || d < 1 || n_local < 1 || row0 < 0 || row0 + n_local > n) return fail(STEIN_E_SHAPE, "bad row block");
-  if (ld_dist < n || (ld_dist & 63)) return fail(STEIN_E_SHAPE, "ld_dist must be >= n and a multiple of 64");
-  if (dtype != STEIN_F32 && !(dtype == STEIN_BF16 && x3_planes))
-    return fail(STEIN_E_UNSUPPORTED, "distance: dtype %d (bf16 inputs need the operand planes)", dtype);
-  const bool sym = (flags & STEIN_STAGE_SYMMETRIC) != 0;
-  if (sym && (row0 != 0 || n_local != n || (ld_dist & 63)))
+  if (b.n < 1 || b.d < 1) return fail(STEIN_E_SHAPE, "bad row block");
+  int rc = check_block("distance", b, x3_planes != nullptr);
+  if (rc) return rc;
+  if (ld_dist < b.n || (ld_dist & 63)) return fail(STEIN_E_SHAPE, "ld_dist must be >= n and a multiple of 64");
+  if ((flags & STEIN_STAGE_SYMMETRIC) && (b.row0 != 0 || b.n_local != b.n))
     return fail(STEIN_E_BADARG, "STEIN_STAGE_SYMMETRIC needs the whole matrix (row0 = 0, n_local = n) and ld_dist %% 64 == 0");
-  const int tiles_m = (int)((n_local + BM - 1) / BM), tiles_n = (int)((n + BN - 1) / BN);
-  const long nblk = distance_grid(sym, tiles_m, tiles_n);
-  if (nblk > 0x7fffffffl) return fail(STEIN_E_SHAPE, "too many tiles");
-  hipStream_t s = (hipStream_t)stream;
-  u64* h0 = (u64*)hist_level0;
-  if (x3_planes) {
+  StepViews v{};
+  if (x3_planes) {   // (the fp32 kernels need nothing of a layout)
     SteinLayout L;
-    int rc = stein_make_layout(n_local, n, d, dtype, STEIN_FLAG_X3 | STEIN_FLAG_NO_FOLD, &L);
-    if (rc) return rc;
-    return stein_x3_distance((const char*)x3_planes, L, dtype, r_all, dist_out, n, d, row0, n_local, ld_dist, h0, sym, s,
-                             spec, spec_buf, (flags & STEIN_STAGE_TILES) ? -1 : ((flags & STEIN_STAGE_PANEL) ? 1 : 0));
+    if ((rc = stein_make_layout(b.n_local, b.n, b.d, b.dtype, stein_staged_flags(true), &L))) return rc;
+    v = stein_step_views(L, nullptr, const_cast<void*>(x3_planes));
   }
-  return stein_fp32_distance((const float*)theta_all, r_all, dist_out, n, d, row0, n_local, ld_dist, h0, sym, s, spec, spec_buf);
+  v.r = const_cast<float*>(r_all); v.D = dist_out; v.L.ld_dist = ld_dist; v.hist = (u64*)hist_level0;
+  v.spec = spec; v.spec_buf = spec_buf;
+  return distance_stage(v, b, theta_all, flags, spec != nullptr, (hipStream_t)stream);
 }
 
 extern "C" int stein_distance_block(const void* theta_all, const float* r_all, int64_t n, int64_t d, int64_t row0,
                                     int64_t n_local, int dtype, float* dist_out, int64_t ld_dist, void* hist_level0,
                                     const void* x3_planes, int flags, void* stream) {
-  return distance_block_impl(theta_all, r_all, n, d, row0, n_local, dtype, dist_out, ld_dist, hist_level0, x3_planes,
-                             flags, stream, nullptr, nullptr);
+  return distance_block(theta_all, r_all, BlockShape{n, d, row0, n_local, dtype}, dist_out, ld_dist, hist_level0, x3_planes,
+                        flags, stream, nullptr, nullptr);
 }
 
 extern "C" int stein_distance_block_spec(const void* theta_all, const float* r_all, int64_t n, int64_t d, int64_t row0,
@@ -457,8 +538,8 @@ extern "C" int stein_distance_block_spec(const void* theta_all, const float* r_a
                                          const void* x3_planes, int flags, void* select_state, void* spec_buf,
                                          void* stream) {
   if (!hist_level0 || !select_state || !spec_buf) return fail(STEIN_E_BADARG, "NULL pointer");
-  return distance_block_impl(theta_all, r_all, n, d, row0, n_local, dtype, dist_out, ld_dist, hist_level0, x3_planes,
-                             flags, stream, spec_of(select_state), (u64*)spec_buf);
+  return distance_block(theta_all, r_all, BlockShape{n, d, row0, n_local, dtype}, dist_out, ld_dist, hist_level0, x3_planes,
+                        flags, stream, spec_of(select_state), (u64*)spec_buf);
 }
 
 extern "C" int stein_kernel_matrix(const float* dist, int64_t ld_dist, int64_t n_local, int64_t n,
@@ -474,78 +555,42 @@ extern "C" int stein_kernel_matrix(const float* dist, int64_t ld_dist, int64_t n
   return STEIN_OK;
 }
 
+// What stein_contract_partial checks, and its views: the workspace need only reach its PLANES section, the planes are the
+// caller's buffer, and dist takes the place of the DIST section.
+static int contract_partial_views(const float* dist, int64_t ld_dist, const void* theta_all, const void* score_all,
+                                  const BlockShape& b, const float* h2_dev, const void* x3_planes, void* workspace,
+                                  size_t ws_bytes, int dist_flags, StepViews* v) {
+  if (dist_flags & ~(STEIN_STAGE_SYMMETRIC | STEIN_STAGE_UPPER)) return fail(STEIN_E_BADARG, "unknown distance flags 0x%x", dist_flags);
+  if ((dist_flags & STEIN_STAGE_UPPER) && (!x3_planes || b.row0 != 0 || b.n_local != b.n))
+    return fail(STEIN_E_BADARG, "STEIN_STAGE_UPPER: only the split path's symmetric distance pass stores the upper triangle alone");
+  if (!dist || (!x3_planes && (!theta_all || !score_all)) || !h2_dev || !workspace)
+    return fail(STEIN_E_BADARG, "NULL pointer");
+  int rc = check_block("contract", b, x3_planes != nullptr);
+  if (rc) return rc;
+  SteinLayout L;
+  if ((rc = stein_make_layout(b.n_local, b.n, b.d, b.dtype, stein_staged_flags(x3_planes != nullptr), &L))) return rc;
+  if (ws_bytes < L.off[STEIN_WS_PLANES]) return fail(STEIN_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L.off[STEIN_WS_PLANES]);
+  if (ld_dist != L.ld_dist) return fail(STEIN_E_SHAPE, "ld_dist %lld != %lld", (long long)ld_dist, (long long)L.ld_dist);
+  *v = stein_step_views(L, workspace, const_cast<void*>(x3_planes));
+  v->D = const_cast<float*>(dist);
+  return STEIN_OK;
+}
+
 extern "C" int stein_contract_partial(const float* dist, int64_t ld_dist, const void* theta_all,
                                       const void* score_all, int64_t n, int64_t d, int64_t row0, int64_t n_local,
                                       int dtype, const float* h2_dev, const void* x3_planes, void* workspace,
                                       size_t ws_bytes, int dist_flags, void* stream) {
-  if (dist_flags & ~(STEIN_STAGE_SYMMETRIC | STEIN_STAGE_UPPER)) return fail(STEIN_E_BADARG, "unknown distance flags 0x%x", dist_flags);
-  const bool upper = (dist_flags & STEIN_STAGE_UPPER) != 0;
-  if (upper && (!x3_planes || row0 != 0 || n_local != n))
-    return fail(STEIN_E_BADARG, "STEIN_STAGE_UPPER: only the split path's symmetric distance pass stores the upper triangle alone");
-  if (!dist || (!x3_planes && (!theta_all || !score_all)) || !h2_dev || !workspace)
-    return fail(STEIN_E_BADARG, "NULL pointer");
-  if (dtype != STEIN_F32 && !(dtype == STEIN_BF16 && x3_planes))
-    return fail(STEIN_E_UNSUPPORTED, "contract: dtype %d (bf16 inputs need the operand planes)", dtype);
-  if (row0 < 0 || row0 + n_local > n) return fail(STEIN_E_SHAPE, "bad row block");
-  SteinLayout L;
-  int rc = stein_make_layout(n_local, n, d, dtype, x3_planes ? STEIN_FLAG_X3 | STEIN_FLAG_NO_FOLD : 0, &L);
+  const BlockShape b{n, d, row0, n_local, dtype};
+  StepViews v;
+  int rc = contract_partial_views(dist, ld_dist, theta_all, score_all, b, h2_dev, x3_planes, workspace, ws_bytes, dist_flags, &v);
   if (rc) return rc;
-  if (ws_bytes < L.off[STEIN_WS_PLANES]) return fail(STEIN_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L.off[STEIN_WS_PLANES]);
-  if (ld_dist != L.ld_dist) return fail(STEIN_E_SHAPE, "ld_dist %lld != %lld", (long long)ld_dist, (long long)L.ld_dist);
-  const StepViews v = stein_step_views(L, workspace);
-  hipStream_t s = (hipStream_t)stream;
-  const long nblk = (long)L.tiles_m * 2 * L.cblocks * L.split;
-  if (nblk > 0x7fffffffl) return fail(STEIN_E_SHAPE, "too many tiles");
-  return x3_planes ? stein_x3_contract_partial(dist, ld_dist, (const char*)x3_planes, L, dtype, h2_dev, v.OG, v.OT, v.RS, n, d,
-                                               n_local, s, upper)
-                   : stein_fp32_contract_partial(dist, ld_dist, (const float*)theta_all, (const float*)score_all, L, h2_dev,
-                                                 v.OG, v.OT, v.RS, n, d, n_local, s);
+  return contract_stage(v, b, theta_all, score_all, h2_dev, (dist_flags & STEIN_STAGE_UPPER) != 0, (hipStream_t)stream);
 }
 
-// score_all: read only with STEIN_FLAG_KSD in flags (the statistic's score rows; sqnorm_out is then double[3])
-static int contract_finish_impl(const void* theta_all, const void* score_all, int64_t n, int64_t d, int64_t row0,
-                                int64_t n_local, int dtype, const float* h2_dev, float* phi_local, double* sqnorm_out,
-                                float* dK_out, void* workspace, size_t ws_bytes, int flags, void* stream, HistSync* fuse_done) {
-  const bool ksd = (flags & STEIN_FLAG_KSD) != 0;
-  if (!theta_all || !h2_dev || !phi_local || !sqnorm_out || !workspace || (ksd && !score_all)) return fail(STEIN_E_BADARG, "NULL pointer");
-  if (dtype != STEIN_F32 && dtype != STEIN_BF16) return fail(STEIN_E_UNSUPPORTED, "contract: dtype %d", dtype);
-  if (row0 < 0 || row0 + n_local > n) return fail(STEIN_E_SHAPE, "bad row block");
-  SteinLayout L;
-  int rc = stein_make_layout(n_local, n, d, dtype, flags, &L);
-  if (rc) return rc;
-  if (ws_bytes < L.off[STEIN_WS_PLANES]) return fail(STEIN_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L.off[STEIN_WS_PLANES]);
-  StepViews v = stein_step_views(L, workspace);
-  if (L.fold) {   // (fused call only: the staged entry points ask for STEIN_FLAG_NO_FOLD) the folded contraction's partials
-    if (ws_bytes < L.total) return fail(STEIN_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L.total);
-    v.OG = (float*)((char*)workspace + L.fold_ow);
-    v.OT = (float*)((char*)workspace + L.fold_ot);
-    v.RS = (float*)((char*)workspace + L.fold_rs);
-  }
-  const int nsplit = (int)(L.fold ? L.fsplit : L.split);
-  hipStream_t s = (hipStream_t)stream;
-  auto al16 = [](const void* p) { return ((uintptr_t)p & 15u) == 0; };
-  const size_t tsz = dtype == STEIN_BF16 ? 2 : 4;
-  auto rows_aligned = [&](const void* p) { return (((uintptr_t)p + (size_t)row0 * d * tsz) & (4 * tsz - 1)) == 0; };
-  const int vec = (d % 4 == 0) && al16(v.OG) && al16(v.OT) && al16(phi_local) && al16(dK_out) && rows_aligned(theta_all) &&
-                  (!ksd || rows_aligned(score_all));
-  auto launch = [&](auto tin, auto ksd_tag, auto fold_tag) {
-    using TIN = decltype(tin);
-    hipLaunchKernelGGL((k_phi_finish<TIN, decltype(ksd_tag)::value, decltype(fold_tag)::value>), dim3((unsigned)L.sq_blocks),
-                       dim3(256), 0, s, v.OG, v.OT, v.RS, (const TIN*)theta_all, h2_dev, phi_local, dK_out, v.SQ, (int)n, (int)d,
-                       (int)row0, (int)n_local, nsplit, L.fold ? 1 : nsplit, vec, fuse_done, sqnorm_out, (const TIN*)score_all);
-  };
-  if (L.fold) {   // fp32 inputs by construction
-    if (ksd) launch(0.f, std::true_type(), std::true_type());
-    else launch(0.f, std::false_type(), std::true_type());
-  } else if (dtype == STEIN_BF16) {
-    if (ksd) launch((unsigned short)0, std::true_type(), std::false_type());
-    else launch((unsigned short)0, std::false_type(), std::false_type());
-  } else {
-    if (ksd) launch(0.f, std::true_type(), std::false_type());
-    else launch(0.f, std::false_type(), std::false_type());
-  }
-  LAUNCH_CHECK("k_phi_finish");
-  return fuse_done ? STEIN_OK : sum_partials(v.SQ, (int)L.sq_blocks, ksd, sqnorm_out, s);
+static int check_finish(const void* theta_all, const BlockShape& b, const float* h2_dev, float* phi_local, double* sqnorm_out,
+                        void* workspace) {
+  if (!theta_all || !h2_dev || !phi_local || !sqnorm_out || !workspace) return fail(STEIN_E_BADARG, "NULL pointer");
+  return check_block("contract", b, true);
 }
 
 extern "C" int stein_contract_finish(const void* theta_all, int64_t n, int64_t d, int64_t row0, int64_t n_local,
@@ -554,9 +599,16 @@ extern "C" int stein_contract_finish(const void* theta_all, int64_t n, int64_t d
   if (flags & STEIN_FLAG_KSD)
     return fail(STEIN_E_BADARG, "STEIN_FLAG_KSD: stein_contract_finish has no score operand; the statistic comes from "
                                 "stein_svgd_phi, stein_rank_finish or stein_rank_step");
-  // (a staged call finishes what stein_contract_partial left: K.[G | theta], never the folded form)
-  return contract_finish_impl(theta_all, nullptr, n, d, row0, n_local, dtype, h2_dev, phi_local, sqnorm_out, dK_out,
-                              workspace, ws_bytes, (flags & ~STEIN_FLAG_FOLD) | STEIN_FLAG_NO_FOLD, stream, nullptr);
+  const BlockShape b{n, d, row0, n_local, dtype};
+  int rc = check_finish(theta_all, b, h2_dev, phi_local, sqnorm_out, workspace);
+  if (rc) return rc;
+  // (a staged call finishes what stein_contract_partial left: K.[G | theta], never the folded form.  The workspace need
+  // only reach its PLANES section, and nothing here touches the planes.)
+  SteinLayout L;
+  if ((rc = stein_make_layout(n_local, n, d, dtype, (flags & ~STEIN_FLAG_FOLD) | STEIN_FLAG_NO_FOLD, &L))) return rc;
+  if (ws_bytes < L.off[STEIN_WS_PLANES]) return fail(STEIN_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L.off[STEIN_WS_PLANES]);
+  return finish_stage(stein_step_views(L, workspace), b, theta_all, nullptr, h2_dev, phi_local, sqnorm_out, dK_out, false,
+                      nullptr, (hipStream_t)stream);
 }
 
 extern "C" int stein_kernel_contract(const float* dist, int64_t ld_dist, const void* theta_all, const void* score_all,
@@ -567,18 +619,22 @@ extern "C" int stein_kernel_contract(const float* dist, int64_t ld_dist, const v
   if (dist_flags & STEIN_FLAG_KSD)
     return fail(STEIN_E_BADARG, "STEIN_FLAG_KSD: stein_kernel_contract takes distance flags only; the statistic comes from "
                                 "stein_svgd_phi, stein_rank_finish or stein_rank_step");
-  int rc = stein_contract_partial(dist, ld_dist, theta_all, score_all, n, d, row0, n_local, dtype, h2_dev, x3_planes,
-                                  workspace, ws_bytes, dist_flags, stream);
+  const BlockShape b{n, d, row0, n_local, dtype};
+  StepViews v;
+  int rc = contract_partial_views(dist, ld_dist, theta_all, score_all, b, h2_dev, x3_planes, workspace, ws_bytes, dist_flags, &v);
   if (rc) return rc;
-  return stein_contract_finish(theta_all, n, d, row0, n_local, dtype, h2_dev, phi_local, sqnorm_out, dK_out, workspace,
-                               ws_bytes, x3_planes ? STEIN_FLAG_X3 : 0, stream);
+  if ((rc = check_finish(theta_all, b, h2_dev, phi_local, sqnorm_out, workspace))) return rc;
+  const hipStream_t s = (hipStream_t)stream;
+  if ((rc = contract_stage(v, b, theta_all, score_all, h2_dev, (dist_flags & STEIN_STAGE_UPPER) != 0, s))) return rc;
+  return finish_stage(v, b, theta_all, nullptr, h2_dev, phi_local, sqnorm_out, dK_out, false, nullptr, s);
 }
 
 // ------------------------------------------------------------------------------------------------
-// rank-step segments: what one rank of a row-sharded run does between two collectives, as ONE call each (the staged calls
+// rank-step segments: what one rank of a row-sharded run does between two collectives, as ONE call each (the stages
 // above, chained on the stream).  The host layer issues: all-gather(theta), all-gather(score) | stein_rank_begin |
 // all-reduce(window table or level-0 histogram) | stein_rank_pick or stein_rank_radix x3 (an all-reduce before each) |
-// stein_rank_finish | all-reduce(|phi|^2).
+// stein_rank_finish | all-reduce(|phi|^2).  Each public segment validates and derives its views (stein_rank_views) and
+// calls its body (stein_rank_*_on); stein_rank_step (stein_comm.hip) does that once for the whole step.
 // ------------------------------------------------------------------------------------------------
 static thread_local std::vector<hipEvent_t> g_tevents;   // (STEIN_T_NSTAGES + 1) events per reserved call
 static thread_local int g_tcalls_reserved = 0, g_tcalls_used = 0;
@@ -603,39 +659,45 @@ struct StageTimer {
   }
 };
 
-static int rank_views(int64_t n, int64_t d, int64_t row0, int64_t n_local, int dtype, void* workspace, size_t ws_bytes,
-                      int flags, StepViews* v) {
+int stein_rank_views(const BlockShape& b, void* workspace, size_t ws_bytes, int flags, StepViews* v) {
   if (!workspace) return fail(STEIN_E_BADARG, "NULL pointer");
-  if (row0 < 0 || n_local < 1 || row0 + n_local > n) return fail(STEIN_E_SHAPE, "bad row block");
+  int rc = check_block("rank step", b, (flags & STEIN_FLAG_X3) != 0);
+  if (rc) return rc;
   if (flags & ~(STEIN_FLAG_X3 | STEIN_FLAG_TILED | STEIN_FLAG_RANK_WINDOW | STEIN_FLAG_TIMING | STEIN_FLAG_KSD)) return fail(STEIN_E_BADARG, "unknown flags 0x%x", flags);
   SteinLayout L;
-  // (the rank segments keep K.[G | theta]: the score's planes are built while its all-gather overlaps the distance pass,
-  // before h2 exists.  The workspace may have been sized with the fold area -- it only adds bytes at the end.)
-  int rc = stein_make_layout(n_local, n, d, dtype, (flags & (STEIN_FLAG_X3 | STEIN_FLAG_TILED | STEIN_FLAG_KSD)) | STEIN_FLAG_TILED | STEIN_FLAG_NO_FOLD, &L);
-  if (rc) return rc;
-  if (dtype == STEIN_BF16 && !(flags & STEIN_FLAG_X3)) return fail(STEIN_E_UNSUPPORTED, "bf16 inputs need STEIN_FLAG_X3");
+  if ((rc = stein_make_layout(b.n_local, b.n, b.d, b.dtype, stein_rank_flags(flags), &L))) return rc;
   if (ws_bytes < L.total) return fail(STEIN_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L.total);
   *v = stein_step_views(L, workspace);
   return STEIN_OK;
 }
 
+int stein_rank_begin_on(const StepViews& v, const BlockShape& b, const void* theta_all, bool window, hipStream_t s) {
+  int rc;
+  if ((rc = stein_rownorms(theta_all, b.n, b.d, b.dtype, v.r, s))) return rc;
+  if (v.planes && (rc = stein_x3_split(v, theta_all, nullptr, b.dtype, b.n, b.d, s, nullptr))) return rc;
+  if (window) rc = stein_spec_begin(v.hist, v.sel, v.spec_buf, b.n * b.n, s);
+  else rc = stein_median_begin(v.hist, v.sel, b.n * b.n, s);
+  if (rc) return rc;
+  if ((rc = distance_stage(v, b, theta_all, 0, window, s))) return rc;
+  if (window) rc = stein_spec_tally(v.sel, v.spec_buf, s);
+  return rc;
+}
+
 extern "C" int stein_rank_begin(const void* theta_all, int64_t n, int64_t d, int64_t row0, int64_t n_local, int dtype,
                                 void* workspace, size_t ws_bytes, int flags, void* stream) {
   if (!theta_all) return fail(STEIN_E_BADARG, "NULL pointer");
+  const BlockShape b{n, d, row0, n_local, dtype};
   StepViews v;
-  int rc = rank_views(n, d, row0, n_local, dtype, workspace, ws_bytes, flags, &v);
+  int rc = stein_rank_views(b, workspace, ws_bytes, flags, &v);
+  return rc ? rc : stein_rank_begin_on(v, b, theta_all, (flags & STEIN_FLAG_RANK_WINDOW) != 0, (hipStream_t)stream);
+}
+
+int stein_rank_pick_on(const StepViews& v, int64_t n, float* h2_out, float* median_out, void* flags_host, hipStream_t s) {
+  int rc = stein_spec_pick(v.sel, v.spec_buf, n, h2_out, median_out, s);
   if (rc) return rc;
-  const bool window = (flags & STEIN_FLAG_RANK_WINDOW) != 0;
-  if ((rc = stein_rownorms(theta_all, n, d, dtype, v.r, stream))) return rc;
-  if (v.planes && (rc = stein_x3_split(theta_all, nullptr, dtype, n, d, v.L, v.planes, (hipStream_t)stream))) return rc;
-  if (window) rc = stein_spec_begin(v.hist, v.sel, v.spec_buf, n * n, stream);
-  else rc = stein_median_begin(v.hist, v.sel, n * n, stream);
-  if (rc) return rc;
-  if ((rc = distance_block_impl(theta_all, v.r, n, d, row0, n_local, dtype, v.D, v.L.ld_dist, v.hist, v.planes, 0, stream,
-                                window ? v.spec : nullptr, window ? v.spec_buf : nullptr)))
-    return rc;
-  if (window) rc = stein_spec_tally(v.sel, v.spec_buf, stream);
-  return rc;
+  // `hit` (SpecState + 28) .. `skip_l0` (+ 52): 28 bytes, to page-locked host memory the caller polls behind an event
+  HIP_TRY(hipMemcpyAsync(flags_host, &v.spec->hit, 28, hipMemcpyDeviceToHost, s));
+  return STEIN_OK;
 }
 
 extern "C" int stein_rank_pick(int64_t n, int64_t d, int64_t row0, int64_t n_local, int dtype, void* workspace,
@@ -643,52 +705,57 @@ extern "C" int stein_rank_pick(int64_t n, int64_t d, int64_t row0, int64_t n_loc
                                void* stream) {
   if (!h2_out || !flags_host) return fail(STEIN_E_BADARG, "NULL pointer");
   StepViews v;
-  int rc = rank_views(n, d, row0, n_local, dtype, workspace, ws_bytes, flags, &v);
+  int rc = stein_rank_views(BlockShape{n, d, row0, n_local, dtype}, workspace, ws_bytes, flags, &v);
+  return rc ? rc : stein_rank_pick_on(v, n, h2_out, median_out, flags_host, (hipStream_t)stream);
+}
+
+// need_pass: first take this level's histogram of the local block (level 0 after a window miss that skipped it);
+// then (the caller has summed hist[level] over the ranks unless need_pass) ... see include/steinhip.h
+int stein_rank_radix_on(const StepViews& v, const BlockShape& b, int level, int need_pass, float* h2_out, float* median_out,
+                        hipStream_t s) {
+  if (level < 0 || level >= STEIN_HIST_LEVELS) return fail(STEIN_E_BADARG, "level %d", level);
+  if (need_pass) return stein_median_hist_pass(v.D, v.L.ld_dist, b.n_local, b.n, level, v.sel, v.hist, 0, s);
+  int rc = stein_median_resolve(v.hist, level, b.n, v.sel, h2_out, median_out, s);
   if (rc) return rc;
-  if ((rc = stein_spec_pick(v.sel, v.spec_buf, n, h2_out, median_out, stream))) return rc;
-  // `hit` (SpecState + 28) .. `skip_l0` (+ 52): 28 bytes, to page-locked host memory the caller polls behind an event
-  HIP_TRY(hipMemcpyAsync(flags_host, &v.spec->hit, 28, hipMemcpyDeviceToHost, (hipStream_t)stream));
-  return STEIN_OK;
+  if (level + 1 < STEIN_HIST_LEVELS)
+    rc = stein_median_hist_pass(v.D, v.L.ld_dist, b.n_local, b.n, level + 1, v.sel, v.hist, 0, s);
+  return rc;
 }
 
 extern "C" int stein_rank_radix(int level, int need_pass, int64_t n, int64_t d, int64_t row0, int64_t n_local, int dtype,
                                 void* workspace, size_t ws_bytes, int flags, float* h2_out, float* median_out,
                                 void* stream) {
-  // need_pass: first take this level's histogram of the local block (level 0 after a window miss that skipped it);
-  // then (the caller has summed hist[level] over the ranks unless need_pass) ... see include/steinhip.h
+  const BlockShape b{n, d, row0, n_local, dtype};
   StepViews v;
-  int rc = rank_views(n, d, row0, n_local, dtype, workspace, ws_bytes, flags, &v);
-  if (rc) return rc;
-  if (level < 0 || level >= STEIN_HIST_LEVELS) return fail(STEIN_E_BADARG, "level %d", level);
-  if (need_pass) return stein_median_hist_pass(v.D, v.L.ld_dist, n_local, n, level, v.sel, v.hist, 0, stream);
-  if ((rc = stein_median_resolve(v.hist, level, n, v.sel, h2_out, median_out, stream))) return rc;
-  if (level + 1 < STEIN_HIST_LEVELS)
-    rc = stein_median_hist_pass(v.D, v.L.ld_dist, n_local, n, level + 1, v.sel, v.hist, 0, stream);
-  return rc;
+  int rc = stein_rank_views(b, workspace, ws_bytes, flags, &v);
+  return rc ? rc : stein_rank_radix_on(v, b, level, need_pass, h2_out, median_out, (hipStream_t)stream);
+}
+
+int stein_rank_finish_on(const StepViews& v, const BlockShape& b, const void* theta_all, const void* score_all,
+                         const float* h2_dev, float* phi_local, double* sqnorm_out, float* dK_out, int flags,
+                         hipStream_t s) {
+  int rc;
+  if ((flags & STEIN_FLAG_RANK_WINDOW) && (rc = stein_spec_update(v.sel, s))) return rc;
+  // STEIN_FLAG_TIMING: the contraction and the finish pass are bracketed by HIP events on the stream (the earlier
+  // stages of the slot read as zero length); read them back with stein_timing_read
+  const StageTimer clk(flags);
+  for (int k = 0; k <= STEIN_T_CONTRACT; ++k)
+    if ((rc = clk.mark(k, s))) return rc;
+  if ((rc = contract_stage(v, b, theta_all, score_all, h2_dev, false, s))) return rc;
+  if ((rc = clk.mark(STEIN_T_FINISH, s))) return rc;
+  rc = finish_stage(v, b, theta_all, score_all, h2_dev, phi_local, sqnorm_out, dK_out, (flags & STEIN_FLAG_KSD) != 0, nullptr, s);
+  return rc ? rc : clk.mark(STEIN_T_NSTAGES, s);
 }
 
 extern "C" int stein_rank_finish(const void* theta_all, const void* score_all, int64_t n, int64_t d, int64_t row0,
                                  int64_t n_local, int dtype, const float* h2_dev, float* phi_local, double* sqnorm_out,
                                  float* dK_out, void* workspace, size_t ws_bytes, int flags, void* stream) {
   if (!theta_all || !score_all || !h2_dev || !phi_local || !sqnorm_out) return fail(STEIN_E_BADARG, "NULL pointer");
+  const BlockShape b{n, d, row0, n_local, dtype};
   StepViews v;
-  int rc = rank_views(n, d, row0, n_local, dtype, workspace, ws_bytes, flags, &v);
-  if (rc) return rc;
-  if ((flags & STEIN_FLAG_RANK_WINDOW) && (rc = stein_spec_update(v.sel, stream))) return rc;
-  // STEIN_FLAG_TIMING: the contraction and the finish pass are bracketed by HIP events on the stream (the earlier
-  // stages of the slot read as zero length); read them back with stein_timing_read
-  const hipStream_t s = (hipStream_t)stream;
-  const StageTimer clk(flags);
-  for (int k = 0; k <= STEIN_T_CONTRACT; ++k)
-    if ((rc = clk.mark(k, s))) return rc;
-  if ((rc = stein_contract_partial(v.D, v.L.ld_dist, theta_all, score_all, n, d, row0, n_local, dtype, h2_dev, v.planes,
-                                   workspace, ws_bytes, 0, stream)))
-    return rc;
-  if ((rc = clk.mark(STEIN_T_FINISH, s))) return rc;
-  rc = contract_finish_impl(theta_all, score_all, n, d, row0, n_local, dtype, h2_dev, phi_local, sqnorm_out, dK_out,
-                            workspace, ws_bytes, (v.planes ? STEIN_FLAG_X3 : 0) | (flags & STEIN_FLAG_KSD) | STEIN_FLAG_NO_FOLD,
-                            stream, nullptr);
-  return rc ? rc : clk.mark(STEIN_T_NSTAGES, s);
+  int rc = stein_rank_views(b, workspace, ws_bytes, flags, &v);
+  return rc ? rc : stein_rank_finish_on(v, b, theta_all, score_all, h2_dev, phi_local, sqnorm_out, dK_out, flags,
+                                        (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -776,29 +843,28 @@ extern "C" int stein_timing_read(float* ms_out, int max_calls, int* calls_out) {
 // operand planes.  bf16 inputs need no scales, so the split does not depend on the prologue: both ride in ONE launch
 // (k_split's grid gets a third slice that does the prologue's work) -- one launch less on the latency-bound sizes this
 // dtype is for.
-static int fused_prologue(const StepViews& v, const void* theta_all, const void* score_all, int64_t n, int64_t d, int dtype,
-                          int flags, hipStream_t s, int fold) {
-  const SteinLayout& L = v.L;
+static int fused_prologue(const StepViews& v, const BlockShape& b, const void* theta_all, const void* score_all, int flags,
+                          hipStream_t s, int fold) {
+  const bool bf16_split = b.dtype == STEIN_BF16 && v.planes;
   PrologueArgs pa;
-  pa.n = (int)n; pa.d = (int)d; pa.r = v.r; pa.st = v.sel; pa.sp = v.spec; pa.fs = v.fuse; pa.total = (u64)(n * n);
+  pa.n = (int)b.n; pa.d = (int)b.d; pa.r = v.r; pa.st = v.sel; pa.sp = v.spec; pa.fs = v.fuse; pa.total = (u64)(b.n * b.n);
   pa.hist = v.hist; pa.slots = v.spec_buf;
-  pa.cmax = v.planes ? (u32*)((float*)(v.planes + L.x3_sc) + 4 * L.x3_dc + 4) : nullptr;   // the column maxima behind the
-  pa.ncmax = v.planes ? (int)(2 * L.x3_dc) : 0;                                              // scales (stein_x3.hip)
+  pa.cmax = v.cmax;   // the column maxima behind the scales (stein_x3.hip); NULL without the planes
+  pa.ncmax = v.planes ? (int)(2 * v.L.x3_dc) : 0;
   pa.allow_window = (flags & STEIN_FLAG_NO_WINDOW) ? 0 : 1;
   pa.hsync = (u32*)v.table; pa.hsync_words = (int)(sizeof(HistSync) / 4);
-  pa.neutral_sc = (dtype == STEIN_BF16 && v.planes) ? (float*)(v.planes + L.x3_sc) : (float*)nullptr;
-  pa.dc = (int)L.x3_dc;
+  pa.neutral_sc = bf16_split ? v.sc : (float*)nullptr;
+  pa.dc = (int)v.L.x3_dc;
   pa.folded = fold ? 1u : 0u;
-  if (dtype == STEIN_BF16 && v.planes)
-    return stein_x3_split(theta_all, score_all, dtype, n, d, L, v.planes, s, (HistSync*)v.table, true, &pa);
-  const dim3 grid((unsigned)((n + 3) / 4 + PRO_INIT_BLOCKS));
-  if (dtype == STEIN_BF16)
+  const SplitFused fused{(HistSync*)v.table, bf16_split ? &pa : nullptr, fold};
+  if (bf16_split) return stein_x3_split(v, theta_all, score_all, b.dtype, b.n, b.d, s, &fused);
+  const dim3 grid((unsigned)((b.n + 3) / 4 + PRO_INIT_BLOCKS));
+  if (b.dtype == STEIN_BF16)
     hipLaunchKernelGGL(k_prologue<unsigned short>, grid, dim3(256), 0, s, (const unsigned short*)theta_all, pa);
   else
     hipLaunchKernelGGL(k_prologue<float>, grid, dim3(256), 0, s, (const float*)theta_all, pa);
   LAUNCH_CHECK("k_prologue");
-  return v.planes ? stein_x3_split(theta_all, score_all, dtype, n, d, L, v.planes, s, (HistSync*)v.table, false, nullptr, fold)
-                  : STEIN_OK;
+  return v.planes ? stein_x3_split(v, theta_all, score_all, b.dtype, b.n, b.d, s, &fused) : STEIN_OK;
 }
 
 extern "C" int stein_svgd_phi(const void* theta_all, const void* score_all, int64_t n, int64_t d, int64_t row0,
@@ -808,22 +874,22 @@ extern "C" int stein_svgd_phi(const void* theta_all, const void* score_all, int6
     return fail(STEIN_E_BADARG, "NULL pointer");
   if (row0 != 0 || n_local != n)
     return fail(STEIN_E_BADARG, "stein_svgd_phi is the single-rank path (row0 = 0, n_local = n); use the staged calls");
+  const BlockShape b{n, d, row0, n_local, dtype};
   SteinLayout L;
-  int rc = stein_make_layout(n_local, n, d, dtype, flags, &L);
+  int rc = stein_make_layout(n_local, n, d, dtype, flags, &L);   // (the fused family: the caller's flags as they are)
   if (rc) return rc;
   if ((rc = stein_take_device_error())) return rc;   // a kernel of an earlier call on this device gave up: say so now
-  if (dtype == STEIN_BF16 && !(flags & STEIN_FLAG_X3))
-    return fail(STEIN_E_UNSUPPORTED, "bf16 inputs run on the bf16-MFMA kernels: pass STEIN_FLAG_X3");
+  if ((rc = check_block("stein_svgd_phi", b, (flags & STEIN_FLAG_X3) != 0))) return rc;   // (bf16 runs on the bf16-MFMA kernels)
   if (ws_bytes < L.total) return fail(STEIN_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L.total);
   const StepViews v = stein_step_views(L, workspace);
   hipStream_t s = (hipStream_t)stream;
+  const bool ksd = (flags & STEIN_FLAG_KSD) != 0;
   const StageTimer clk(flags);   // STEIN_FLAG_TIMING: one event per stage boundary
   if ((rc = clk.mark(STEIN_T_PREPARE, s))) return rc;
   if (!(flags & STEIN_FLAG_TILED) && stein_small_ok(n, d, dtype)) {   // the reference's own example sizes: one kernel does it all (stein_small.hip)
     for (int k = STEIN_T_DISTANCE; k <= STEIN_T_CONTRACT; ++k)
       if ((rc = clk.mark(k, s))) return rc;
     int nparts = 0;
-    const bool ksd = (flags & STEIN_FLAG_KSD) != 0;
     if ((rc = stein_small_phi((const float*)theta_all, (const float*)score_all, n, d, phi_local, h2_out, v.SQ, K_out,
                               dK_out, &nparts, sqnorm_out, ksd, s)))
       return rc;
@@ -839,32 +905,27 @@ extern "C" int stein_svgd_phi(const void* theta_all, const void* score_all, int6
   // HistSync, so no grid is too large for them); bf16 inputs: six.
   // folded operand (L.fold: split path, fp32 inputs, where it pays or is forced): the contraction multiplies K with
   // W = G - theta / h2 alone; with dK_out or the Stein discrepancy, with [W | theta] -- phi comes from the W half either way
-  const bool fold_theta = L.fold && (dK_out || (flags & STEIN_FLAG_KSD));
-  if ((rc = fused_prologue(v, theta_all, score_all, n, d, dtype, flags, s, L.fold ? (fold_theta ? 2 : 1) : 0))) return rc;
+  const bool fold_theta = L.fold && (dK_out || ksd);
+  if ((rc = fused_prologue(v, b, theta_all, score_all, flags, s, L.fold ? (fold_theta ? 2 : 1) : 0))) return rc;
   if ((rc = clk.mark(STEIN_T_DISTANCE, s))) return rc;
   // single rank: the block is the whole symmetric matrix -> upper-triangle distance pass with mirrored stores,
   // level-0 histogram taken in its epilogue, levels 1-2 read the upper triangle only
   const int sf = STEIN_STAGE_SYMMETRIC | ((flags & STEIN_FLAG_TILE_DISTANCE) ? STEIN_STAGE_TILES : 0);
-  if ((rc = distance_block_impl(theta_all, v.r, n, d, row0, n_local, dtype, v.D, L.ld_dist, v.hist, v.planes, sf, stream,
-                                v.spec, v.spec_buf)))
-    return rc;
+  if ((rc = distance_stage(v, b, theta_all, sf, true, s))) return rc;
   if ((rc = clk.mark(STEIN_T_MEDIAN, s))) return rc;
   if ((rc = stein_fused_select(v, n, h2_out, s))) return rc;
   // the split path's symmetric distance pass stores only the tiles on and above the diagonal
-  const int df = v.planes ? (STEIN_STAGE_SYMMETRIC | STEIN_STAGE_UPPER) : STEIN_STAGE_SYMMETRIC;
-  if (K_out && (rc = stein_kernel_matrix(v.D, L.ld_dist, n_local, n, h2_out, K_out, n, df, stream))) return rc;
-  if (L.fold && (rc = stein_x3_split_w((const float*)theta_all, (const float*)score_all, n, d, L, v.planes, h2_out, s))) return rc;
+  const bool upper = v.planes != nullptr;
+  if (K_out && (rc = stein_kernel_matrix(v.D, L.ld_dist, n_local, n, h2_out, K_out, n,
+                                         STEIN_STAGE_SYMMETRIC | (upper ? STEIN_STAGE_UPPER : 0), stream)))
+    return rc;
+  if (L.fold && (rc = stein_x3_split_w(v, (const float*)theta_all, (const float*)score_all, n, d, h2_out, s))) return rc;
   if ((rc = clk.mark(STEIN_T_CONTRACT, s))) return rc;
-  if (L.fold) rc = stein_x3_contract_fold(v.D, L.ld_dist, (char*)workspace, L, h2_out, n, d, fold_theta, s);
-  else rc = stein_contract_partial(v.D, L.ld_dist, theta_all, score_all, n, d, row0, n_local, dtype, h2_out, v.planes,
-                                   workspace, ws_bytes, df, stream);
+  if (L.fold) rc = stein_x3_contract_fold(v, h2_out, n, d, fold_theta, s);
+  else rc = contract_stage(v, b, theta_all, score_all, h2_out, upper, s);
   if (rc) return rc;
   if ((rc = clk.mark(STEIN_T_FINISH, s))) return rc;
-  const int keep = STEIN_FLAG_KSD | STEIN_FLAG_TILED | STEIN_FLAG_FOLD | STEIN_FLAG_NO_FOLD;   // what the layout depends on
-  if ((rc = contract_finish_impl(theta_all, score_all, n, d, row0, n_local, dtype, h2_out, phi_local, sqnorm_out, dK_out,
-                                 workspace, ws_bytes, (v.planes ? STEIN_FLAG_X3 : 0) | (flags & keep), stream,
-                                 (HistSync*)v.table)))
+  if ((rc = finish_stage(v, b, theta_all, score_all, h2_out, phi_local, sqnorm_out, dK_out, ksd, (HistSync*)v.table, s)))
     return rc;
   return clk.mark(STEIN_T_NSTAGES, s);
 }
-

@@ -245,3 +245,52 @@ def test_column_maxima_paths_agree(cuda):
     st.x3_prepare(T_un, G_un, n, d, eng.planes)
     torch.cuda.synchronize()
     assert torch.equal(eng.planes, aligned)
+
+
+@pytest.mark.parametrize("n,d,dtype", [(385, 1, torch.float32), (1281, 129, torch.float32), (385, 1, torch.bfloat16)],
+                         ids=["385x1-f32", "1281x129-f32", "385x1-bf16"])
+def test_staged_calls_on_the_smallest_buffers(cuda, n, d, dtype):
+    """include/steinhip.h: the staged calls take the operand planes as a buffer of their own (total - off[PLANES] bytes)
+    and a workspace that need only reach its PLANES section.  Distance, median, contract-partial and contract-finish on
+    two tensors of exactly those sizes give phi, h2 and |phi|^2 to the bit as the same engine's compute_phi(mark=...) does
+    on its full-size workspace.  (385, 1): four ragged row tiles, one column; (1281, 129): eleven row tiles, two column
+    blocks."""
+    T64, G64 = _inputs(n, d, seed=17)
+    T = torch.tensor(T64, dtype=torch.float32, device=cuda).to(dtype)
+    G = torch.tensor(G64, dtype=torch.float32, device=cuda).to(dtype)
+    eng = SvgdEngine(n, d, device=cuda, x3=True, dtype=dtype, small=False)
+    eng.compute_phi(T, G, mark=lambda label: None)
+    torch.cuda.synchronize()
+    want = eng.phi.clone(), eng.h2.clone(), eng.sqnorm.clone()
+
+    st = eng.stages
+    flags = _lib.FLAG_X3 | _lib.FLAG_TILED
+    total, offs, extra = st.workspace_layout(n, n, d, flags, _lib.BF16 if dtype == torch.bfloat16 else _lib.F32)
+    ld = extra[_lib.WSX_LD_DIST]
+    ws = torch.empty(offs[_lib.WS_PLANES], dtype=torch.uint8, device=cuda)
+    planes = torch.empty(total - offs[_lib.WS_PLANES], dtype=torch.uint8, device=cuda)
+
+    def section(sec, nbytes, as_dtype):
+        return ws[offs[sec]:offs[sec] + nbytes].view(as_dtype)
+    r = section(_lib.WS_ROWNORM, n * 4, torch.float32)
+    D = section(_lib.WS_DIST, (n + 127) // 128 * 128 * ld * 4, torch.float32)
+    hist = section(_lib.WS_HIST, _lib.HIST_LEVELS * 2 * _lib.HIST_BINS * 8, torch.int64).view(_lib.HIST_LEVELS, 2, _lib.HIST_BINS)
+    sel = section(_lib.WS_SELECT, 128, torch.uint8)
+    phi = torch.empty(n, d, dtype=torch.float32, device=cuda)
+    h2, median = torch.zeros(1, device=cuda), torch.zeros(1, device=cuda)
+    sq = torch.zeros(1, dtype=torch.float64, device=cuda)
+
+    st.rownorms(T, n, d, r)
+    st.x3_prepare(T, G, n, d, planes)
+    st.median_begin(hist, sel, n * n)
+    st.distance_block(T, r, n, d, 0, n, D, ld, hist0=hist[0], symmetric=True, planes=planes)
+    for level in range(_lib.HIST_LEVELS):
+        if level > 0:
+            st.median_hist_pass(D, ld, n, n, level, sel, hist, symmetric=True)
+        st.median_resolve(hist, level, n, sel, h2, median)
+    st.contract_partial(D, ld, T, G, n, d, 0, n, h2, ws, planes, upper=True)
+    st.contract_finish(T, n, d, 0, n, h2, phi, sq, None, ws, flags)
+    torch.cuda.synchronize()
+    assert torch.equal(h2, want[1]), (h2.item(), want[1].item())
+    assert torch.equal(phi, want[0])
+    assert torch.equal(sq, want[2]), (sq.item(), want[2].item())
