@@ -170,6 +170,42 @@ int stein_svgd_phi(const void* theta_all, const void* score_all, int64_t n, int6
                    float* K_out, float* dK_out,
                    void* workspace, size_t ws_bytes, int flags, void* stream);
 
+/* ---- streaming single-rank path: the bandwidth is the caller's, the workspace is O(n d) --------------------------
+ * The same reference lines as stein_svgd_phi with SquaredExponentialKernel's bandwidth GIVEN (Liu & Wang's
+ * svgd_kernel(theta, h) with h > 0) instead of taken from the median of all n^2 distances:
+ *   phi = (K.G + (rowsum(K) theta - K.theta) / h2) / n,   K_ij = exp(-|theta_i - theta_j|^2 / (2 h2)),   h2 = *h2_in
+ * With h2 known up front neither the median select nor the n x n distance image is needed: W = G - theta / h2 is built
+ * first and every 128 x 128 tile of D is exponentiated and contracted with W as soon as it is complete, then dropped
+ * (stein_amd/csrc/stein_stream.hip; same split-fp16 arithmetic per entry as STEIN_FLAG_X3 | STEIN_FLAG_FOLD).
+ *   theta, score : [n][d] float (dtype must be STEIN_F32; STEIN_BF16 returns STEIN_E_UNSUPPORTED)
+ *   h2_in        : DEVICE float[1], bandwidth^2, read by the kernels of this call: the caller may rewrite it on the stream
+ *                  between calls (an annealing schedule, another workspace's h2_out) without a host round trip.  The host
+ *                  cannot validate a device scalar: h2 = 0 gives NaN phi, as on every other path.
+ *   phi          : [n][d] float (unclipped);  sqnorm_out: double[1] = sum(phi^2), what stein_apply_* read
+ *   flags        : must be 0 (STEIN_E_BADARG otherwise).  n >= 1 (no ln n here), d >= 1.
+ * Limits of this entry: fp32 inputs, one rank (all n rows), no K_out / dK_out, no Stein discrepancy.  d > 256 is taken
+ * in ceil(d / 256) column groups, each of which recomputes the distance tiles: correct for any d, but the
+ * stored-D path is the one for wide particles.
+ * The workspace must be 16-byte aligned (STEIN_E_BADARG otherwise; hipMalloc and PyTorch allocations are).  It carries
+ * nothing from call to call and its contents on entry do not matter.  Its size has no term in n^2:
+ *   stein_stream_workspace_bytes = 4 N + 4 (6 dc + 4) + 6 N dk + 6 N dc + 4 jsplit n d + 4 jsplit n + 8 min(1024, ceil(n d / 1024)),
+ *   N = roundup(n, 128), dk = roundup(d, 32), dc = roundup(d, 128), every term rounded up to 256 bytes
+ *   (row norms | scales | theta's planes | W's planes | partial K.W | partial rowsum(K) | |phi|^2 block partials).
+ * stein_stream_plan (host arithmetic): row_tiles = ceil(n / 128), col_groups = ceil(d / 256) and the number of j ranges
+ * jsplit = clamp(floor(256 / (row_tiles col_groups)), 1, row_tiles) with empty tails dropped -- one workgroup per
+ * (row tile, column group, j range); the ranges' partial sums are added in range order, no float atomics: a repeated call
+ * is bit-identical.  The 256 is the MI355X's CU count, built in as a constant (the plan and with it the workspace size stay
+ * host arithmetic; on a part with another count the plan is still correct, only less well filled).
+ * jsplit > 1 only while the whole grid fits the 256 CUs, so the partial sums hold at most 32 MiB more
+ * than n d floats.  stein_debug_stream_jsplit(k) (test hook, per calling thread): k > 0 replaces the floor(...) above in
+ * the plan, the workspace size and the call alike; 0 restores the rule. */
+int stein_stream_workspace_bytes(int64_t n, int64_t d, int dtype, int flags, size_t* out_bytes);
+int stein_stream_plan(int64_t n, int64_t d, int* row_tiles, int* col_groups, int* jsplit);
+int stein_svgd_phi_stream(const void* theta, const void* score, int64_t n, int64_t d, int dtype,
+                          const float* h2_in, float* phi, double* sqnorm_out,
+                          void* workspace, size_t ws_bytes, int flags, void* stream);
+int stein_debug_stream_jsplit(int jsplit);
+
 /* ---- staged path (tests, multi-rank: the host puts collectives between the stages) ------------ */
 
 /* r_i = sum_k theta_ik^2            abstract_kernel.py:34 */

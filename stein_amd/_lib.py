@@ -70,6 +70,10 @@ _SIGNATURES = {
     "stein_timing_reserve": [_int],
     "stein_timing_read": [_c.POINTER(_c.c_float), _int, _c.POINTER(_int)],
     "stein_svgd_phi": [_vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _int, _vp],
+    "stein_stream_workspace_bytes": [_i64, _i64, _int, _int, _c.POINTER(_sz)],
+    "stein_stream_plan": [_i64, _i64, _c.POINTER(_int), _c.POINTER(_int), _c.POINTER(_int)],
+    "stein_svgd_phi_stream": [_vp, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _sz, _int, _vp],
+    "stein_debug_stream_jsplit": [_int],
     "stein_rownorms": [_vp, _i64, _i64, _int, _vp, _vp],
     "stein_distance_block": [_vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _i64, _vp, _vp, _int, _vp],
     "stein_x3_prepare": [_vp, _vp, _i64, _i64, _int, _vp, _sz, _vp],
@@ -161,6 +165,25 @@ def layout_folds(n_local, n, d, dtype=F32, flags=0):
     out = _int(0)
     call("stein_layout_folds", n_local, n, d, dtype, flags, ctypes.byref(out))
     return bool(out.value)
+
+
+def stream_workspace_bytes(n, d, dtype=F32, flags=0):
+    """Workspace bytes of the streaming step (stein_svgd_phi_stream): O(n d), no distance image.  Host arithmetic."""
+    total = _sz(0)
+    call("stein_stream_workspace_bytes", n, d, dtype, flags, ctypes.byref(total))
+    return int(total.value)
+
+
+def stream_plan(n, d):
+    """-> (row_tiles, col_groups, jsplit) of the streaming step's grid.  Host arithmetic."""
+    rt, cg, js = _int(0), _int(0), _int(0)
+    call("stein_stream_plan", n, d, ctypes.byref(rt), ctypes.byref(cg), ctypes.byref(js))
+    return int(rt.value), int(cg.value), int(js.value)
+
+
+def debug_stream_jsplit(jsplit):
+    """Test hook (per calling thread): j ranges the streaming step's plan asks for; 0 restores the plan's own rule."""
+    call("stein_debug_stream_jsplit", int(jsplit))
 
 
 def version():

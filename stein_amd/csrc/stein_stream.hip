@@ -1,0 +1,408 @@
+// stein_stream.hip -- the SVGD direction at a bandwidth the caller supplies, without the n x n distance image.
+//
+// With h2 known before the step starts nothing needs all of D at once: the folded operand W = G - theta / h2 (stein_x3.hip,
+// "folded operand") is built first, and a tile of D is exponentiated and contracted with W the moment its accumulators are
+// complete, then dropped.  The workspace is O(n d): row norms, scales, theta's row-major planes, W's transposed planes and
+// the partial sums (stein_stream_make_layout below).
+//
+//   stein_rownorms, k_colmax, k_make_scales, k_split (theta, row-major image only), k_split_w   as they are (stein_x3.hip)
+//   k_phi_stream        distance tile -> P = exp2(c D + 14) -> O += P.W, running rowsum(P); D and K never reach memory
+//   k_stream_finish     sums the j ranges in order, phi = (K.W + rowsum(K) theta / h2) / n, |phi|^2 block partials (fp64)
+//   k_stream_sqsum      one workgroup: the block partials -> sqnorm_out
+//
+// k_phi_stream: a 512-thread workgroup (8 waves, two per SIMD) owns 128 rows of particles x one column group of W (two
+// 128-column blocks) x one range of 128-column j tiles.  Per j tile:
+//   distance     wave w computes the 32 rows x 64 columns (w >> 1, w & 1) of S^T = T_j T_i^T on 16x16x32 fp16 MFMAs, three
+//                products per fragment pair (x3_products16), both operands read in fragment order straight from theta's
+//                planes T3 (1 KB coalesced loads; the row tile's panel stays in the L2).  Transposed, so that a lane
+//                holds FOUR CONSECUTIVE j of one row i: one 8-byte LDS store per plane.
+//   exp / split  D = (r_i + r_j) - two_s S, P = exp2(c D + 14), columns j >= n forced to 0, hi = fp16(P), lo = fp16(P - hi)
+//                into the LDS image the stored-D contraction uses ([k tile][plane][128 rows][64 B], pswz); rowsum += P
+//   barrier      (one per j tile: the P image is double-buffered)
+//   contraction  wave w owns all 128 rows x the 32 columns (w & 3) of 128-column block w >> 2: A fragments (P) by
+//                ds_read_b128, B fragments (W) by coalesced 1 KB loads from W's planes, three products each
+// Every load is plain C++ (the compiler counts its own waits); no workgroup waits for another; every loop bound is an
+// argument.  The partial sums of the j ranges go to [jsplit][n][d] / [jsplit][n] and are added in range order by the finish
+// pass: no float atomics, a repeated call is bit-identical.
+// Resources (hipcc, gfx950): recorded in DESIGN.md, "streaming step".
+
+#include "stein_x3.h"
+
+#include "stein_x3_dev.h"
+
+constexpr int ST_THREADS = 512;
+constexpr int ST_ROWS = 128;              // particles per row tile
+constexpr int ST_JT = 128;                // columns of D per step (4 k tiles of the contraction)
+constexpr int ST_COLS = 256;              // columns of W per column group
+constexpr int ST_PLN = ST_ROWS * XROW;    // one plane of one 32-deep k tile of P in LDS: 8 KB
+constexpr int ST_KTB = 2 * ST_PLN;        // hi and lo plane
+constexpr int ST_BUF = (ST_JT / 32) * ST_KTB;   // one P image: 64 KB; two of them
+constexpr int ST_PEXP = 14;               // P = exp2(c D + 14): the fp16 range of the stored-D contraction (PEXP_H2)
+constexpr double ST_RESIDENT = 256.0;     // workgroups the chip holds at once (one per CU: 128 KB of LDS each).  The MI355X's 256
+                                          // CUs, as a constant: the plan and the workspace size are host arithmetic
+                                          // (stein_make_layout's contraction plan does the same)
+
+// the P image's per-row chunk permutation and the fp16 split of a pair: the stored-D contraction's (stein_x3.hip), so that
+// both paths do the same arithmetic per entry
+__device__ __forceinline__ int st_pswz(int row, int chunk) { return (chunk ^ ((0x78 >> (((row >> 2) & 3) * 2)) & 3)) * 16; }
+__device__ __forceinline__ u32 st_cvt_pk_f16(float lo, float hi) {   // round-to-nearest-even, lo -> bits 15:0
+  u32 r;
+  asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+  return r;
+}
+__device__ __forceinline__ float st_resid_lo(u32 h, float x) {   // x - (fp16 in the low half of h), exact
+  float r;
+  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(x));
+  return r;
+}
+__device__ __forceinline__ float st_resid_hi(u32 h, float x) {
+  float r;
+  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(x));
+  return r;
+}
+
+__global__ __launch_bounds__(ST_THREADS) void k_phi_stream(const u16* __restrict__ T3, int ntk, const u16* __restrict__ Wt3,
+                                                           long ntj, const float* __restrict__ r,
+                                                           const float* __restrict__ sc, int dc,
+                                                           const float* __restrict__ h2p, float* __restrict__ O,
+                                                           float* __restrict__ RS, int n, int d, int row_tiles,
+                                                           int col_groups, int cblocks, int jtiles, int jtiles_per) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * ST_BUF];
+  // column group fastest: the workgroups of one row tile are neighbours (same XCD, same T panels in its L2)
+  const int logical = xcd_remap(blockIdx.x, gridDim.x);
+  const int cg = logical % col_groups;
+  const int tile_m = (logical / col_groups) % row_tiles;
+  const int z = logical / (col_groups * row_tiles);
+  const int i0 = tile_m * ST_ROWS;
+  const int jt0 = z * jtiles_per, jt1 = min(jtiles, jt0 + jtiles_per);
+
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int l15 = lane & 15, lq = lane >> 4;
+  // distance role: rows [32 wr, 32 wr + 32) x columns [64 wc, 64 wc + 64) of the 128 x 128 tile
+  const int wr = w >> 1, wc = w & 1;
+  // contraction role: all 128 rows x 32 columns at wcol of 128-column block g.  A block past the matrix's last (an odd block
+  // count: d <= 128, or the last column group) has nothing to contract: its four waves only take part in the distance
+  // tiles and the barriers (wave-uniform test)
+  const int g = 2 * cg + (w >> 2);
+  const bool live = g < cblocks;
+  const int gl = min(g, cblocks - 1);
+  const int wcol = (w & 3) * 32;
+
+  const float cexp = -1.44269504088896341f / (2.f * *h2p);   // exp(-D / (2 h2)) = exp2(cexp D)
+  const float two_s = sc[4 * dc + 1];
+  float ri[2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a) ri[a] = r[i0 + wr * 32 + a * 16 + l15];   // (r is padded to the row tiles; rows >= n are never stored)
+  float rs[2] = {0.f, 0.f};
+
+  f32x4 acc[8][2];
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const u16* __restrict__ ta = T3 + (size_t)tile_m * ntk * 3 * XTILE_E + (wr * 2) * 512 + lane * 8;
+  const u16* __restrict__ wb = Wt3 + (size_t)gl * ntj * 3 * XTILE_E + wcol * 32 + lane * 8;
+  const int aoff = l15 * XROW + st_pswz(l15, lq);
+
+  for (int jt = jt0; jt < jt1; ++jt) {
+    unsigned char* buf = smem + ((jt - jt0) & 1) * ST_BUF;
+    const int j0 = jt * ST_JT;
+    // ---- distance: S^T block [4 j blocks][2 i blocks] of this wave
+    f32x4 s[4][2];
+#pragma unroll
+    for (int jb = 0; jb < 4; ++jb)
+#pragma unroll
+      for (int ib = 0; ib < 2; ++ib) s[jb][ib] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const u16* __restrict__ tb = T3 + (size_t)jt * ntk * 3 * XTILE_E + (wc * 4) * 512 + lane * 8;
+    for (int kt = 0; kt < ntk; ++kt) {
+      u32x4 fa[2][3], fb[4][3];
+#pragma unroll
+      for (int p = 0; p < 2; ++p) {
+#pragma unroll
+        for (int ib = 0; ib < 2; ++ib)
+          fa[ib][p] = *reinterpret_cast<const u32x4*>(ta + ((size_t)kt * 3 + p) * XTILE_E + ib * 512);
+#pragma unroll
+        for (int jb = 0; jb < 4; ++jb)
+          fb[jb][p] = *reinterpret_cast<const u32x4*>(tb + ((size_t)kt * 3 + p) * XTILE_E + jb * 512);
+      }
+#pragma unroll
+      for (int jb = 0; jb < 4; ++jb)
+#pragma unroll
+        for (int ib = 0; ib < 2; ++ib) s[jb][ib] = x3_products16<2>(fb[jb], fa[ib], s[jb][ib]);
+    }
+    // ---- exp, split, stage: lane holds S^T[j = 16 jb + 4 lq + e][i = 16 ib + l15]
+#pragma unroll
+    for (int jb = 0; jb < 4; ++jb) {
+      const int jc = wc * 64 + jb * 16 + 4 * lq;          // first of this lane's 4 columns inside the tile
+      const float4 rj4 = *reinterpret_cast<const float4*>(r + j0 + jc);   // (padded; columns >= n are masked below)
+      const float rj[4] = {rj4.x, rj4.y, rj4.z, rj4.w};
+#pragma unroll
+      for (int ib = 0; ib < 2; ++ib) {
+        float q[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float dv = (ri[ib] + rj[e]) - two_s * s[jb][ib][e];
+          q[e] = __builtin_amdgcn_exp2f(__builtin_fmaf(cexp, dv, (float)ST_PEXP));
+          q[e] = (j0 + jc + e < n) ? q[e] : 0.f;
+        }
+        rs[ib] += (q[0] + q[1]) + (q[2] + q[3]);
+        const u32 h0 = st_cvt_pk_f16(q[0], q[1]), h1 = st_cvt_pk_f16(q[2], q[3]);
+        const u32 o0 = st_cvt_pk_f16(st_resid_lo(h0, q[0]), st_resid_hi(h0, q[1]));
+        const u32 o1 = st_cvt_pk_f16(st_resid_lo(h1, q[2]), st_resid_hi(h1, q[3]));
+        const int row = wr * 32 + ib * 16 + l15;
+        unsigned char* dst = buf + (jc >> 5) * ST_KTB + row * XROW + st_pswz(row, (jc & 31) >> 3) + (jc & 4) * 2;
+        *reinterpret_cast<uint2*>(dst) = make_uint2(h0, h1);
+        *reinterpret_cast<uint2*>(dst + ST_PLN) = make_uint2(o0, o1);
+      }
+    }
+    __syncthreads();
+    // ---- contraction: O += P . W_j over the tile's (up to) four 32-deep k tiles
+    for (int kt = 0; live && kt < ST_JT / 32; ++kt) {
+      if (j0 + kt * 32 >= n) break;   // P is zero there
+      u32x4 b[2][3];
+      const u16* __restrict__ src = wb + ((size_t)jt * (ST_JT / 32) + kt) * 3 * XTILE_E;
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int p = 0; p < 2; ++p) b[j][p] = *reinterpret_cast<const u32x4*>(src + p * XTILE_E + j * 512);
+      const unsigned char* As = buf + kt * ST_KTB + aoff;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        u32x4 a[3];
+#pragma unroll
+        for (int p = 0; p < 2; ++p) a[p] = *reinterpret_cast<const u32x4*>(As + i * 16 * XROW + p * ST_PLN);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = x3_products16<2>(a, b[j], acc[i][j]);
+      }
+    }
+  }
+
+  // ---- partial O of this j range (out-scaled), partial row sums
+  if (live) {
+    float* __restrict__ Oz = O + (size_t)z * n * d;
+    const float* __restrict__ osc = sc + 2 * dc;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int col = g * 128 + wcol + j * 16 + l15;
+      if (col >= d) continue;
+      const float os = osc[col];
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int row = i0 + i * 16 + 4 * lq + e;
+          if (row < n) Oz[(size_t)row * d + col] = acc[i][j][e] * os;
+        }
+    }
+  }
+  if (cg == 0) {
+    // a row's sum: the four lane groups lq of a wave, then the two waves wc = 0, 1 (through LDS, in that order)
+    __syncthreads();   // every wave is past its last read of the P images
+    float* red = reinterpret_cast<float*>(smem);   // [2][128]
+#pragma unroll
+    for (int ib = 0; ib < 2; ++ib) {
+      float a = rs[ib];
+      a += __shfl_xor(a, 16);
+      a += __shfl_xor(a, 32);
+      if (lq == 0) red[wc * ST_ROWS + wr * 32 + ib * 16 + l15] = a;
+    }
+    __syncthreads();
+    const int row = i0 + t;
+    if (t < ST_ROWS && row < n) RS[(size_t)z * n + row] = (red[t] + red[ST_ROWS + t]) * sc[4 * dc + 2];
+  }
+}
+
+// phi = (sum_z O_z + (sum_z RS_z) theta / h2) / n (the folded finish of k_phi_finish, steinhip.hip) and this workgroup's
+// fp64 partial of |phi|^2.  vec: d % 4 == 0 and every pointer 16-byte aligned.
+__global__ __launch_bounds__(256) void k_stream_finish(const float* __restrict__ O, const float* __restrict__ RS,
+                                                       const float* __restrict__ T, const float* __restrict__ h2p,
+                                                       float* __restrict__ phi, double* __restrict__ sqpart, int n, int d,
+                                                       int jsplit, int vec) {
+  __shared__ double red[4];
+  const float h2 = *h2p;
+  const float fn = (float)n;
+  const long total = (long)n * d;
+  const size_t zs = (size_t)n * d;
+  double sq = 0.0;
+  if (vec) {
+    const long total4 = total >> 2;
+    const int d4 = d >> 2;
+    for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < total4; q += (long)gridDim.x * 256) {
+      const int i = (int)(q / d4);
+      const long e = q << 2;
+      float4 og = make_float4(0.f, 0.f, 0.f, 0.f);
+      float rs = 0.f;
+      for (int z = 0; z < jsplit; ++z) {
+        const float4 a = *reinterpret_cast<const float4*>(O + z * zs + e);
+        og.x += a.x; og.y += a.y; og.z += a.z; og.w += a.w;
+        rs += RS[(size_t)z * n + i];
+      }
+      const float4 th = *reinterpret_cast<const float4*>(T + e);
+      float4 ph;
+      ph.x = (og.x + rs * th.x / h2) / fn; ph.y = (og.y + rs * th.y / h2) / fn;
+      ph.z = (og.z + rs * th.z / h2) / fn; ph.w = (og.w + rs * th.w / h2) / fn;
+      *reinterpret_cast<float4*>(phi + e) = ph;
+      sq += ((double)ph.x * (double)ph.x + (double)ph.y * (double)ph.y) + ((double)ph.z * (double)ph.z + (double)ph.w * (double)ph.w);
+    }
+  } else {
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+      const int i = (int)(e / d);
+      float og = 0.f, rs = 0.f;
+      for (int z = 0; z < jsplit; ++z) {
+        og += O[z * zs + e];
+        rs += RS[(size_t)z * n + i];
+      }
+      const float ph = (og + rs * T[e] / h2) / fn;
+      phi[e] = ph;
+      sq += (double)ph * (double)ph;
+    }
+  }
+  double part[1] = {sq};
+  block_sum256(part, red);
+  if (threadIdx.x == 0) sqpart[blockIdx.x] = part[0];
+}
+
+// the block partials of k_stream_finish, in a fixed order -> sqnorm_out[0]
+__global__ __launch_bounds__(256) void k_stream_sqsum(const double* __restrict__ part, int count, double* __restrict__ out) {
+  __shared__ double red[4];
+  double s[1] = {0.0};
+  for (int i = threadIdx.x; i < count; i += 256) s[0] += part[i];
+  block_sum256(s, red);
+  if (threadIdx.x == 0) out[0] = s[0];
+}
+
+// ================================================================================================
+// host side
+// ================================================================================================
+static thread_local int g_stream_jsplit = 0;   // stein_debug_stream_jsplit: 0 = the plan's own rule
+
+struct StreamLayout {
+  int64_t row_tiles, col_groups, cblocks, jsplit, jtiles_per, sq_blocks;
+  int64_t rows, dk, dc, nk;                      // padded extents of the planes (the x3_* of SteinLayout)
+  size_t r, sc, t3, wt3, o, rs, sq, total;       // byte offsets, 256-byte aligned
+};
+
+static inline size_t st_align(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+static int stream_check_shape(int64_t n, int64_t d, int dtype, int flags) {
+  if (dtype == STEIN_BF16) return fail(STEIN_E_UNSUPPORTED, "the streaming step takes fp32 inputs (STEIN_F32), not bf16");
+  if (dtype != STEIN_F32) return fail(STEIN_E_UNSUPPORTED, "dtype %d", dtype);
+  if (flags != 0) return fail(STEIN_E_BADARG, "the streaming step takes no flags, got 0x%x", flags);
+  if (n < 1 || d < 1) return fail(STEIN_E_SHAPE, "bad shape n=%lld d=%lld", (long long)n, (long long)d);
+  if (n > (1ll << 30) || d > (1ll << 24) || n * d > (1ll << 40)) return fail(STEIN_E_SHAPE, "shape too large");
+  return STEIN_OK;
+}
+
+// The plan: one workgroup per (row tile, column group, j range).  The j ranges fill the resident grid (one workgroup per CU)
+// when the row tiles and column groups alone do not: jsplit = floor(resident / (row_tiles col_groups)), at most one range
+// per 128-column j tile; ranges are whole j tiles and empty tails are dropped.  So jsplit > 1 only while
+// jsplit row_tiles col_groups <= resident: the partial sums then hold at most resident x 128 x 256 floats (32 MiB),
+// whatever n and d; beyond that there is one range and they are n d floats.
+static int stream_make_layout(int64_t n, int64_t d, StreamLayout* L) {
+  L->row_tiles = (n + ST_ROWS - 1) / ST_ROWS;
+  L->cblocks = (d + 127) / 128;
+  L->col_groups = (d + ST_COLS - 1) / ST_COLS;
+  const int64_t jtiles = L->row_tiles;
+  int64_t want = g_stream_jsplit > 0 ? g_stream_jsplit : (int64_t)(ST_RESIDENT / (double)(L->row_tiles * L->col_groups));
+  if (want < 1) want = 1;
+  if (want > jtiles) want = jtiles;
+  L->jtiles_per = (jtiles + want - 1) / want;
+  L->jsplit = (jtiles + L->jtiles_per - 1) / L->jtiles_per;
+  L->rows = L->row_tiles * ST_ROWS;
+  L->nk = L->rows;
+  L->dk = (int64_t)st_align((size_t)d, 32);
+  L->dc = (int64_t)st_align((size_t)d, 128);
+  int64_t sqb = (n * d + 1023) / 1024;
+  if (sqb > 1024) sqb = 1024;
+  L->sq_blocks = sqb;
+  size_t at = 0;
+  auto put = [&](size_t bytes) { const size_t o = at; at = st_align(at + bytes, 256); return o; };
+  L->r = put((size_t)L->rows * 4);
+  L->sc = put((size_t)(6 * L->dc + 4) * 4);
+  L->t3 = put((size_t)3 * L->rows * L->dk * 2);
+  L->wt3 = put((size_t)3 * L->dc * L->nk * 2);
+  L->o = put((size_t)L->jsplit * n * d * 4);
+  L->rs = put((size_t)L->jsplit * n * 4);
+  L->sq = put((size_t)sqb * 8);
+  L->total = at;
+  if (L->row_tiles * L->col_groups * L->jsplit > 0x7fffffffll) return fail(STEIN_E_SHAPE, "too many tiles");
+  return STEIN_OK;
+}
+
+extern "C" int stein_debug_stream_jsplit(int jsplit) {
+  if (jsplit < 0) return fail(STEIN_E_BADARG, "jsplit < 0");
+  g_stream_jsplit = jsplit;
+  return STEIN_OK;
+}
+
+extern "C" int stein_stream_workspace_bytes(int64_t n, int64_t d, int dtype, int flags, size_t* out_bytes) {
+  if (!out_bytes) return fail(STEIN_E_BADARG, "out_bytes is NULL");
+  int rc = stream_check_shape(n, d, dtype, flags);
+  if (rc) return rc;
+  StreamLayout L;
+  if ((rc = stream_make_layout(n, d, &L))) return rc;
+  *out_bytes = L.total;
+  return STEIN_OK;
+}
+
+extern "C" int stein_stream_plan(int64_t n, int64_t d, int* row_tiles, int* col_groups, int* jsplit) {
+  if (!row_tiles || !col_groups || !jsplit) return fail(STEIN_E_BADARG, "NULL output");
+  int rc = stream_check_shape(n, d, STEIN_F32, 0);
+  if (rc) return rc;
+  StreamLayout L;
+  if ((rc = stream_make_layout(n, d, &L))) return rc;
+  *row_tiles = (int)L.row_tiles;
+  *col_groups = (int)L.col_groups;
+  *jsplit = (int)L.jsplit;
+  return STEIN_OK;
+}
+
+extern "C" int stein_svgd_phi_stream(const void* theta, const void* score, int64_t n, int64_t d, int dtype,
+                                     const float* h2_in, float* phi, double* sqnorm_out, void* workspace, size_t ws_bytes,
+                                     int flags, void* stream) {
+  if (!theta || !score || !h2_in || !phi || !sqnorm_out || !workspace) return fail(STEIN_E_BADARG, "NULL pointer");
+  if ((uintptr_t)workspace & 15) return fail(STEIN_E_BADARG, "the workspace must be 16-byte aligned");   // (16-byte loads of its sections)
+  int rc = stream_check_shape(n, d, dtype, flags);
+  if (rc) return rc;
+  StreamLayout L;
+  if ((rc = stream_make_layout(n, d, &L))) return rc;
+  if (ws_bytes < L.total) return fail(STEIN_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L.total);
+  if ((rc = stein_take_device_error())) return rc;   // a kernel of an earlier call on this device gave up: say so now
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  // the views the split launchers take: the planes' extents and addresses, nothing else of a stored-D layout
+  StepViews v{};
+  v.L.x3_rows = L.rows; v.L.x3_dk = L.dk; v.L.x3_dc = L.dc; v.L.x3_nk = L.nk;
+  v.r = (float*)(ws + L.r);
+  v.planes = ws;
+  v.T3 = (unsigned short*)(ws + L.t3);
+  v.Gt3 = (unsigned short*)(ws + L.wt3);
+  v.sc = (float*)(ws + L.sc);
+  v.cmax = (u32*)(v.sc + x3_sc_cmax(L.dc));
+  v.two_s = v.sc + x3_sc_two_s(L.dc);
+  float* O = (float*)(ws + L.o);
+  float* RS = (float*)(ws + L.rs);
+  double* SQ = (double*)(ws + L.sq);
+  // 1. row norms (the padding rows of r are never read into a stored result), column maxima -> scales
+  // 2. theta's row-major planes (fold form of the split: no transposed image, the score only feeds the maxima)
+  if ((rc = stein_rownorms(theta, n, d, dtype, v.r, stream))) return rc;
+  const SplitFused only_rows{nullptr, nullptr, 1};
+  if ((rc = stein_x3_split(v, theta, score, dtype, n, d, s, &only_rows))) return rc;
+  // 3. W = G - theta / h2 at the caller's bandwidth
+  if ((rc = stein_x3_split_w(v, (const float*)theta, (const float*)score, n, d, h2_in, s))) return rc;
+  // 4. the streaming contraction
+  const long nblk = (long)(L.row_tiles * L.col_groups * L.jsplit);
+  hipLaunchKernelGGL(k_phi_stream, dim3((unsigned)nblk), dim3(ST_THREADS), 0, s, v.T3, (int)(L.dk / 32), v.Gt3,
+                     (long)(L.nk / 32), v.r, v.sc, (int)L.dc, h2_in, O, RS, (int)n, (int)d, (int)L.row_tiles,
+                     (int)L.col_groups, (int)L.cblocks, (int)L.row_tiles, (int)L.jtiles_per);
+  LAUNCH_CHECK("k_phi_stream");
+  // 5. finish
+  const int vec = d % 4 == 0 && (((uintptr_t)theta | (uintptr_t)phi) & 15) == 0;
+  hipLaunchKernelGGL(k_stream_finish, dim3((unsigned)L.sq_blocks), dim3(256), 0, s, O, RS, (const float*)theta, h2_in, phi,
+                     SQ, (int)n, (int)d, (int)L.jsplit, vec);
+  LAUNCH_CHECK("k_stream_finish");
+  hipLaunchKernelGGL(k_stream_sqsum, dim3(1), dim3(256), 0, s, SQ, (int)L.sq_blocks, sqnorm_out);
+  LAUNCH_CHECK("k_stream_sqsum");
+  return STEIN_OK;
+}

@@ -79,6 +79,11 @@ class HipStages:
         _lib.call_on(T.device, "stein_svgd_phi", _ptr(T), _ptr(G), n, d, 0, n, _dt(T), _ptr(phi), _ptr(h2), _ptr(sqnorm),
                   _ptr(K), _ptr(dK), _ptr(ws), ws.numel(), flags, _stream(T))
 
+    def svgd_phi_stream(self, T, G, n, d, h2, phi, sqnorm, ws):
+        """the streaming step at the bandwidth^2 held by the 1-element device tensor h2 (include/steinhip.h)"""
+        _lib.call_on(T.device, "stein_svgd_phi_stream", _ptr(T), _ptr(G), n, d, _dt(T), _ptr(h2), _ptr(phi), _ptr(sqnorm),
+                     _ptr(ws), ws.numel(), 0, _stream(T))
+
     def x3_prepare(self, T, G, n, d, planes):
         """T or G may be None: only the other matrix's scales and planes are rebuilt."""
         ref = T if T is not None else G
@@ -196,12 +201,24 @@ class SvgdEngine:
               on its own RCCL communicator, the whole step one C call (stein_rank_step; 68 us of host time per step
               against ~190).  Native is opt-in until a run on two or more GPUs has passed bench.py's native-vs-torch
               cross-check: so far it has only ever seen one-rank groups, where every collective is a self-copy.
+    h2      : None (default): the bandwidth is the median heuristic's, taken from all n^2 distances in every step, and
+              nothing here changes.  Otherwise the SQUARED bandwidth is the caller's and the engine takes the streaming
+              step (stein_svgd_phi_stream): no median, no n x n distance image, a workspace of O(n d) bytes.  A positive
+              finite float is stored once in a 1-element device tensor; a 1-element float32 device tensor is used as it
+              is -- the library reads it on the device in every step, so the caller may rewrite it in place between steps
+              (an annealing schedule) or hand over another engine's `h2` (a median refreshed every k-th step and held in
+              between).  Either way `self.h2` is that tensor.  fp32 inputs on the split path, one rank; K_out, dK_out,
+              dist_matrix(), ksd, mark= and group= are refused with a ValueError.
     """
 
     def __init__(self, n, d, device="cuda", group=None, stages=None, x3=None, dtype=torch.float32, small=True,
                  window=True, force_collectives=False, comm="auto", tile_distance=False, dist_window=None, ksd=False,
-                 fold=None):
+                 fold=None, h2=None):
         self.n, self.d = int(n), int(d)
+        self.streaming = h2 is not None
+        if self.streaming:
+            self._init_stream(h2, device, group, stages, x3, dtype, ksd)
+            return
         # dtype of the theta / score tensors handed to compute_phi: float32, or bfloat16 (BASELINE config 2: the
         # values are used as they are, K is rounded to bf16, one bf16 MFMA per product, fp32 accumulation)
         if dtype not in (torch.float32, torch.bfloat16):
@@ -307,6 +324,57 @@ class SvgdEngine:
                 raise RuntimeError("comm='native': " + self.comm_error)
         self.comm = "native" if self._comm is not None else ("torch" if self.sharded else None)
 
+    def _init_stream(self, h2, device, group, stages, x3, dtype, ksd):
+        """The engine of the streaming step (h2 given): what it cannot do is refused here, by name."""
+        if group is not None:
+            raise ValueError("h2=: the streaming step runs on one rank; group= is not supported with a supplied bandwidth")
+        if dtype != torch.float32:
+            raise ValueError("h2=: the streaming step takes float32 inputs; bf16 is not supported with a supplied bandwidth")
+        if x3 is not None and not x3:
+            raise ValueError("h2=: the streaming step only exists on the split path; x3=False is not supported")
+        if ksd:
+            raise ValueError("h2=: ksd=True is not supported (the Stein discrepancy at a supplied bandwidth needs K.theta)")
+        self.device = torch.device(device)
+        if isinstance(h2, torch.Tensor):
+            if h2.numel() != 1 or h2.dtype != torch.float32 or h2.device.type != self.device.type or \
+                    (self.device.index is not None and h2.device.index != self.device.index):
+                raise ValueError("h2 must be a positive finite float or a 1-element float32 tensor on %s, got %s %s on %s" %
+                                 (self.device, tuple(h2.shape), h2.dtype, h2.device))
+            self.h2 = h2       # read on the device in every step: never copied, never checked (that would synchronise)
+        else:
+            import math
+            try:
+                value = float(h2)
+            except (TypeError, ValueError):
+                raise ValueError("h2 must be a positive finite float or a 1-element float32 device tensor, got %r" % (h2,))
+            if not math.isfinite(value) or value <= 0.0:
+                raise ValueError("h2 (the squared bandwidth) must be positive and finite, got %r" % (h2,))
+            self.h2 = torch.full((1,), value, dtype=torch.float32, device=self.device)
+        if self.n < 1 or self.d < 1:
+            raise ValueError("need n >= 1 and d >= 1, got n = %d, d = %d" % (self.n, self.d))
+        self.dtype, self.x3, self.ksd, self.fold = torch.float32, True, False, False
+        self.flags = 0
+        self.stages = stages if stages is not None else HipStages()
+        if not hasattr(self.stages, "svgd_phi_stream"):
+            raise ValueError("h2=: the stages have no streaming step (HipStages has)")
+        self.group, self.world, self.rank, self.sharded = None, 1, 0, False
+        self.n_local, self.row0 = self.n, 0
+        self.comm, self._comm, self.comm_error = None, None, None
+        self.dist_window, self.window_hit = False, None
+        self._ksd_ready = False
+        self._have_dist, self._one_kernel, self.dist_upper = False, False, False
+        self.row_tiles, self.col_groups, self.jsplit = _lib.stream_plan(self.n, self.d)
+        self.ws_bytes = _lib.stream_workspace_bytes(self.n, self.d)
+        dev = self.device
+        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)   # nothing in it is read before it is written
+        self.phi = torch.empty(self.n, self.d, dtype=torch.float32, device=dev)
+        self._sums = torch.zeros(3, dtype=torch.float64, device=dev)
+        self.sqnorm = self._sums[:1]
+        # what the stored-D engine has and this one does not: named, so that a stray use fails on None and not on a
+        # missing attribute (the workspace views refuse with a ValueError: _section)
+        self._offs, self.ld_dist, self.split, self.median = None, 0, 0, None
+        self._flags_host, self._flags_event = None, None
+
     def _make_native_comm(self):
         """Group rank 0 makes the 128-byte RCCL id, the group broadcasts it, every rank joins -- collective, and
         collective in failure too: every rank takes part in the same two torch collectives whatever happens to it, so
@@ -356,6 +424,9 @@ class SvgdEngine:
 
     # views into the workspace -------------------------------------------------------------
     def _section(self, sec, nbytes, dtype):
+        if self.streaming:
+            raise ValueError("h2=: the streaming step's workspace has no sections of the stored-D layout (row norms, distance "
+                             "image, histograms, select state, planes); use an engine without a supplied bandwidth")
         o = self._offs[sec]
         return self.ws[o:o + nbytes].view(dtype)
 
@@ -373,6 +444,9 @@ class SvgdEngine:
     def dist_matrix(self):
         """Row-major [n_local, n] copy of the distance block (de-tiled; for inspection and tests).  After a single-rank
         step on the split path only the tiles on and above the diagonal are stored; the rest is mirrored in here."""
+        if self.streaming:
+            raise ValueError("h2=: the streaming step never stores the distance matrix; dist_matrix() needs an engine "
+                             "without a supplied bandwidth")
         if not self._have_dist:
             raise RuntimeError("no distance image: this engine's fused call takes the one-kernel path (n <= 160), which "
                                "keeps D in LDS; build the engine with small=False to get one")
@@ -400,12 +474,14 @@ class SvgdEngine:
 
     @property
     def spec_section(self):
+        self._section(_lib.WS_SPEC, 0, torch.uint8)      # (refuses on a streaming engine)
         o = self._offs[_lib.WS_SPEC]
         return self.ws[o:self._offs[_lib.WS_PLANES]]
 
     @property
     def spec_table(self):
         """the rank-summed window table (int64 view), behind the slots and the entry buffer of the SPEC section"""
+        self._section(_lib.WS_SPEC, 0, torch.uint8)      # (refuses on a streaming engine)
         o = self._offs[_lib.WS_SPEC] + 8 * _lib.SPEC_TABLE_OFFSET_WORDS
         return self.ws[o:o + 8 * _lib.SPEC_TABLE_WORDS].view(torch.int64)
 
@@ -414,6 +490,7 @@ class SvgdEngine:
         """split-precision operand planes and scales (None unless x3)"""
         if not self.x3:
             return None
+        self._section(_lib.WS_PLANES, 0, torch.uint8)    # (refuses on a streaming engine)
         o = self._offs[_lib.WS_PLANES]
         return self.ws[o:self.ws_bytes]
 
@@ -535,6 +612,17 @@ class SvgdEngine:
         sharded step with K_out) do not compute them and are refused.
         """
         st, n, d, nl = self.stages, self.n, self.d, self.n_local
+        if self.streaming:
+            if K_out is not None or dK_out is not None:
+                raise ValueError("h2=: the streaming step forms neither K nor dK; K_out / dK_out are not supported")
+            if mark is not None or timing:
+                raise ValueError("h2=: the streaming step is one call; mark= / timing= are not supported")
+            for name, t in (("theta", theta_local), ("score", score_local)):
+                if tuple(t.shape) != (n, d) or t.dtype != torch.float32 or not t.is_contiguous():
+                    raise ValueError("%s must be a contiguous torch.float32 [%d, %d] tensor, got %s %s" %
+                                     (name, n, d, tuple(t.shape), t.dtype))
+            st.svgd_phi_stream(theta_local, score_local, n, d, self.h2, self.phi, self.sqnorm, self.ws)
+            return self.phi
         if self.ksd and (mark is not None or (self.sharded and K_out is not None)):
             raise ValueError("ksd=True: the staged calls (mark=, or K_out on a sharded engine) do not compute the Stein "
                              "discrepancy; use the fused call / rank segments")

@@ -28,7 +28,7 @@ class AbstractSteinSampler:
     INIT_SCALE = 0.01  # abstract_stein_sampler.py:72
 
     def __init__(self, n_particles, log_p, theta=None, *, model_vars=None, device="cuda", dtype=torch.float32,
-                 group=None, seed=None, kernel_dtype=torch.float32, x3=None, ksd=False):
+                 group=None, seed=None, kernel_dtype=torch.float32, x3=None, ksd=False, bandwidth=None, h2=None):
         """
         n_particles : total number of particles n (across all ranks).
         log_p       : see SteinSampler.
@@ -43,6 +43,11 @@ class AbstractSteinSampler:
                       are fed to the kernel / contraction (the reference rounds fp64 -> fp32 at that point).
         x3          : None (default: split-fp16 GEMMs on the 16-bit matrix cores) / False (fp32-input MFMA GEMMs); see engine.SvgdEngine.
         ksd         : also compute the kernelized Stein discrepancy in every step (stein_discrepancy()); see engine.SvgdEngine.
+        bandwidth   : None (default): the median heuristic, every step.  A positive finite float h -- the reference's
+                      ``kernel.bandwidth`` quantity, K = exp(-D / (2 h^2)) -- fixes the kernel instead: every step then takes
+                      the streaming path (no median, no n x n workspace; see engine.SvgdEngine, h2=).
+        h2          : the device form of the same: a 1-element float32 device tensor holding h^2, read on the device in every
+                      step, which the caller may rewrite in place (annealing).  Give one of bandwidth / h2, not both.
         """
         self.n_particles = int(n_particles)
         self.log_p = log_p
@@ -105,8 +110,19 @@ class AbstractSteinSampler:
         self.theta_matrix = packed.to(device=self.device, dtype=dtype).contiguous()
         self.n_params = self.theta_matrix.shape[1]
         self.kernel_dtype = kernel_dtype
+        if bandwidth is not None:
+            if h2 is not None:
+                raise ValueError("give bandwidth= (a float h) or h2= (a device tensor holding h^2), not both")
+            import math
+            try:
+                h = float(bandwidth)
+            except (TypeError, ValueError):
+                raise ValueError("bandwidth must be a positive finite float, got %r" % (bandwidth,))
+            if not math.isfinite(h) or h <= 0.0:
+                raise ValueError("bandwidth must be positive and finite, got %r" % (bandwidth,))
+            h2 = h * h
         self.engine = SvgdEngine(self.n_particles, self.n_params, device=self.device, group=group, x3=x3,
-                                 dtype=kernel_dtype, ksd=ksd)
+                                 dtype=kernel_dtype, ksd=ksd, h2=h2)
         self._theta32 = (self.theta_matrix if dtype == kernel_dtype else
                          torch.empty(self.n_local, self.n_params, dtype=kernel_dtype, device=self.device))
 
