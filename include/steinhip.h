@@ -206,6 +206,37 @@ int stein_svgd_phi_stream(const void* theta, const void* score, int64_t n, int64
                           void* workspace, size_t ws_bytes, int flags, void* stream);
 int stein_debug_stream_jsplit(int jsplit);
 
+/* ---- streaming median: the median-heuristic bandwidth in the streaming step's workspace -----------------------------
+ * h2 = median(D) / ln n over all n^2 squared distances (compute_median.py:12-15, abstract_kernel.py:40), exact, without
+ * the n x n image: the 3-level radix select of the other paths (11 + 11 + 10 key bits) with the 128 x 128 distance tiles
+ * recomputed once per level and counted straight from the matrix-core accumulators (k_stream_hist, stein_stream.hip).
+ * The tiles run the distance code of stein_svgd_phi_stream on the same row norms, scales and planes, so the median is
+ * that of the D values the step exponentiates; the final arithmetic (median_bandwidth) is every other path's.
+ * Chain, all on `stream`, no host read: row norms; theta's scales and row-major planes; select state and histograms
+ * zeroed; per level one histogram launch and one resolve.
+ *   theta      : [n][d] float (STEIN_F32; STEIN_BF16 returns STEIN_E_UNSUPPORTED)
+ *   h2_out     : DEVICE float[1];  median_out: DEVICE float[1] or NULL
+ *   flags      : must be 0.  n >= 2 (n = 1: STEIN_E_SHAPE, ln 1 = 0), d >= 1 (any d: the k loop covers ceil(d / 32) tiles)
+ * The workspace must be 16-byte aligned; it carries nothing between calls and its contents on entry do not matter.
+ *   stein_stream_median_workspace_bytes = 4 N + 4 (6 dc + 4) + 6 N dk (each rounded up to 256, as above) + 98304 + 256
+ *   (row norms | scales | theta's planes at the streaming step's own offsets, then 3 x 2 x 2048 u64 histograms and the
+ *   64-byte select state where the step keeps W's planes).  It is never larger than stein_stream_workspace_bytes(n, d):
+ *   one buffer serves stein_stream_median and then stein_svgd_phi_stream, h2_out handed over as h2_in; the step rebuilds
+ *   its planes itself.
+ * Counts are integers added with 64-bit atomics: the result does not depend on the grid and a repeated call is
+ * bit-identical.  Grid: min(tiles, 2 x 256) workgroups, tiles = nt (nt + 1) / 2, nt = ceil(n / 128) (two 512-thread
+ * workgroups fit a CU; 256 = the MI355X's CU count, a constant as in stein_stream_plan).
+ * stein_stream_median_plan (host arithmetic): byte offsets of the histograms and of the select state inside the
+ * workspace (lo and hi are the floats at state_offset + 40 and + 44), the number of tiles and the grid.
+ * stein_debug_stream_median_grid(k) (test hook, per calling thread): k > 0 launches exactly k workgroups, 0 restores the
+ * rule. */
+int stein_stream_median_workspace_bytes(int64_t n, int64_t d, int dtype, int flags, size_t* out_bytes);
+int stein_stream_median_plan(int64_t n, int64_t d, size_t* hist_offset, size_t* state_offset, int64_t* tiles, int* blocks);
+int stein_stream_median(const void* theta, int64_t n, int64_t d, int dtype,
+                        float* h2_out, float* median_out /* may be NULL */,
+                        void* workspace, size_t ws_bytes, int flags, void* stream);
+int stein_debug_stream_median_grid(int blocks);   /* test hook, per calling thread; 0 = default */
+
 /* ---- staged path (tests, multi-rank: the host puts collectives between the stages) ------------ */
 
 /* r_i = sum_k theta_ik^2            abstract_kernel.py:34 */

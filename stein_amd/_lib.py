@@ -74,6 +74,10 @@ _SIGNATURES = {
     "stein_stream_plan": [_i64, _i64, _c.POINTER(_int), _c.POINTER(_int), _c.POINTER(_int)],
     "stein_svgd_phi_stream": [_vp, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _sz, _int, _vp],
     "stein_debug_stream_jsplit": [_int],
+    "stein_stream_median_workspace_bytes": [_i64, _i64, _int, _int, _c.POINTER(_sz)],
+    "stein_stream_median_plan": [_i64, _i64, _c.POINTER(_sz), _c.POINTER(_sz), _c.POINTER(_i64), _c.POINTER(_int)],
+    "stein_stream_median": [_vp, _i64, _i64, _int, _vp, _vp, _vp, _sz, _int, _vp],
+    "stein_debug_stream_median_grid": [_int],
     "stein_rownorms": [_vp, _i64, _i64, _int, _vp, _vp],
     "stein_distance_block": [_vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _i64, _vp, _vp, _int, _vp],
     "stein_x3_prepare": [_vp, _vp, _i64, _i64, _int, _vp, _sz, _vp],
@@ -184,6 +188,26 @@ def stream_plan(n, d):
 def debug_stream_jsplit(jsplit):
     """Test hook (per calling thread): j ranges the streaming step's plan asks for; 0 restores the plan's own rule."""
     call("stein_debug_stream_jsplit", int(jsplit))
+
+
+def stream_median_workspace_bytes(n, d, dtype=F32, flags=0):
+    """Workspace bytes of the streaming median (stein_stream_median): never more than stream_workspace_bytes.  Host arithmetic."""
+    total = _sz(0)
+    call("stein_stream_median_workspace_bytes", n, d, dtype, flags, ctypes.byref(total))
+    return int(total.value)
+
+
+def stream_median_plan(n, d):
+    """-> (byte offset of the [3][2][2048] int64 histograms, byte offset of the 64-byte select state, tiles, workgroups)
+    of the streaming median inside its workspace.  Host arithmetic."""
+    ho, so, tiles, blocks = _sz(0), _sz(0), _i64(0), _int(0)
+    call("stein_stream_median_plan", n, d, ctypes.byref(ho), ctypes.byref(so), ctypes.byref(tiles), ctypes.byref(blocks))
+    return int(ho.value), int(so.value), int(tiles.value), int(blocks.value)
+
+
+def debug_stream_median_grid(blocks):
+    """Test hook (per calling thread): workgroups of the streaming median's histogram launches; 0 restores the rule."""
+    call("stein_debug_stream_median_grid", int(blocks))
 
 
 def version():

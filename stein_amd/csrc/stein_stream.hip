@@ -25,6 +25,15 @@
 // argument.  The partial sums of the j ranges go to [jsplit][n][d] / [jsplit][n] and are added in range order by the finish
 // pass: no float atomics, a repeated call is bit-identical.
 // Resources (hipcc, gfx950): recorded in DESIGN.md, "streaming step".
+//
+// The streaming median (stein_stream_median): the exact median-heuristic bandwidth of the same particles in the same O(n d)
+// workspace.  The n^2 distances are never stored: the 3-level radix select of stein_select.hip (11 + 11 + 10 key bits)
+// recomputes the distance tiles once per level and counts them straight from the MFMA accumulators.
+//   stein_rownorms, k_colmax, k_make_scales, k_split (theta, row-major image only)   as in the step: the same r, T3, two_s
+//   k_sel_init, then per level:  k_stream_hist<LEVEL>  distance tile -> digit of LEVEL -> LDS histogram -> one flush
+//                                k_resolve             (stein_select.hip) -> prefixes; level 2: lo, hi, median, h2
+// k_stream_hist runs the distance phase of k_phi_stream (st_distance_tile below, one body for both), so the median is the
+// median of the D values the step exponentiates.
 
 #include "stein_x3.h"
 
@@ -59,6 +68,34 @@ __device__ __forceinline__ float st_resid_hi(u32 h, float x) {
   float r;
   asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(x));
   return r;
+}
+
+// The distance phase of one 128 x 128 tile, shared by k_phi_stream and k_stream_hist (one body: both kernels form every
+// S value in the same order, so the streaming median is the median of the very D values the step exponentiates).  Wave
+// (wr, wc) of eight: s[jb][ib] = the 16 x 16 block S^T[j = 64 wc + 16 jb ..][i = 32 wr + 16 ib ..] over all ntk k tiles;
+// ta / tb: this lane's 16 bytes of the first fragment of the row tile's rows 32 wr.. and of the column tile's rows 64 wc..
+__device__ __forceinline__ void st_distance_tile(const u16* __restrict__ ta, const u16* __restrict__ tb, int ntk,
+                                                 f32x4 (&s)[4][2]) {
+#pragma unroll
+  for (int jb = 0; jb < 4; ++jb)
+#pragma unroll
+    for (int ib = 0; ib < 2; ++ib) s[jb][ib] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int kt = 0; kt < ntk; ++kt) {
+    u32x4 fa[2][3], fb[4][3];
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+#pragma unroll
+      for (int ib = 0; ib < 2; ++ib)
+        fa[ib][p] = *reinterpret_cast<const u32x4*>(ta + ((size_t)kt * 3 + p) * XTILE_E + ib * 512);
+#pragma unroll
+      for (int jb = 0; jb < 4; ++jb)
+        fb[jb][p] = *reinterpret_cast<const u32x4*>(tb + ((size_t)kt * 3 + p) * XTILE_E + jb * 512);
+    }
+#pragma unroll
+    for (int jb = 0; jb < 4; ++jb)
+#pragma unroll
+      for (int ib = 0; ib < 2; ++ib) s[jb][ib] = x3_products16<2>(fb[jb], fa[ib], s[jb][ib]);
+  }
 }
 
 __global__ __launch_bounds__(ST_THREADS) void k_phi_stream(const u16* __restrict__ T3, int ntk, const u16* __restrict__ Wt3,
@@ -110,27 +147,8 @@ __global__ __launch_bounds__(ST_THREADS) void k_phi_stream(const u16* __restrict
     const int j0 = jt * ST_JT;
     // ---- distance: S^T block [4 j blocks][2 i blocks] of this wave
     f32x4 s[4][2];
-#pragma unroll
-    for (int jb = 0; jb < 4; ++jb)
-#pragma unroll
-      for (int ib = 0; ib < 2; ++ib) s[jb][ib] = f32x4{0.f, 0.f, 0.f, 0.f};
     const u16* __restrict__ tb = T3 + (size_t)jt * ntk * 3 * XTILE_E + (wc * 4) * 512 + lane * 8;
-    for (int kt = 0; kt < ntk; ++kt) {
-      u32x4 fa[2][3], fb[4][3];
-#pragma unroll
-      for (int p = 0; p < 2; ++p) {
-#pragma unroll
-        for (int ib = 0; ib < 2; ++ib)
-          fa[ib][p] = *reinterpret_cast<const u32x4*>(ta + ((size_t)kt * 3 + p) * XTILE_E + ib * 512);
-#pragma unroll
-        for (int jb = 0; jb < 4; ++jb)
-          fb[jb][p] = *reinterpret_cast<const u32x4*>(tb + ((size_t)kt * 3 + p) * XTILE_E + jb * 512);
-      }
-#pragma unroll
-      for (int jb = 0; jb < 4; ++jb)
-#pragma unroll
-        for (int ib = 0; ib < 2; ++ib) s[jb][ib] = x3_products16<2>(fb[jb], fa[ib], s[jb][ib]);
-    }
+    st_distance_tile(ta, tb, ntk, s);
     // ---- exp, split, stage: lane holds S^T[j = 16 jb + 4 lq + e][i = 16 ib + l15]
 #pragma unroll
     for (int jb = 0; jb < 4; ++jb) {
@@ -211,6 +229,110 @@ __global__ __launch_bounds__(ST_THREADS) void k_phi_stream(const u16* __restrict
     const int row = i0 + t;
     if (t < ST_ROWS && row < n) RS[(size_t)z * n + row] = (red[t] + red[ST_ROWS + t]) * sc[4 * dc + 2];
   }
+}
+
+// ================================================================================================
+// the streaming median: radix-select histograms straight from the distance tiles
+// ================================================================================================
+// One level's digits of one wave's share (32 rows x 64 columns) of tile (ti, tj), tj >= ti, into the LDS histogram
+// h[2][STEIN_HIST_BINS]: the semantics of hist_pass_body<LEVEL, true> (stein_select.hip).  PRED = false: an off-diagonal
+// tile that lies inside the matrix -- every entry stands for itself and its mirror image (weight 2), no per-entry test.
+// PRED = true (diagonal and edge tiles): col > row weighs 2, col == row 1, col < row and everything >= n is skipped.
+// Level 0 sees every entry and a handful of bins take them all: the wave-merged hist_add (every lane of the wave gets
+// here: the branches around the call are workgroup-uniform).  Levels 1 and 2 see the entries under the prefixes only.
+template <int LEVEL, bool PRED>
+__device__ __forceinline__ void sh_count(const f32x4 (&s)[4][2], const float (&ri)[2], const float* __restrict__ r, float two_s,
+                                         int row0 /* of this lane: + 16 ib */, int col0 /* of this lane: + 16 jb + e */, int n,
+                                         u32* h, u32 pa, u32 pb, bool two, int lane) {
+#pragma unroll
+  for (int jb = 0; jb < 4; ++jb) {
+    const int c4 = col0 + jb * 16;
+    const float4 rj4 = *reinterpret_cast<const float4*>(r + c4);   // (r is padded to the tiles; columns >= n are not counted)
+    const float rj[4] = {rj4.x, rj4.y, rj4.z, rj4.w};
+#pragma unroll
+    for (int ib = 0; ib < 2; ++ib) {
+      const int row = row0 + ib * 16;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int col = c4 + e;
+        const float dv = (ri[ib] + rj[e]) - two_s * s[jb][ib][e];   // k_phi_stream's expression, term for term
+        const u32 key = f32_key(dv);
+        const bool inb = !PRED || (row < n && col < n && col >= row);
+        const bool dg = PRED && col == row;
+        if (LEVEL == 0) {
+          hist_add(h, key >> 21, inb && !dg, lane, 2u);
+          if (PRED && inb && dg) atomicAdd(&h[key >> 21], 1u);
+        } else {
+          const u32 digit = LEVEL == 1 ? ((key >> 10) & 2047u) : (key & 1023u);
+          const u32 hi = LEVEL == 1 ? (key >> 21) : (key >> 10);
+          const u32 w = dg ? 1u : 2u;
+          if (inb && hi == pa) atomicAdd(&h[digit], w);
+          if (two && inb && hi == pb) atomicAdd(&h[STEIN_HIST_BINS + digit], w);
+        }
+      }
+    }
+  }
+}
+
+// A workgroup (512 threads, k_phi_stream's distance roles) owns tiles u = logical id, + grid, + 2 grid, ... of the
+// nt (nt + 1) / 2 tiles (ti, tj >= ti) of the symmetric matrix -- useful tiles only, in folded-row order: virtual row v is
+// row v (nt - v tiles) followed by row nt - 1 - v (v + 1 tiles), nt + 1 tiles whatever v, and the middle row of an odd nt
+// comes last by itself.  Consecutive u share a row tile, and consecutive logical ids an XCD (xcd_remap): the row tile's
+// fragments stay in that L2.
+// Counts are integers: the u64 adds of the flush commute, so the histogram does not depend on the grid or on the order of
+// the workgroups, and a repeated call is bit-identical.  The LDS counters are 32-bit and one tile adds at most
+// 128 x 128 x 2 = 32768 to one bin: after flush_tiles <= 65536 tiles (65536 x 32768 = 2^31 < 2^32) the histogram is
+// flushed and zeroed again; a workgroup with fewer tiles than that flushes once, at the end.
+// Plain C++ loads; no workgroup waits for another; every loop bound is an argument.
+constexpr int SH_FLUSH_TILES = 65536;
+template <int LEVEL>
+__global__ __launch_bounds__(ST_THREADS) void k_stream_hist(const u16* __restrict__ T3, int ntk, const float* __restrict__ r,
+                                                            const float* __restrict__ sc, int dc,
+                                                            const SelState* __restrict__ st, u64* __restrict__ hist, int n,
+                                                            int nt, long tiles, int flush_tiles) {
+  __shared__ u32 h[2 * STEIN_HIST_BINS];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int l15 = lane & 15, lq = lane >> 4;
+  const int wr = w >> 1, wc = w & 1;   // rows [32 wr, 32 wr + 32) x columns [64 wc, 64 wc + 64) of the tile
+  const u32 pa = st->prefix[0], pb = st->prefix[1];
+  const bool two = LEVEL > 0 && st->diverged != 0u;
+  const int nbins = (two ? 2 : 1) * STEIN_HIST_BINS;
+  for (int b = t; b < 2 * STEIN_HIST_BINS; b += ST_THREADS) h[b] = 0u;
+  __syncthreads();
+  const float two_s = sc[4 * dc + 1];
+  const long paired = (long)(nt >> 1) * (nt + 1);
+  int since = 0;
+  for (long u = xcd_remap(blockIdx.x, gridDim.x); u < tiles; u += gridDim.x) {
+    int ti, tj;
+    if (u < paired) {
+      const int v = (int)(u / (nt + 1)), x = (int)(u - (long)v * (nt + 1)), len0 = nt - v;
+      if (x < len0) { ti = v; tj = v + x; }
+      else { ti = nt - 1 - v; tj = ti + (x - len0); }
+    } else {
+      ti = nt >> 1;
+      tj = ti + (int)(u - paired);
+    }
+    const int row0 = ti * ST_ROWS + wr * 32 + l15, col0 = tj * ST_JT + wc * 64 + 4 * lq;
+    float ri[2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a) ri[a] = r[row0 + a * 16];   // (padded to the row tiles; rows >= n are not counted)
+    const u16* __restrict__ ta = T3 + (size_t)ti * ntk * 3 * XTILE_E + (wr * 2) * 512 + lane * 8;
+    const u16* __restrict__ tb = T3 + (size_t)tj * ntk * 3 * XTILE_E + (wc * 4) * 512 + lane * 8;
+    f32x4 s[4][2];
+    st_distance_tile(ta, tb, ntk, s);
+    if (ti != tj && tj * ST_JT + ST_JT <= n) sh_count<LEVEL, false>(s, ri, r, two_s, row0, col0, n, h, pa, pb, two, lane);
+    else sh_count<LEVEL, true>(s, ri, r, two_s, row0, col0, n, h, pa, pb, two, lane);
+    if (++since == flush_tiles) {   // (workgroup-uniform)
+      since = 0;
+      __syncthreads();
+      for (int b = t; b < nbins; b += ST_THREADS)
+        if (h[b]) { atomicAdd(&hist[b], (u64)h[b]); h[b] = 0u; }
+      __syncthreads();
+    }
+  }
+  __syncthreads();
+  for (int b = t; b < nbins; b += ST_THREADS)
+    if (h[b]) atomicAdd(&hist[b], (u64)h[b]);
 }
 
 // phi = (sum_z O_z + (sum_z RS_z) theta / h2) / n (the folded finish of k_phi_finish, steinhip.hip) and this workgroup's
@@ -405,4 +527,114 @@ extern "C" int stein_svgd_phi_stream(const void* theta, const void* score, int64
   hipLaunchKernelGGL(k_stream_sqsum, dim3(1), dim3(256), 0, s, SQ, (int)L.sq_blocks, sqnorm_out);
   LAUNCH_CHECK("k_stream_sqsum");
   return STEIN_OK;
+}
+
+// ---- the streaming median -------------------------------------------------------------------------------------------
+// Workspace: a prefix-compatible subset of StreamLayout.  Row norms, scales and theta's planes sit at the step's own offsets
+// (none of them depends on the j split); the three histograms (96 KiB) start where the step keeps W's planes, the select
+// state (64 bytes, its own 256) behind them.  W's planes are at least 3 x 128 x 128 x 2 = 96 KiB and the step has three more
+// sections of at least 256 bytes behind them, so this layout never reaches past the step's: one buffer serves both calls
+// back to back (at the smallest shapes the select state lies in the step's partial-sum area, not in W's planes).
+static thread_local int g_stream_median_grid = 0;   // stein_debug_stream_median_grid: 0 = the rule below
+// Workgroups per CU the grid is sized for.  k_stream_hist: 90-92 VGPRs (96 allocated), 16 KB of LDS, 8 waves -> the register file
+// holds five waves per SIMD, i.e. two whole workgroups (two waves per SIMD each) per CU ("streaming median"); tiles cost the same, so a grid of
+// exactly the resident workgroups with strided shares is balanced to within one tile.
+constexpr int SH_WG_PER_CU = 2;
+constexpr size_t SH_HIST_BYTES = (size_t)STEIN_HIST_LEVELS * 2 * STEIN_HIST_BINS * 8;
+
+struct StreamMedianLayout {
+  StreamLayout L;            // r, sc, t3 and the planes' extents
+  size_t hist, sel, total;
+  int64_t tiles, blocks;
+};
+
+static int stream_median_make_layout(int64_t n, int64_t d, int dtype, int flags, StreamMedianLayout* M) {
+  int rc = stream_check_shape(n, d, dtype, flags);
+  if (rc) return rc;
+  if (n < 2) return fail(STEIN_E_SHAPE, "n = %lld: the median-heuristic bandwidth divides by ln n; need n >= 2", (long long)n);
+  if ((rc = stream_make_layout(n, d, &M->L))) return rc;
+  M->hist = M->L.wt3;
+  M->sel = M->hist + st_align(SH_HIST_BYTES, 256);
+  M->total = M->sel + 256;
+  const int64_t nt = M->L.row_tiles;
+  M->tiles = nt * (nt + 1) / 2;
+  const int64_t want = g_stream_median_grid > 0 ? g_stream_median_grid : (int64_t)SH_WG_PER_CU * (int64_t)ST_RESIDENT;
+  M->blocks = g_stream_median_grid > 0 ? want : (M->tiles < want ? M->tiles : want);
+  return STEIN_OK;
+}
+
+extern "C" int stein_debug_stream_median_grid(int blocks) {
+  if (blocks < 0 || blocks > 65535) return fail(STEIN_E_BADARG, "blocks %d", blocks);
+  g_stream_median_grid = blocks;
+  return STEIN_OK;
+}
+
+extern "C" int stein_stream_median_workspace_bytes(int64_t n, int64_t d, int dtype, int flags, size_t* out_bytes) {
+  if (!out_bytes) return fail(STEIN_E_BADARG, "out_bytes is NULL");
+  StreamMedianLayout M;
+  if (int rc = stream_median_make_layout(n, d, dtype, flags, &M)) return rc;
+  *out_bytes = M.total;
+  return STEIN_OK;
+}
+
+extern "C" int stein_stream_median_plan(int64_t n, int64_t d, size_t* hist_offset, size_t* state_offset, int64_t* tiles,
+                                        int* blocks) {
+  if (!hist_offset || !state_offset || !tiles || !blocks) return fail(STEIN_E_BADARG, "NULL output");
+  StreamMedianLayout M;
+  if (int rc = stream_median_make_layout(n, d, STEIN_F32, 0, &M)) return rc;
+  *hist_offset = M.hist;
+  *state_offset = M.sel;
+  *tiles = M.tiles;
+  *blocks = (int)M.blocks;
+  return STEIN_OK;
+}
+
+template <int LEVEL>
+static void launch_stream_hist(const StreamMedianLayout& M, const StepViews& v, const SelState* st, u64* hist, int64_t n,
+                               hipStream_t s) {
+  hipLaunchKernelGGL((k_stream_hist<LEVEL>), dim3((unsigned)M.blocks), dim3(ST_THREADS), 0, s, v.T3, (int)(M.L.dk / 32), v.r,
+                     v.sc, (int)M.L.dc, st, hist + (size_t)LEVEL * 2 * STEIN_HIST_BINS, (int)n, (int)M.L.row_tiles,
+                     (long)M.tiles, SH_FLUSH_TILES);
+}
+
+extern "C" int stein_stream_median(const void* theta, int64_t n, int64_t d, int dtype, float* h2_out, float* median_out,
+                                   void* workspace, size_t ws_bytes, int flags, void* stream) {
+  if (!theta || !h2_out || !workspace) return fail(STEIN_E_BADARG, "NULL pointer");
+  if ((uintptr_t)workspace & 15) return fail(STEIN_E_BADARG, "the workspace must be 16-byte aligned");
+  StreamMedianLayout M;
+  int rc = stream_median_make_layout(n, d, dtype, flags, &M);
+  if (rc) return rc;
+  const StreamLayout& L = M.L;
+  if (ws_bytes < M.total) return fail(STEIN_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, M.total);
+  if ((rc = stein_take_device_error())) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  StepViews v{};
+  v.L.x3_rows = L.rows; v.L.x3_dk = L.dk; v.L.x3_dc = L.dc; v.L.x3_nk = L.nk;
+  v.r = (float*)(ws + L.r);
+  v.planes = ws;
+  v.T3 = (unsigned short*)(ws + L.t3);
+  v.sc = (float*)(ws + L.sc);
+  v.cmax = (u32*)(v.sc + x3_sc_cmax(L.dc));
+  v.two_s = v.sc + x3_sc_two_s(L.dc);
+  u64* hist = (u64*)(ws + M.hist);
+  SelState* sel = (SelState*)(ws + M.sel);
+  // 1. row norms; 2. theta's scales and row-major planes, as the step builds them.  There is no score: the split takes a
+  // NULL score as "leave that half of the column maxima alone", and k_make_scales reads both halves -- the score's only
+  // feed scales this call never uses, but they are zeroed here so that nothing reads what the workspace held.
+  if ((rc = stein_rownorms(theta, n, d, dtype, v.r, stream))) return rc;
+  HIP_TRY(hipMemsetAsync(v.cmax, 0, (size_t)L.dc * sizeof(u32), s));
+  const SplitFused only_rows{nullptr, nullptr, 1};
+  if ((rc = stein_x3_split(v, theta, nullptr, dtype, n, d, s, &only_rows))) return rc;
+  // 3. select state for n^2 entries, histograms zeroed; 4. three levels, k_resolve between them
+  if ((rc = stein_median_begin(hist, sel, n * n, stream))) return rc;
+  launch_stream_hist<0>(M, v, sel, hist, n, s);
+  LAUNCH_CHECK("k_stream_hist<0>");
+  if ((rc = stein_median_resolve(hist, 0, n, sel, h2_out, median_out, stream))) return rc;
+  launch_stream_hist<1>(M, v, sel, hist, n, s);
+  LAUNCH_CHECK("k_stream_hist<1>");
+  if ((rc = stein_median_resolve(hist, 1, n, sel, h2_out, median_out, stream))) return rc;
+  launch_stream_hist<2>(M, v, sel, hist, n, s);
+  LAUNCH_CHECK("k_stream_hist<2>");
+  return stein_median_resolve(hist, 2, n, sel, h2_out, median_out, stream);
 }

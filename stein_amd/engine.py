@@ -84,6 +84,12 @@ class HipStages:
         _lib.call_on(T.device, "stein_svgd_phi_stream", _ptr(T), _ptr(G), n, d, _dt(T), _ptr(h2), _ptr(phi), _ptr(sqnorm),
                      _ptr(ws), ws.numel(), 0, _stream(T))
 
+    def stream_median(self, T, n, d, h2, median, ws):
+        """the median-heuristic bandwidth^2 (and the median) of T's n^2 distances into the 1-element device tensors h2 and
+        median (median may be None), in a streaming workspace: no n x n image (stein_stream_median, include/steinhip.h)"""
+        _lib.call_on(T.device, "stein_stream_median", _ptr(T), n, d, _dt(T), _ptr(h2), _ptr(median), _ptr(ws), ws.numel(), 0,
+                     _stream(T))
+
     def x3_prepare(self, T, G, n, d, planes):
         """T or G may be None: only the other matrix's scales and planes are rebuilt."""
         ref = T if T is not None else G
@@ -209,13 +215,27 @@ class SvgdEngine:
               (an annealing schedule) or hand over another engine's `h2` (a median refreshed every k-th step and held in
               between).  Either way `self.h2` is that tensor.  fp32 inputs on the split path, one rank; K_out, dK_out,
               dist_matrix(), ksd, mark= and group= are refused with a ValueError.
+              "median": the streaming step at the median heuristic's own bandwidth, still without the n x n image: the
+              engine owns `self.h2` and `self.median` (1-element float32 device tensors) and, before the step of every
+              call whose 0-based index is a multiple of `median_every`, takes the exact median of the n^2 distances in
+              its own O(n d) workspace (stein_stream_median: the distance tiles recomputed once per radix level); h2 is
+              held in between.  refresh_bandwidth(theta) does the same on demand.  Needs n >= 2.
+    median_every : with h2="median", the step period of the median refresh: an integer >= 1 (default 1: every step).
+              Refused with a ValueError on any other engine.
     """
 
     def __init__(self, n, d, device="cuda", group=None, stages=None, x3=None, dtype=torch.float32, small=True,
                  window=True, force_collectives=False, comm="auto", tile_distance=False, dist_window=None, ksd=False,
-                 fold=None, h2=None):
+                 fold=None, h2=None, median_every=1):
         self.n, self.d = int(n), int(d)
         self.streaming = h2 is not None
+        stream_median = isinstance(h2, str) and h2 == "median"
+        if isinstance(median_every, bool) or not isinstance(median_every, int) or median_every < 1:
+            raise ValueError("median_every must be an integer >= 1, got %r" % (median_every,))
+        if median_every != 1 and not stream_median:
+            raise ValueError("median_every= is the refresh period of h2=\"median\" (the streaming step at the median "
+                             "heuristic's bandwidth); it is not supported on any other engine")
+        self.median_every = median_every if stream_median else None
         if self.streaming:
             self._init_stream(h2, device, group, stages, x3, dtype, ksd)
             return
@@ -335,7 +355,11 @@ class SvgdEngine:
         if ksd:
             raise ValueError("h2=: ksd=True is not supported (the Stein discrepancy at a supplied bandwidth needs K.theta)")
         self.device = torch.device(device)
-        if isinstance(h2, torch.Tensor):
+        if self.median_every is not None:
+            if self.n < 2:
+                raise ValueError("n_particles = %d: the median-heuristic bandwidth divides by ln(n); need n >= 2" % self.n)
+            self.h2 = torch.zeros(1, dtype=torch.float32, device=self.device)     # written by the median call, on the device
+        elif isinstance(h2, torch.Tensor):
             if h2.numel() != 1 or h2.dtype != torch.float32 or h2.device.type != self.device.type or \
                     (self.device.index is not None and h2.device.index != self.device.index):
                 raise ValueError("h2 must be a positive finite float or a 1-element float32 tensor on %s, got %s %s on %s" %
@@ -357,6 +381,8 @@ class SvgdEngine:
         self.stages = stages if stages is not None else HipStages()
         if not hasattr(self.stages, "svgd_phi_stream"):
             raise ValueError("h2=: the stages have no streaming step (HipStages has)")
+        if self.median_every is not None and not hasattr(self.stages, "stream_median"):
+            raise ValueError("h2=\"median\": the stages have no streaming median (HipStages has)")
         self.group, self.world, self.rank, self.sharded = None, 1, 0, False
         self.n_local, self.row0 = self.n, 0
         self.comm, self._comm, self.comm_error = None, None, None
@@ -374,6 +400,26 @@ class SvgdEngine:
         # missing attribute (the workspace views refuse with a ValueError: _section)
         self._offs, self.ld_dist, self.split, self.median = None, 0, 0, None
         self._flags_host, self._flags_event = None, None
+        self._stream_calls = 0
+        if self.median_every is not None:
+            # the median call works in a prefix-compatible subset of the step's layout: one buffer serves both
+            assert _lib.stream_median_workspace_bytes(self.n, self.d) <= self.ws_bytes
+            self.median = torch.zeros(1, dtype=torch.float32, device=dev)
+
+    def _check_stream_input(self, name, t):
+        if tuple(t.shape) != (self.n, self.d) or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous torch.float32 [%d, %d] tensor, got %s %s" %
+                             (name, self.n, self.d, tuple(t.shape), t.dtype))
+
+    def refresh_bandwidth(self, theta):
+        """h2="median": take the median-heuristic bandwidth of `theta` ([n, d] float32 device tensor) now, in this engine's
+        own workspace; returns self.h2 (self.median holds the median).  Nothing syncs with the host.  The refresh
+        schedule of compute_phi (median_every) is not affected."""
+        if self.median_every is None:
+            raise ValueError("refresh_bandwidth needs an engine built with h2=\"median\"")
+        self._check_stream_input("theta", theta)
+        self.stages.stream_median(theta, self.n, self.d, self.h2, self.median, self.ws)
+        return self.h2
 
     def _make_native_comm(self):
         """Group rank 0 makes the 128-byte RCCL id, the group broadcasts it, every rank joins -- collective, and
@@ -618,9 +664,11 @@ class SvgdEngine:
             if mark is not None or timing:
                 raise ValueError("h2=: the streaming step is one call; mark= / timing= are not supported")
             for name, t in (("theta", theta_local), ("score", score_local)):
-                if tuple(t.shape) != (n, d) or t.dtype != torch.float32 or not t.is_contiguous():
-                    raise ValueError("%s must be a contiguous torch.float32 [%d, %d] tensor, got %s %s" %
-                                     (name, n, d, tuple(t.shape), t.dtype))
+                self._check_stream_input(name, t)
+            if self.median_every is not None:
+                if self._stream_calls % self.median_every == 0:
+                    st.stream_median(theta_local, n, d, self.h2, self.median, self.ws)
+                self._stream_calls += 1
             st.svgd_phi_stream(theta_local, score_local, n, d, self.h2, self.phi, self.sqnorm, self.ws)
             return self.phi
         if self.ksd and (mark is not None or (self.sharded and K_out is not None)):

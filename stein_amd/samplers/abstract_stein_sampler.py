@@ -28,7 +28,8 @@ class AbstractSteinSampler:
     INIT_SCALE = 0.01  # abstract_stein_sampler.py:72
 
     def __init__(self, n_particles, log_p, theta=None, *, model_vars=None, device="cuda", dtype=torch.float32,
-                 group=None, seed=None, kernel_dtype=torch.float32, x3=None, ksd=False, bandwidth=None, h2=None):
+                 group=None, seed=None, kernel_dtype=torch.float32, x3=None, ksd=False, bandwidth=None, h2=None,
+                 median_every=1):
         """
         n_particles : total number of particles n (across all ranks).
         log_p       : see SteinSampler.
@@ -48,6 +49,10 @@ class AbstractSteinSampler:
                       the streaming path (no median, no n x n workspace; see engine.SvgdEngine, h2=).
         h2          : the device form of the same: a 1-element float32 device tensor holding h^2, read on the device in every
                       step, which the caller may rewrite in place (annealing).  Give one of bandwidth / h2, not both.
+                      bandwidth="median": the median heuristic on the streaming path -- the exact median of the n^2
+                      distances taken without the n x n workspace (engine.SvgdEngine, h2="median").
+        median_every : with bandwidth="median", refresh the median every this many steps (integer >= 1, default 1) and
+                      hold the bandwidth in between; refused otherwise.
         """
         self.n_particles = int(n_particles)
         self.log_p = log_p
@@ -113,16 +118,19 @@ class AbstractSteinSampler:
         if bandwidth is not None:
             if h2 is not None:
                 raise ValueError("give bandwidth= (a float h) or h2= (a device tensor holding h^2), not both")
-            import math
-            try:
-                h = float(bandwidth)
-            except (TypeError, ValueError):
-                raise ValueError("bandwidth must be a positive finite float, got %r" % (bandwidth,))
-            if not math.isfinite(h) or h <= 0.0:
-                raise ValueError("bandwidth must be positive and finite, got %r" % (bandwidth,))
-            h2 = h * h
+            if isinstance(bandwidth, str) and bandwidth == "median":
+                h2 = "median"
+            else:
+                import math
+                try:
+                    h = float(bandwidth)
+                except (TypeError, ValueError):
+                    raise ValueError("bandwidth must be a positive finite float or \"median\", got %r" % (bandwidth,))
+                if not math.isfinite(h) or h <= 0.0:
+                    raise ValueError("bandwidth must be positive and finite, got %r" % (bandwidth,))
+                h2 = h * h
         self.engine = SvgdEngine(self.n_particles, self.n_params, device=self.device, group=group, x3=x3,
-                                 dtype=kernel_dtype, ksd=ksd, h2=h2)
+                                 dtype=kernel_dtype, ksd=ksd, h2=h2, median_every=median_every)
         self._theta32 = (self.theta_matrix if dtype == kernel_dtype else
                          torch.empty(self.n_local, self.n_params, dtype=kernel_dtype, device=self.device))
 
