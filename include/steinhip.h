@@ -141,6 +141,13 @@ int stein_workspace_layout(int64_t n_local, int64_t n, int64_t d, int dtype, int
 
 /* *out = 1 if stein_svgd_phi with these arguments takes the folded contraction (STEIN_FLAG_FOLD), else 0.  Host arithmetic. */
 int stein_layout_folds(int64_t n_local, int64_t n, int64_t d, int dtype, int flags, int* out);
+/* *out = the j ranges of that call's folded contraction (what its finish pass sums), 0 if it does not fold.  Host arithmetic.
+ * stein_debug_fold_split(k) (test hook, per calling thread): k > 0 asks the plan for k ranges instead of its own rule, 0
+ * restores the rule.  A range still starts on a multiple of 128 columns and empty tails are dropped, so fewer may come out;
+ * the workspace size depends on it: set it before sizing the workspace and keep it through the calls.  Results do not
+ * depend on the ranges beyond the order of the fp32 sums over them. */
+int stein_layout_fold_ranges(int64_t n_local, int64_t n, int64_t d, int dtype, int flags, int* out);
+int stein_debug_fold_split(int ranges);
 
 /* ---- fused single-rank path ------------------------------------------------------------------
  * Replaces AbstractSteinSampler.compute_phi (stein/samplers/abstract_stein_sampler.py:100-105)
@@ -476,6 +483,8 @@ int stein_cast_f32_to_bf16(const float* src, void* dst, int64_t count, void* str
  * stein_debug_raise_device_error raises the current device's word as a kernel would. */
 int stein_take_device_error(void);
 int stein_debug_hist_all_grid(int blocks);
+int stein_debug_no_warm(int off);   /* test hook, per calling thread: 1 = the fused call's select launches without the
+                                       workgroups that re-read theta and the score for the folded operand's split; 0 = default */
 int stein_debug_hist_all_vblocks(int nvb);   /* tuning aid: virtual workgroups per level of that kernel (0 = default) */
 int stein_debug_raise_device_error(void);
 

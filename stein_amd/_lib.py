@@ -50,6 +50,9 @@ _SIGNATURES = {
     "stein_workspace_bytes": [_i64, _i64, _i64, _int, _int, _c.POINTER(_sz)],
     "stein_workspace_layout": [_i64, _i64, _i64, _int, _int, _c.POINTER(_sz), _c.POINTER(_i64)],
     "stein_layout_folds": [_i64, _i64, _i64, _int, _int, _c.POINTER(_int)],
+    "stein_layout_fold_ranges": [_i64, _i64, _i64, _int, _int, _c.POINTER(_int)],
+    "stein_debug_fold_split": [_int],
+    "stein_debug_no_warm": [_int],
     "stein_spec_begin": [_vp, _vp, _vp, _i64, _vp],
     "stein_distance_block_spec": [_vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _i64, _vp, _vp, _int, _vp, _vp, _vp],
     "stein_spec_tally": [_vp, _vp, _vp],
@@ -169,6 +172,23 @@ def layout_folds(n_local, n, d, dtype=F32, flags=0):
     out = _int(0)
     call("stein_layout_folds", n_local, n, d, dtype, flags, ctypes.byref(out))
     return bool(out.value)
+
+
+def layout_fold_ranges(n_local, n, d, dtype=F32, flags=0):
+    """j ranges of the folded contraction of the fused call with these arguments (0: it does not fold).  Host arithmetic."""
+    out = _int(0)
+    call("stein_layout_fold_ranges", n_local, n, d, dtype, flags, ctypes.byref(out))
+    return int(out.value)
+
+
+def debug_fold_split(ranges):
+    """Test hook (per calling thread): j ranges the folded contraction's plan asks for; 0 restores the plan's own rule."""
+    call("stein_debug_fold_split", int(ranges))
+
+
+def debug_no_warm(off):
+    """Test hook (per calling thread): True launches the fused call's select without its warm slice."""
+    call("stein_debug_no_warm", 1 if off else 0)
 
 
 def stream_workspace_bytes(n, d, dtype=F32, flags=0):

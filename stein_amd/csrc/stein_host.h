@@ -75,7 +75,9 @@ int stein_device_error_word(u32** out);
 int stein_take_device_error(void);
 
 // stein_select.hip: the fused call's median behind its distance pass (k_spec_select, then k_hist_all unless n is small)
-int stein_fused_select(const StepViews& v, int64_t n, float* h2_out, hipStream_t stream);
+// theta_all / score_all: the call's inputs, read (and dropped) by the select launch's warm slice when the operand is folded
+int stein_fused_select(const StepViews& v, int64_t n, int64_t d, float* h2_out, const void* theta_all, const void* score_all,
+                       hipStream_t stream);
 
 // stein_fp32.hip: the fp32-input MFMA kernels, for calls without the split planes (what stein_x3_distance and
 // stein_x3_contract_partial are for the split path).  window: also feed the speculative median window (v.spec, v.spec_buf)

@@ -673,9 +673,30 @@ __device__ __forceinline__ void solo_select(const float* __restrict__ D, long ld
 }
 
 // D != NULL ("solo", fused call on a small symmetric block): a miss is resolved here by solo_select
+// Workgroups 1 .. gridDim.x - 1 (fused call with the folded operand only; the select is workgroup 0, one workgroup on an
+// otherwise idle chip) read warm0 and warm1 -- theta and the score, warm4 16-byte pieces each -- and drop the values: the
+// distance pass has just pushed 0.5 GB of D through the memory-side cache, and k_split_w, next but one in the stream, then
+// finds its inputs there again.  They store nothing, wait for nothing and nothing waits for them.
 __global__ __launch_bounds__(1024) void k_spec_select(SelState* st, SpecState* sp, const u64* __restrict__ slots,
                                                       float ln_n, float* h2_out, int update,
-                                                      const float* __restrict__ D, long ldD, int n) {
+                                                      const float* __restrict__ D, long ldD, int n,
+                                                      const float4* __restrict__ warm0, const float4* __restrict__ warm1,
+                                                      long warm4) {
+  if (blockIdx.x) {
+    const long stride = (long)(gridDim.x - 1) * 1024;
+    auto keep = [](const float4& a) { asm volatile("" ::"v"(a.x), "v"(a.y), "v"(a.z), "v"(a.w)); };
+    long i = (long)(blockIdx.x - 1) * 1024 + threadIdx.x;
+    for (; i + 3 * stride < warm4; i += 4 * stride) {   // eight loads in flight per lane, both matrices together
+      const float4 a0 = warm0[i], a1 = warm0[i + stride], a2 = warm0[i + 2 * stride], a3 = warm0[i + 3 * stride];
+      const float4 b0 = warm1[i], b1 = warm1[i + stride], b2 = warm1[i + 2 * stride], b3 = warm1[i + 3 * stride];
+      keep(a0); keep(a1); keep(a2); keep(a3); keep(b0); keep(b1); keep(b2); keep(b3);
+    }
+    for (; i < warm4; i += stride) {
+      const float4 a0 = warm0[i], b0 = warm1[i];
+      keep(a0); keep(b0);
+    }
+    return;
+  }
   const bool hit = spec_select_body(st, sp, slots, ln_n, h2_out, update);
   if (!hit && D) {
     __syncthreads();
@@ -916,6 +937,13 @@ extern "C" int stein_spec_update(void* select_state, void* stream) {
 // test hooks (per calling thread; tests/test_gpu_spec.py): launch k_hist_all with this many workgroups instead of one per
 // virtual workgroup (0 = default); stein_debug_raise_device_error (steinhip.hip) raises the error word as a kernel would
 static thread_local int g_hist_all_grid = 0, g_hist_all_nvb = 0;
+constexpr int SPEC_WARM_WGS = 255;
+static thread_local int g_no_warm = 0;   // stein_debug_no_warm: 1 = the select launches without its warm slice
+extern "C" int stein_debug_no_warm(int off) {
+  if (off != 0 && off != 1) return fail(STEIN_E_BADARG, "off %d", off);
+  g_no_warm = off;
+  return STEIN_OK;
+}
 extern "C" int stein_debug_hist_all_grid(int blocks) {
   if (blocks < 0 || blocks > 65535) return fail(STEIN_E_BADARG, "blocks %d", blocks);
   g_hist_all_grid = blocks;
@@ -928,12 +956,23 @@ extern "C" int stein_debug_hist_all_vblocks(int nvb) {   // (tuning aid: virtual
 }
 
 // ---- the fused call's select ----------------------------------------------------------------------------------------
-int stein_fused_select(const StepViews& v, int64_t n, float* h2_out, hipStream_t s) {
+int stein_fused_select(const StepViews& v, int64_t n, int64_t d, float* h2_out, const void* theta_all,
+                       const void* score_all, hipStream_t s) {
   // the window either yields the median now (spec->hit) or the radix-select passes below run; each of them
   // checks the flag on the device, so nothing here waits for the host
   const bool solo = n <= SOLO_MAX_N;   // small block: a miss is resolved inside k_spec_select, no histogram launches
-  hipLaunchKernelGGL(k_spec_select, dim3(1), dim3(1024), 0, s, v.sel, v.spec, v.spec_buf, (float)log((double)n), h2_out,
-                     1, solo ? (const float*)v.D : (const float*)nullptr, (long)v.L.ld_dist, (int)n);
+  // the warm slice (k_spec_select): folded operand, fp32 inputs on 16-byte boundaries; one workgroup per 128 KB of a
+  // matrix, at most SPEC_WARM_WGS (one per compute unit beside the select's)
+  long warm4 = 0;
+  int warm_wgs = 0;
+  if (v.L.fold && !g_no_warm && theta_all && score_all && (((uintptr_t)theta_all | (uintptr_t)score_all) & 15u) == 0) {
+    warm4 = (long)(n * d) >> 2;
+    const long want = (warm4 + 8191) / 8192;
+    warm_wgs = (int)(want < SPEC_WARM_WGS ? want : SPEC_WARM_WGS);
+  }
+  hipLaunchKernelGGL(k_spec_select, dim3(1 + warm_wgs), dim3(1024), 0, s, v.sel, v.spec, v.spec_buf, (float)log((double)n),
+                     h2_out, 1, solo ? (const float*)v.D : (const float*)nullptr, (long)v.L.ld_dist, (int)n,
+                     (const float4*)theta_all, (const float4*)score_all, warm4);
   LAUNCH_CHECK("k_spec_select");
   if (solo) return STEIN_OK;
   // chained radix select, ONE launch whatever n (k_hist_all: in-launch level barriers that need no co-residency; it returns

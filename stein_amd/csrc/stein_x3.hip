@@ -248,11 +248,61 @@ __global__ __launch_bounds__(256) void k_make_scales(const u32* __restrict__ cma
 // (prologue_body, stein_common.h: row norms, median state, tickets, neutral scales) -- bf16 planes need no scales, so
 // nothing here waits for it, and the step is one launch shorter.  The split slices then must not READ the scales (the
 // prologue slice writes them in the same launch): they are 1 by definition for KIND 1.
+// LDS image of a transposed 64 x 64 tile, one per plane: [64 columns][32 particle pairs] of u32 (particle 2p in the low half,
+// 2p + 1 in the high one: a pair is one word of the k-contiguous operand), no padding; the 16-byte slot p >> 2 of column c
+// sits at slot ^ ((c >> 2) & 7).
+//   ds_write_b32 (banks mod 32, 32-lane groups): a group holds the 16 column quads twice; the quads 0-7 write pairs
+//     p & 3 = {0, 1}, the quads 8-15 {2, 3} (tp_pair) into eight distinct slots each: 32 distinct banks.
+//   ds_read_b128 (banks mod 64, lane groups {0-3,12-15,20-27}, ...): a group holds the columns {0,3,5,6} or {1,2,4,7} (+ 8)
+//     with four slots 2 quarter + e each; the two columns of equal parity differ in c >> 2, so in the slot's low bit: 16
+//     distinct slots of the 256-byte bank row.
+// (The image used to be [64][66] u16 written and read one half-word at a time: 32 LDS stores and 32 loads per thread and
+// plane, and the kernels ran at 2.3 TB/s.)
+constexpr int TP_WORDS = 64 * 32;
+__device__ __forceinline__ int tp_index(int c, int p) { return c * 32 + ((((p >> 2) ^ (c >> 2)) & 7) << 2) + (p & 3); }
+// the particle pair (rows 2 p, 2 p + 1 of the tile) thread t converts in pass 0 or 1; its columns are 4 (t & 15) ..+3.  Eight
+// consecutive lanes still read 128 consecutive bytes of a row.
+__device__ __forceinline__ int tp_pair(int t, int pass) { return 16 * pass + 4 * (t >> 6) + (((t >> 4) & 3) ^ ((t >> 2) & 2)); }
+
+// four consecutive entries of row `row` from column `col` (col % 4 == 0), zero outside the matrix.  vec (host: fp32,
+// d % 4 == 0, the matrix on a 16-byte boundary): one 16-byte load instead of four
+template <typename TIN>
+__device__ __forceinline__ void load_row4(const TIN* __restrict__ X, int row, int col, int n, int d, int vec, float (&v)[4]) {
+  if constexpr (std::is_same<TIN, float>::value) {
+    if (vec) {
+      const float4 x = (row < n && col < d) ? *reinterpret_cast<const float4*>(X + (size_t)row * d + col) : make_float4(0.f, 0.f, 0.f, 0.f);
+      v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
+      return;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) v[q] = (row < n && col + q < d) ? elem_f32(X + (size_t)row * d + col + q) : 0.f;
+}
+
+// the image -> the transposed planes: thread -> (parameter c = t >> 2, the 16 particles starting at j = row0 + 16 (t & 3)) =
+// two 8-element chunks of the k tile, written in MFMA fragment order (vfrag_offset)
+template <int KIND>
+__device__ __forceinline__ void tp_store(const u32 (*tile)[TP_WORDS], u16* __restrict__ Tt, long ntk_t, int dc, long nk,
+                                         int row0, int col0, int t) {
+  const int c = col0 + (t >> 2), j = row0 + (t & 3) * 16;
+  if (c < dc && j < nk) {   // nk % 32 == 0 and j % 16 == 0: both fragments stay inside one k tile
+    const int rowc = c & 127, ch0 = (j & 31) >> 3;
+#pragma unroll
+    for (int s = 0; s < KIND; ++s) {
+      const uint4 w0 = *reinterpret_cast<const uint4*>(&tile[s][tp_index(t >> 2, (t & 3) * 8)]);
+      const uint4 w1 = *reinterpret_cast<const uint4*>(&tile[s][tp_index(t >> 2, (t & 3) * 8 + 4)]);
+      u16* base = Tt + (((size_t)(c >> 7) * ntk_t + (j >> 5)) * 3 + s) * XTILE_E;
+      *reinterpret_cast<uint4*>(base + vfrag_offset(rowc, ch0)) = w0;
+      *reinterpret_cast<uint4*>(base + vfrag_offset(rowc, ch0 + 1)) = w1;
+    }
+  }
+}
+
 template <typename TIN, int KIND, bool PRO = false>
 __global__ __launch_bounds__(256) void k_split(const TIN* __restrict__ X0, const TIN* __restrict__ X1, int n, int d,
                                                u16* __restrict__ R0, long r_rows, int dk, u16* __restrict__ Tt0,
                                                u16* __restrict__ Tt1, int dc, long nk, const float* __restrict__ sc,
-                                               int zbase, PrologueArgs pro) {
+                                               int zbase, PrologueArgs pro, int vec) {
   if (PRO && blockIdx.z == gridDim.z - 1) {
     prologue_body<TIN>(X0, pro, (int)(blockIdx.y * gridDim.x + blockIdx.x), (int)(gridDim.x * gridDim.y));
     return;
@@ -264,59 +314,45 @@ __global__ __launch_bounds__(256) void k_split(const TIN* __restrict__ X0, const
   u16* __restrict__ Tt = score ? Tt1 : Tt0;
   const float* __restrict__ sc_all = sc + 4 * dc;                 // scale of the row-major theta image
   const float* __restrict__ sc_col = sc + (score ? 0 : dc);       // per-column scales of this matrix
-  __shared__ u16 tile[KIND][64][66];
+  __shared__ __attribute__((aligned(16))) u32 tile[KIND][TP_WORDS];
   const int t = threadIdx.x;
   const int row0 = blockIdx.y * 64, col0 = blockIdx.x * 64;
-  const int lr = t >> 4, lc = (t & 15) * 4;
+  const int lc = (t & 15) * 4;
   const long ntk_r = dk >> 5, ntk_t = nk >> 5;
   const float sa = (R && !PRO) ? *sc_all : 1.f;
   float scq[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) scq[q] = (!PRO && Tt && col0 + lc + q < dc) ? sc_col[col0 + lc + q] : 1.f;
 #pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    const int row = row0 + lr + 16 * p, col = col0 + lc;
-    float v[4];
+  for (int p = 0; p < 2; ++p) {
+    const int pr = tp_pair(t, p), col = col0 + lc;
+    float v[2][4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) v[q] = (row < n && col + q < d) ? elem_f32(X + (size_t)row * d + col + q) : 0.f;
-    if (R && row < r_rows && col < dk) {   // col % 4 == 0: the 4 entries stay inside one 32-wide k tile
-      u32 wa[3], wb[3];
-      split_pair<KIND>(v[0] * sa, v[1] * sa, wa);
-      split_pair<KIND>(v[2] * sa, v[3] * sa, wb);
-      u16* dst = R + (((size_t)(row >> 7) * ntk_r + (col >> 5)) * 3) * XTILE_E + vfrag_offset(row & 127, (col & 31) >> 3) + (col & 7);
+    for (int h = 0; h < 2; ++h) {
+      const int row = row0 + 2 * pr + h;
+      load_row4(X, row, col, n, d, vec, v[h]);
+      if (R && row < r_rows && col < dk) {   // col % 4 == 0: the 4 entries stay inside one 32-wide k tile
+        u32 wa[3], wb[3];
+        split_pair<KIND>(v[h][0] * sa, v[h][1] * sa, wa);
+        split_pair<KIND>(v[h][2] * sa, v[h][3] * sa, wb);
+        u16* dst = R + (((size_t)(row >> 7) * ntk_r + (col >> 5)) * 3) * XTILE_E + vfrag_offset(row & 127, (col & 31) >> 3) + (col & 7);
 #pragma unroll
-      for (int s = 0; s < KIND; ++s) *reinterpret_cast<uint2*>(dst + s * XTILE_E) = make_uint2(wa[s], wb[s]);
+        for (int s = 0; s < KIND; ++s) *reinterpret_cast<uint2*>(dst + s * XTILE_E) = make_uint2(wa[s], wb[s]);
+      }
     }
-    if (Tt) {
-      u32 wa[3], wb[3];
-      split_pair<KIND>(v[0] * scq[0], v[1] * scq[1], wa);
-      split_pair<KIND>(v[2] * scq[2], v[3] * scq[3], wb);
-      const int rr = lr + 16 * p;
+    if (Tt) {   // a column's two particles make one word: the terms are the same element by element
 #pragma unroll
-      for (int s = 0; s < KIND; ++s) {
-        tile[s][lc + 0][rr] = (u16)wa[s]; tile[s][lc + 1][rr] = (u16)(wa[s] >> 16);
-        tile[s][lc + 2][rr] = (u16)wb[s]; tile[s][lc + 3][rr] = (u16)(wb[s] >> 16);
+      for (int q = 0; q < 4; ++q) {
+        u32 w[3];
+        split_pair<KIND>(v[0][q] * scq[q], v[1][q] * scq[q], w);
+#pragma unroll
+        for (int s = 0; s < KIND; ++s) tile[s][tp_index(lc + q, pr)] = w[s];
       }
     }
   }
   if (!Tt) return;
   __syncthreads();
-  // transposed store: thread -> (parameter c = t >> 2, the 16 particles starting at j = row0 + 16 (t & 3)) = two
-  // 8-element chunks of the k tile, written in MFMA fragment order (vfrag_offset)
-  const int c = col0 + (t >> 2), j = row0 + (t & 3) * 16;
-  if (c < dc && j < nk) {   // nk % 32 == 0 and j % 16 == 0: both fragments stay inside one k tile
-    const int rowc = c & 127, ch0 = (j & 31) >> 3;
-#pragma unroll
-    for (int s = 0; s < KIND; ++s) {
-      u32 w[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q)
-        w[q] = (u32)tile[s][t >> 2][(t & 3) * 16 + 2 * q] | ((u32)tile[s][t >> 2][(t & 3) * 16 + 2 * q + 1] << 16);
-      u16* base = Tt + (((size_t)(c >> 7) * ntk_t + (j >> 5)) * 3 + s) * XTILE_E;
-      *reinterpret_cast<uint4*>(base + vfrag_offset(rowc, ch0)) = make_uint4(w[0], w[1], w[2], w[3]);
-      *reinterpret_cast<uint4*>(base + vfrag_offset(rowc, ch0 + 1)) = make_uint4(w[4], w[5], w[6], w[7]);
-    }
-  }
+  tp_store<KIND>(tile, Tt, ntk_t, dc, nk, row0, col0, t);
 }
 
 // The folded operand (fused call, fp32 inputs; stein_fold_pays): phi_i = (sum_j K_ij w_j + rowsum_i theta_i / h2) / n with
@@ -329,11 +365,11 @@ __global__ __launch_bounds__(256) void k_split(const TIN* __restrict__ X0, const
 // the scale 1, W holds inf / NaN and phi comes out NaN as on every other path.
 __global__ __launch_bounds__(256) void k_split_w(const float* __restrict__ T, const float* __restrict__ G, int n, int d,
                                                  u16* __restrict__ Wt, int dc, long nk, float* __restrict__ sc,
-                                                 const u32* __restrict__ cmax, const float* __restrict__ h2p) {
-  __shared__ u16 tile[2][64][66];
+                                                 const u32* __restrict__ cmax, const float* __restrict__ h2p, int vec) {
+  __shared__ __attribute__((aligned(16))) u32 tile[2][TP_WORDS];
   const int t = threadIdx.x;
   const int row0 = blockIdx.y * 64, col0 = blockIdx.x * 64;
-  const int lr = t >> 4, lc = (t & 15) * 4;
+  const int lc = (t & 15) * 4;
   const long ntk_t = nk >> 5;
   const float ih = 1.f / *h2p;
   float scq[4];
@@ -343,46 +379,34 @@ __global__ __launch_bounds__(256) void k_split_w(const float* __restrict__ T, co
     int se = 0;
     if (c < dc) se = scale_exp(__float_as_uint(__builtin_fmaf(__uint_as_float(cmax[dc + c]), ih, __uint_as_float(cmax[c]))), 100);
     scq[q] = pow2i(se);
-    if (blockIdx.y == 0 && lr == 0 && c < dc) {
+    if (blockIdx.y == 0 && (t >> 4) == 0 && c < dc) {
       sc[c] = scq[q];
       sc[2 * dc + c] = pow2i(-se - PEXP_H2);
     }
   }
 #pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    const int row = row0 + lr + 16 * p, col = col0 + lc;
-    float v[4];
+  for (int p = 0; p < 2; ++p) {
+    const int pr = tp_pair(t, p), col = col0 + lc;
+    float v[2][4];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int row = row0 + 2 * pr + h;
+      float th[4], g[4];
+      load_row4(T, row, col, n, d, vec, th);
+      load_row4(G, row, col, n, d, vec, g);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) v[h][q] = (row < n && col + q < d) ? __builtin_fmaf(-th[q], ih, g[q]) : 0.f;
+    }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const size_t at = (size_t)row * d + col + q;
-      v[q] = (row < n && col + q < d) ? __builtin_fmaf(-T[at], ih, G[at]) : 0.f;
-    }
-    u32 wa[3], wb[3];
-    split_pair<2>(v[0] * scq[0], v[1] * scq[1], wa);
-    split_pair<2>(v[2] * scq[2], v[3] * scq[3], wb);
-    const int rr = lr + 16 * p;
+      u32 w[3];
+      split_pair<2>(v[0][q] * scq[q], v[1][q] * scq[q], w);
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      tile[s][lc + 0][rr] = (u16)wa[s]; tile[s][lc + 1][rr] = (u16)(wa[s] >> 16);
-      tile[s][lc + 2][rr] = (u16)wb[s]; tile[s][lc + 3][rr] = (u16)(wb[s] >> 16);
+      for (int s = 0; s < 2; ++s) tile[s][tp_index(lc + q, pr)] = w[s];
     }
   }
   __syncthreads();
-  // transposed store, as in k_split
-  const int c = col0 + (t >> 2), j = row0 + (t & 3) * 16;
-  if (c < dc && j < nk) {
-    const int rowc = c & 127, ch0 = (j & 31) >> 3;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      u32 w[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q)
-        w[q] = (u32)tile[s][t >> 2][(t & 3) * 16 + 2 * q] | ((u32)tile[s][t >> 2][(t & 3) * 16 + 2 * q + 1] << 16);
-      u16* base = Wt + (((size_t)(c >> 7) * ntk_t + (j >> 5)) * 3 + s) * XTILE_E;
-      *reinterpret_cast<uint4*>(base + vfrag_offset(rowc, ch0)) = make_uint4(w[0], w[1], w[2], w[3]);
-      *reinterpret_cast<uint4*>(base + vfrag_offset(rowc, ch0 + 1)) = make_uint4(w[4], w[5], w[6], w[7]);
-    }
-  }
+  tp_store<2>(tile, Wt, ntk_t, dc, nk, row0, col0, t);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -987,17 +1011,19 @@ static void launch_split(hipStream_t stream, const TIN* theta, const TIN* score,
   // grid.z walks [theta, score]; a NULL matrix is left out (its planes keep their contents)
   const unsigned nz = (theta ? 1u : 0u) + (score ? 1u : 0u);
   const int zbase = theta ? 0 : 1;
+  // 16-byte loads of the inputs (load_row4): fp32 rows that start on 16-byte boundaries
+  const int vec = std::is_same<TIN, float>::value && d % 4 == 0 && (((uintptr_t)theta | (uintptr_t)score) & 15u) == 0;
   const int64_t rows = L.x3_rows > L.x3_nk ? L.x3_rows : L.x3_nk;   // particle extent to cover (both multiples of 32)
   const int64_t cols = L.x3_dk > L.x3_dc ? L.x3_dk : L.x3_dc;      // parameter extent
   if (KIND == 1 && pro && theta) {   // + the prologue slice (fused call, bf16)
     const dim3 grid((unsigned)((cols + 63) / 64), (unsigned)((rows + 63) / 64), nz + 1u);
     hipLaunchKernelGGL((k_split<TIN, KIND, true>), grid, dim3(256), 0, stream, theta, score, (int)n, (int)d, T3,
-                       (long)L.x3_rows, (int)L.x3_dk, Tt3, Gt3, (int)L.x3_dc, (long)L.x3_nk, sc, zbase, *pro);
+                       (long)L.x3_rows, (int)L.x3_dk, Tt3, Gt3, (int)L.x3_dc, (long)L.x3_nk, sc, zbase, *pro, vec);
     return;
   }
   const dim3 grid((unsigned)((cols + 63) / 64), (unsigned)((rows + 63) / 64), nz);
   hipLaunchKernelGGL((k_split<TIN, KIND, false>), grid, dim3(256), 0, stream, theta, score, (int)n, (int)d, T3,
-                     (long)L.x3_rows, (int)L.x3_dk, Tt3, Gt3, (int)L.x3_dc, (long)L.x3_nk, sc, zbase, PrologueArgs{});
+                     (long)L.x3_rows, (int)L.x3_dk, Tt3, Gt3, (int)L.x3_dc, (long)L.x3_nk, sc, zbase, PrologueArgs{}, vec);
 }
 
 int stein_x3_split(const StepViews& v, const void* theta_all, const void* score_all, int dtype, int64_t n, int64_t d,
@@ -1053,8 +1079,9 @@ int stein_x3_split_w(const StepViews& v, const float* theta_all, const float* sc
                      const float* h2_dev, hipStream_t stream) {
   const SteinLayout& L = v.L;
   const dim3 grid((unsigned)((L.x3_dc + 63) / 64), (unsigned)((L.x3_nk + 63) / 64));
+  const int vec = d % 4 == 0 && (((uintptr_t)theta_all | (uintptr_t)score_all) & 15u) == 0;   // 16-byte loads (load_row4)
   hipLaunchKernelGGL(k_split_w, grid, dim3(256), 0, stream, theta_all, score_all, (int)n, (int)d, v.Gt3, (int)L.x3_dc,
-                     (long)L.x3_nk, v.sc, (const u32*)v.cmax, h2_dev);
+                     (long)L.x3_nk, v.sc, (const u32*)v.cmax, h2_dev, vec);
   LAUNCH_CHECK("k_split_w");
   return STEIN_OK;
 }

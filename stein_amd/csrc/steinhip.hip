@@ -123,43 +123,95 @@ __global__ __launch_bounds__(256) void k_phi_finish(const float* __restrict__ OG
   if (vec) {   // host: d % 4 == 0 and every pointer aligned for four columns at a time
     // four consecutive columns of one row per step, 16-byte loads and stores (one entry at a time with an integer
     // division each, the kernel moved its 68 MB at 2.8 TB/s; bf16 inputs took that path until round 4: 19 us at C2)
+    // NZ j ranges of OG and RS and NT of OT known at compile time (NZ = 1, 2, 4, NT = NZ or, folded, 0 or 1; NZ = 0: any
+    // numbers, the loop): every load of an element group -- the ranges' OG / OT / RS and theta -- is issued before the first add.  (With the runtime count the unrolled loop was a chain of
+    // branches with one 16-byte load between each pair: one or two loads in flight per thread, 67 MB at 3.7 TB/s.)  The
+    // sums run in the same order on every form: 0 + a0 + a1 ...
     const long total4 = total >> 2;
     const int d4 = d >> 2;
-    for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < total4; q += (long)gridDim.x * 256) {
-      const int i = (int)(q / d4);
-      const long e = q << 2;
-      float4 og = make_float4(0.f, 0.f, 0.f, 0.f), ot = og;
-      float rs = 0.f;
+    auto run = [&](auto nz, auto nt) {
+      constexpr int NZ = decltype(nz)::value, NT = decltype(nt)::value;
+      for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < total4; q += (long)gridDim.x * 256) {
+        const int i = (int)(q / d4);
+        const long e = q << 2;
+        float4 og = make_float4(0.f, 0.f, 0.f, 0.f), ot = og;
+        float rs = 0.f;
+        float4 th;
+        if constexpr (NZ > 0) {
+          float4 a[NZ], b[NT > 0 ? NT : 1];
+          float r[NZ];
+#pragma unroll
+          for (int z = 0; z < NZ; ++z) {
+            a[z] = *reinterpret_cast<const float4*>(OG + z * zs + e);
+            r[z] = RS[(size_t)z * n_local + i];
+          }
+          th = theta4(T + (size_t)row0 * d + e);
+#pragma unroll
+          for (int z = 0; z < NT; ++z) b[z] = *reinterpret_cast<const float4*>(OT + z * zs + e);
+#pragma unroll
+          for (int z = 0; z < NZ; ++z) {
+            og.x += a[z].x; og.y += a[z].y; og.z += a[z].z; og.w += a[z].w;
+            if (z < NT) { ot.x += b[z].x; ot.y += b[z].y; ot.z += b[z].z; ot.w += b[z].w; }
+            rs += r[z];
+          }
+        } else {
 #pragma unroll 8
-      for (int z = 0; z < split; ++z) {   // unrolled: the loads of eight slices in flight, the sums in the same order
-        const float4 a = *reinterpret_cast<const float4*>(OG + z * zs + e);
-        og.x += a.x; og.y += a.y; og.z += a.z; og.w += a.w;
-        if (FOLD ? need_t && z < tsplit : true) {   // (FOLD: K.theta comes in tsplit = 1 range)
-          const float4 b = *reinterpret_cast<const float4*>(OT + z * zs + e);
-          ot.x += b.x; ot.y += b.y; ot.z += b.z; ot.w += b.w;
+          for (int z = 0; z < split; ++z) {   // unrolled: the loads of eight slices in flight, the sums in the same order
+            const float4 a = *reinterpret_cast<const float4*>(OG + z * zs + e);
+            og.x += a.x; og.y += a.y; og.z += a.z; og.w += a.w;
+            if (FOLD ? need_t && z < tsplit : true) {
+              const float4 b = *reinterpret_cast<const float4*>(OT + z * zs + e);
+              ot.x += b.x; ot.y += b.y; ot.z += b.z; ot.w += b.w;
+            }
+            rs += RS[(size_t)z * n_local + i];
+          }
+          th = theta4(T + (size_t)row0 * d + e);
         }
-        rs += RS[(size_t)z * n_local + i];
+        // rowsum * theta - K.theta, written out the way the single-loop kernel was compiled (folded: the rounded product,
+        // which phi shares, then the difference; unfolded: one fma), so that dK does not move with the compiler's choice
+        // of contraction in each specialised loop
+        auto rt_minus = [&](float t, float o) {
+          if constexpr (FOLD) {
+#pragma clang fp contract(off)
+            const float m = rs * t;
+            return m - o;
+          } else {
+            return __builtin_fmaf(rs, t, -o);
+          }
+        };
+        float4 dk, ph;
+        dk.x = rt_minus(th.x, ot.x) / h2; dk.y = rt_minus(th.y, ot.y) / h2; dk.z = rt_minus(th.z, ot.z) / h2; dk.w = rt_minus(th.w, ot.w) / h2;
+        if constexpr (FOLD) {
+          ph.x = (og.x + rs * th.x / h2) / fn; ph.y = (og.y + rs * th.y / h2) / fn;
+          ph.z = (og.z + rs * th.z / h2) / fn; ph.w = (og.w + rs * th.w / h2) / fn;
+        } else {
+          ph.x = (og.x + dk.x) / fn; ph.y = (og.y + dk.y) / fn; ph.z = (og.z + dk.z) / fn; ph.w = (og.w + dk.w) / fn;
+        }
+        *reinterpret_cast<float4*>(phi + e) = ph;
+        if (dK) *reinterpret_cast<float4*>(dK + e) = dk;
+        // (the square of a float is exact in fp64, so a fused and an unfused x * x + y * y round alike: whatever the compiler
+        // contracts in one specialised loop and not in another, |phi|^2 is the same to the bit.  The statistic's terms below
+        // are not of that kind; nothing compares them bit for bit between the forms.)
+        sq += ((double)ph.x * (double)ph.x + (double)ph.y * (double)ph.y) + ((double)ph.z * (double)ph.z + (double)ph.w * (double)ph.w);
+        if constexpr (KSD) {
+          const float4 g = theta4(G + (size_t)row0 * d + e);
+          ksd_terms(g.x, kg(og.x, ot.x), ot.x, th.x, rs, ih, ks, kd);
+          ksd_terms(g.y, kg(og.y, ot.y), ot.y, th.y, rs, ih, ks, kd);
+          ksd_terms(g.z, kg(og.z, ot.z), ot.z, th.z, rs, ih, ks, kd);
+          ksd_terms(g.w, kg(og.w, ot.w), ot.w, th.w, rs, ih, ks, kd);
+        }
       }
-      const float4 th = theta4(T + (size_t)row0 * d + e);
-      float4 dk, ph;
-      dk.x = (rs * th.x - ot.x) / h2; dk.y = (rs * th.y - ot.y) / h2; dk.z = (rs * th.z - ot.z) / h2; dk.w = (rs * th.w - ot.w) / h2;
-      if constexpr (FOLD) {
-        ph.x = (og.x + rs * th.x / h2) / fn; ph.y = (og.y + rs * th.y / h2) / fn;
-        ph.z = (og.z + rs * th.z / h2) / fn; ph.w = (og.w + rs * th.w / h2) / fn;
-      } else {
-        ph.x = (og.x + dk.x) / fn; ph.y = (og.y + dk.y) / fn; ph.z = (og.z + dk.z) / fn; ph.w = (og.w + dk.w) / fn;
-      }
-      *reinterpret_cast<float4*>(phi + e) = ph;
-      if (dK) *reinterpret_cast<float4*>(dK + e) = dk;
-      sq += ((double)ph.x * (double)ph.x + (double)ph.y * (double)ph.y) + ((double)ph.z * (double)ph.z + (double)ph.w * (double)ph.w);
-      if constexpr (KSD) {
-        const float4 g = theta4(G + (size_t)row0 * d + e);
-        ksd_terms(g.x, kg(og.x, ot.x), ot.x, th.x, rs, ih, ks, kd);
-        ksd_terms(g.y, kg(og.y, ot.y), ot.y, th.y, rs, ih, ks, kd);
-        ksd_terms(g.z, kg(og.z, ot.z), ot.z, th.z, rs, ih, ks, kd);
-        ksd_terms(g.w, kg(og.w, ot.w), ot.w, th.w, rs, ih, ks, kd);
-      }
-    }
+    };
+    using std::integral_constant;
+    auto run_nz = [&](auto nz) {   // (FOLD: K.theta comes in ONE range -- stein_step_views -- and only when something asks for it)
+      if constexpr (!FOLD) run(nz, nz);
+      else if (need_t) run(nz, integral_constant<int, 1>());
+      else run(nz, integral_constant<int, 0>());
+    };
+    if (split == 1) run_nz(integral_constant<int, 1>());
+    else if (split == 2) run_nz(integral_constant<int, 2>());
+    else if (split == 4) run_nz(integral_constant<int, 4>());
+    else run(integral_constant<int, 0>(), integral_constant<int, 0>());
   } else {
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
       const int i = (int)(e / d);
@@ -235,6 +287,15 @@ static int sum_partials(const double* part, int count, bool ksd, double* out, hi
 // ================================================================================================
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// test hook (per calling thread; tests/test_gpu_glue.py): j ranges the folded contraction's plan asks for, 0 = its own rule.
+// A range still starts on a multiple of 128 columns and empty tails are dropped: stein_layout_fold_ranges tells the outcome.
+static thread_local int g_fold_split = 0;
+extern "C" int stein_debug_fold_split(int ranges) {
+  if (ranges < 0 || ranges > 65535) return fail(STEIN_E_BADARG, "ranges %d", ranges);
+  g_fold_split = ranges;
+  return STEIN_OK;
+}
+
 int stein_make_layout(int64_t n_local, int64_t n, int64_t d, int dtype, int flags, SteinLayout* L) {
   if (n < 2) return fail(STEIN_E_BADARG, "n = %lld: the bandwidth divides by ln(n), need n >= 2", (long long)n);
   if (d < 1 || n_local < 1 || n_local > n) return fail(STEIN_E_SHAPE, "bad shape n_local=%lld n=%lld d=%lld", (long long)n_local, (long long)n, (long long)d);
@@ -256,10 +317,11 @@ int stein_make_layout(int64_t n_local, int64_t n, int64_t d, int dtype, int flag
   const double resident = x3 ? 256.0 : 768.0;
   int64_t max_split = jt / 8 > 0 ? jt / 8 : 1;
   if (max_split > 16) max_split = 16;
-  auto choose_split = [&](int64_t base_wgs, int64_t* jchunk_out) {
+  auto choose_split = [&](int64_t base_wgs, int64_t* jchunk_out, int64_t forced = 0) {
     int64_t split = 1;
     double best = -1.0;
-    for (int64_t s = 1; s <= max_split; ++s) {
+    if (forced > 0) split = forced < jt ? forced : jt;   // (test hook: the ranges asked for; the rounding below still holds)
+    for (int64_t s = 1; forced <= 0 && s <= max_split; ++s) {
       const double rounds = (double)(base_wgs * s) / resident;
       const double eff = rounds / ceil(rounds) - 0.004 * (double)(s - 1);
       if (eff > best + 1e-9) { best = eff; split = s; }
@@ -321,7 +383,7 @@ int stein_make_layout(int64_t n_local, int64_t n, int64_t d, int dtype, int flag
   L->fsplit = L->fjchunk = 0;
   size_t fold_extra = 0;
   if (L->fold) {
-    L->fsplit = choose_split(L->tiles_m * ((L->cblocks + 1) / 2), &L->fjchunk);
+    L->fsplit = choose_split(L->tiles_m * ((L->cblocks + 1) / 2), &L->fjchunk, g_fold_split);
     const size_t ow = align_up((size_t)L->fsplit * n_local * d * 4, 256), ot = align_up((size_t)n_local * d * 4, 256),
                  rs = align_up((size_t)L->fsplit * n_local * 4, 256);
     if (ow <= L->off[STEIN_WS_PART_RS] - L->off[STEIN_WS_PART_G] && ot + rs <= t3) {
@@ -404,6 +466,15 @@ extern "C" int stein_workspace_layout(int64_t n_local, int64_t n, int64_t d, int
   extra[STEIN_WSX_SPLIT] = L.split;
   extra[STEIN_WSX_SQ_BLOCKS] = L.sq_blocks;
   extra[STEIN_WSX_HIST_BINS] = STEIN_HIST_BINS;
+  return STEIN_OK;
+}
+
+extern "C" int stein_layout_fold_ranges(int64_t n_local, int64_t n, int64_t d, int dtype, int flags, int* out) {
+  if (!out) return fail(STEIN_E_BADARG, "out is NULL");
+  SteinLayout L;
+  int rc = stein_make_layout(n_local, n, d, dtype, flags, &L);
+  if (rc) return rc;
+  *out = L.fold ? (int)L.fsplit : 0;
   return STEIN_OK;
 }
 
@@ -913,7 +984,7 @@ extern "C" int stein_svgd_phi(const void* theta_all, const void* score_all, int6
   const int sf = STEIN_STAGE_SYMMETRIC | ((flags & STEIN_FLAG_TILE_DISTANCE) ? STEIN_STAGE_TILES : 0);
   if ((rc = distance_stage(v, b, theta_all, sf, true, s))) return rc;
   if ((rc = clk.mark(STEIN_T_MEDIAN, s))) return rc;
-  if ((rc = stein_fused_select(v, n, h2_out, s))) return rc;
+  if ((rc = stein_fused_select(v, n, d, h2_out, theta_all, score_all, s))) return rc;
   // the split path's symmetric distance pass stores only the tiles on and above the diagonal
   const bool upper = v.planes != nullptr;
   if (K_out && (rc = stein_kernel_matrix(v.D, L.ld_dist, n_local, n, h2_out, K_out, n,
