@@ -94,19 +94,33 @@ __global__ __launch_bounds__(SM_THREADS) void k_svgd_small(const float* __restri
       __syncthreads();
       if (mine) {
         const int cend = min(ck, d - c0);
+        auto chunk = [&](float (&s)[RR][RR], float (&sa)[RR], float (&sb)[RR]) {
 #pragma unroll 8
-        for (int c = 0; c < cend; ++c) {
-          float a[RR], b[RR];
+          for (int c = 0; c < cend; ++c) {
+            float a[RR], b[RR];
 #pragma unroll
-          for (int r = 0; r < RR; ++r) {
-            a[r] = pa[r][c]; b[r] = pb[r][c];
-            na[r] = fmaf(a[r], a[r], na[r]);
-            nb[r] = fmaf(b[r], b[r], nb[r]);
+            for (int r = 0; r < RR; ++r) {
+              a[r] = pa[r][c]; b[r] = pb[r][c];
+              sa[r] = fmaf(a[r], a[r], sa[r]);
+              sb[r] = fmaf(b[r], b[r], sb[r]);
+            }
+#pragma unroll
+            for (int r = 0; r < RR; ++r)
+#pragma unroll
+              for (int q = 0; q < RR; ++q) s[r][q] = fmaf(a[r], b[q], s[r][q]);
           }
-#pragma unroll
-          for (int r = 0; r < RR; ++r)
-#pragma unroll
-            for (int q = 0; q < RR; ++q) acc[r][q] = fmaf(a[r], b[q], acc[r][q]);
+        };
+        // n <= 32 is where d goes to 32768 (n^2 d <= 2.2e6 keeps d <= 2020 from n = 33 on): there every chunk is summed
+        // on its own and then added to the running sums, so the rounding error of a norm or a dot product grows with the
+        // chunk width plus the number of chunks and not with d.  (One chain over all 32768 columns of 2 particles left
+        // h2 3.1e-6 off fp64 and 4.6e-6 off the tiled kernels'; summed per chunk it is 1.0e-7 and 1.4e-6, measured.
+        // One chunk gives the same bits either way.)
+        if constexpr (RR == 1) {
+          float s[1][1] = {{0.f}}, sa[1] = {0.f}, sb[1] = {0.f};
+          chunk(s, sa, sb);
+          acc[0][0] += s[0][0]; na[0] += sa[0]; nb[0] += sb[0];
+        } else {
+          chunk(acc, na, nb);
         }
       }
     }
