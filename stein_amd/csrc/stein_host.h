@@ -15,6 +15,18 @@ static inline int grid_for(long count, int cap) {
   return (int)b;
 }
 
+static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// Workgroups the chip holds at once of a kernel that runs one per CU (128 KB of LDS each: the split-precision contraction,
+// k_phi_stream).  The MI355X's 256 CUs, as a constant: the plans and the workspace sizes are host arithmetic.
+constexpr double RESIDENT_ONE_PER_CU = 256.0;
+
+// the size limits every layout shares: int indices of rows and columns, and n d elements within 2^40
+static inline int stein_check_size(int64_t n, int64_t d) {
+  if (n > (1ll << 30) || d > (1ll << 24) || n * d > (1ll << 40)) return fail(STEIN_E_SHAPE, "shape too large");
+  return STEIN_OK;
+}
+
 // addresses inside the SELECT section (SelState | SpecState | FuseState) and the SPEC section (slots | entries | table)
 static inline SpecState* spec_of(void* select_state) { return (SpecState*)((char*)select_state + sizeof(SelState)); }
 static inline FuseState* fuse_of(void* select_state) { return (FuseState*)((char*)spec_of(select_state) + sizeof(SpecState)); }

@@ -9,6 +9,11 @@
 //   k_phi_stream        distance tile -> P = exp2(c D + 14) -> O += P.W, running rowsum(P); D and K never reach memory
 //   k_stream_finish     sums the j ranges in order, phi = (K.W + rowsum(K) theta / h2) / n, |phi|^2 block partials (fp64)
 //   k_stream_sqsum      one workgroup: the block partials -> sqnorm_out
+// The P image's swizzle, the fp16 split and the exponent offset (pswz, cvt_pk_f16, f16_resid_lo / _hi, PEXP_H2) are
+// stein_x3_dev.h's, the ones the stored-D contraction uses; the size limits, align_up and the resident-workgroup count are
+// stein_host.h's, shared with stein_make_layout.  The finish pass stays a kernel of this file although k_phi_finish's FOLD
+// form (steinhip.hip) gives the same bits: at 8 j ranges that kernel takes its generic loop and the step measured slower
+// ("streaming step").
 //
 // k_phi_stream: a 512-thread workgroup (8 waves, two per SIMD) owns 128 rows of particles x one column group of W (two
 // 128-column blocks) x one range of 128-column j tiles.  Per j tile:
@@ -46,29 +51,6 @@ constexpr int ST_COLS = 256;              // columns of W per column group
 constexpr int ST_PLN = ST_ROWS * XROW;    // one plane of one 32-deep k tile of P in LDS: 8 KB
 constexpr int ST_KTB = 2 * ST_PLN;        // hi and lo plane
 constexpr int ST_BUF = (ST_JT / 32) * ST_KTB;   // one P image: 64 KB; two of them
-constexpr int ST_PEXP = 14;               // P = exp2(c D + 14): the fp16 range of the stored-D contraction (PEXP_H2)
-constexpr double ST_RESIDENT = 256.0;     // workgroups the chip holds at once (one per CU: 128 KB of LDS each).  The MI355X's 256
-                                          // CUs, as a constant: the plan and the workspace size are host arithmetic
-                                          // (stein_make_layout's contraction plan does the same)
-
-// the P image's per-row chunk permutation and the fp16 split of a pair: the stored-D contraction's (stein_x3.hip), so that
-// both paths do the same arithmetic per entry
-__device__ __forceinline__ int st_pswz(int row, int chunk) { return (chunk ^ ((0x78 >> (((row >> 2) & 3) * 2)) & 3)) * 16; }
-__device__ __forceinline__ u32 st_cvt_pk_f16(float lo, float hi) {   // round-to-nearest-even, lo -> bits 15:0
-  u32 r;
-  asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-__device__ __forceinline__ float st_resid_lo(u32 h, float x) {   // x - (fp16 in the low half of h), exact
-  float r;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(x));
-  return r;
-}
-__device__ __forceinline__ float st_resid_hi(u32 h, float x) {
-  float r;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(x));
-  return r;
-}
 
 // The distance phase of one 128 x 128 tile, shared by k_phi_stream and k_stream_hist (one body: both kernels form every
 // S value in the same order, so the streaming median is the median of the very D values the step exponentiates).  Wave
@@ -140,7 +122,7 @@ __global__ __launch_bounds__(ST_THREADS) void k_phi_stream(const u16* __restrict
 
   const u16* __restrict__ ta = T3 + (size_t)tile_m * ntk * 3 * XTILE_E + (wr * 2) * 512 + lane * 8;
   const u16* __restrict__ wb = Wt3 + (size_t)gl * ntj * 3 * XTILE_E + wcol * 32 + lane * 8;
-  const int aoff = l15 * XROW + st_pswz(l15, lq);
+  const int aoff = l15 * XROW + pswz(l15, lq);
 
   for (int jt = jt0; jt < jt1; ++jt) {
     unsigned char* buf = smem + ((jt - jt0) & 1) * ST_BUF;
@@ -161,15 +143,15 @@ __global__ __launch_bounds__(ST_THREADS) void k_phi_stream(const u16* __restrict
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const float dv = (ri[ib] + rj[e]) - two_s * s[jb][ib][e];
-          q[e] = __builtin_amdgcn_exp2f(__builtin_fmaf(cexp, dv, (float)ST_PEXP));
+          q[e] = __builtin_amdgcn_exp2f(__builtin_fmaf(cexp, dv, (float)PEXP_H2));
           q[e] = (j0 + jc + e < n) ? q[e] : 0.f;
         }
         rs[ib] += (q[0] + q[1]) + (q[2] + q[3]);
-        const u32 h0 = st_cvt_pk_f16(q[0], q[1]), h1 = st_cvt_pk_f16(q[2], q[3]);
-        const u32 o0 = st_cvt_pk_f16(st_resid_lo(h0, q[0]), st_resid_hi(h0, q[1]));
-        const u32 o1 = st_cvt_pk_f16(st_resid_lo(h1, q[2]), st_resid_hi(h1, q[3]));
+        const u32 h0 = cvt_pk_f16(q[0], q[1]), h1 = cvt_pk_f16(q[2], q[3]);
+        const u32 o0 = cvt_pk_f16(f16_resid_lo(h0, q[0]), f16_resid_hi(h0, q[1]));
+        const u32 o1 = cvt_pk_f16(f16_resid_lo(h1, q[2]), f16_resid_hi(h1, q[3]));
         const int row = wr * 32 + ib * 16 + l15;
-        unsigned char* dst = buf + (jc >> 5) * ST_KTB + row * XROW + st_pswz(row, (jc & 31) >> 3) + (jc & 4) * 2;
+        unsigned char* dst = buf + (jc >> 5) * ST_KTB + row * XROW + pswz(row, (jc & 31) >> 3) + (jc & 4) * 2;
         *reinterpret_cast<uint2*>(dst) = make_uint2(h0, h1);
         *reinterpret_cast<uint2*>(dst + ST_PLN) = make_uint2(o0, o1);
       }
@@ -405,15 +387,12 @@ struct StreamLayout {
   size_t r, sc, t3, wt3, o, rs, sq, total;       // byte offsets, 256-byte aligned
 };
 
-static inline size_t st_align(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 static int stream_check_shape(int64_t n, int64_t d, int dtype, int flags) {
   if (dtype == STEIN_BF16) return fail(STEIN_E_UNSUPPORTED, "the streaming step takes fp32 inputs (STEIN_F32), not bf16");
   if (dtype != STEIN_F32) return fail(STEIN_E_UNSUPPORTED, "dtype %d", dtype);
   if (flags != 0) return fail(STEIN_E_BADARG, "the streaming step takes no flags, got 0x%x", flags);
   if (n < 1 || d < 1) return fail(STEIN_E_SHAPE, "bad shape n=%lld d=%lld", (long long)n, (long long)d);
-  if (n > (1ll << 30) || d > (1ll << 24) || n * d > (1ll << 40)) return fail(STEIN_E_SHAPE, "shape too large");
-  return STEIN_OK;
+  return stein_check_size(n, d);
 }
 
 // The plan: one workgroup per (row tile, column group, j range).  The j ranges fill the resident grid (one workgroup per CU)
@@ -426,20 +405,20 @@ static int stream_make_layout(int64_t n, int64_t d, StreamLayout* L) {
   L->cblocks = (d + 127) / 128;
   L->col_groups = (d + ST_COLS - 1) / ST_COLS;
   const int64_t jtiles = L->row_tiles;
-  int64_t want = g_stream_jsplit > 0 ? g_stream_jsplit : (int64_t)(ST_RESIDENT / (double)(L->row_tiles * L->col_groups));
+  int64_t want = g_stream_jsplit > 0 ? g_stream_jsplit : (int64_t)(RESIDENT_ONE_PER_CU / (double)(L->row_tiles * L->col_groups));
   if (want < 1) want = 1;
   if (want > jtiles) want = jtiles;
   L->jtiles_per = (jtiles + want - 1) / want;
   L->jsplit = (jtiles + L->jtiles_per - 1) / L->jtiles_per;
   L->rows = L->row_tiles * ST_ROWS;
   L->nk = L->rows;
-  L->dk = (int64_t)st_align((size_t)d, 32);
-  L->dc = (int64_t)st_align((size_t)d, 128);
+  L->dk = (int64_t)align_up((size_t)d, 32);
+  L->dc = (int64_t)align_up((size_t)d, 128);
   int64_t sqb = (n * d + 1023) / 1024;
   if (sqb > 1024) sqb = 1024;
   L->sq_blocks = sqb;
   size_t at = 0;
-  auto put = [&](size_t bytes) { const size_t o = at; at = st_align(at + bytes, 256); return o; };
+  auto put = [&](size_t bytes) { const size_t o = at; at = align_up(at + bytes, 256); return o; };
   L->r = put((size_t)L->rows * 4);
   L->sc = put((size_t)(6 * L->dc + 4) * 4);
   L->t3 = put((size_t)3 * L->rows * L->dk * 2);
@@ -450,6 +429,32 @@ static int stream_make_layout(int64_t n, int64_t d, StreamLayout* L) {
   L->total = at;
   if (L->row_tiles * L->col_groups * L->jsplit > 0x7fffffffll) return fail(STEIN_E_SHAPE, "too many tiles");
   return STEIN_OK;
+}
+
+// Every address the streaming entry points use, formed once: of a stored-D layout only the planes' extents; the planes the
+// split launchers take; and the step's partial sums (K.W of the j ranges in OG, their rowsum(K) in RS, the |phi|^2 block
+// partials in SQ; no K.theta: nothing here asks for dK or the statistic).
+// The median passes StreamMedianLayout's hist / sel offsets: its histograms and select state lie where the step keeps W's
+// planes and partial sums, which that call never touches.
+static StepViews stream_views(const StreamLayout& L, void* workspace, size_t hist_at = 0, size_t sel_at = 0) {
+  char* ws = (char*)workspace;
+  StepViews v{};
+  v.L.x3_rows = L.rows; v.L.x3_dk = L.dk; v.L.x3_dc = L.dc; v.L.x3_nk = L.nk;
+  v.r = (float*)(ws + L.r);
+  v.planes = ws;
+  v.T3 = (unsigned short*)(ws + L.t3);
+  v.Gt3 = (unsigned short*)(ws + L.wt3);
+  v.sc = (float*)(ws + L.sc);
+  v.cmax = (u32*)(v.sc + x3_sc_cmax(L.dc));
+  v.two_s = v.sc + x3_sc_two_s(L.dc);
+  v.OG = (float*)(ws + L.o);
+  v.RS = (float*)(ws + L.rs);
+  v.SQ = (double*)(ws + L.sq);
+  if (sel_at) {
+    v.hist = (u64*)(ws + hist_at);
+    v.sel = (SelState*)(ws + sel_at);
+  }
+  return v;
 }
 
 extern "C" int stein_debug_stream_jsplit(int jsplit) {
@@ -492,20 +497,7 @@ extern "C" int stein_svgd_phi_stream(const void* theta, const void* score, int64
   if (ws_bytes < L.total) return fail(STEIN_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L.total);
   if ((rc = stein_take_device_error())) return rc;   // a kernel of an earlier call on this device gave up: say so now
   hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  // the views the split launchers take: the planes' extents and addresses, nothing else of a stored-D layout
-  StepViews v{};
-  v.L.x3_rows = L.rows; v.L.x3_dk = L.dk; v.L.x3_dc = L.dc; v.L.x3_nk = L.nk;
-  v.r = (float*)(ws + L.r);
-  v.planes = ws;
-  v.T3 = (unsigned short*)(ws + L.t3);
-  v.Gt3 = (unsigned short*)(ws + L.wt3);
-  v.sc = (float*)(ws + L.sc);
-  v.cmax = (u32*)(v.sc + x3_sc_cmax(L.dc));
-  v.two_s = v.sc + x3_sc_two_s(L.dc);
-  float* O = (float*)(ws + L.o);
-  float* RS = (float*)(ws + L.rs);
-  double* SQ = (double*)(ws + L.sq);
+  const StepViews v = stream_views(L, workspace);
   // 1. row norms (the padding rows of r are never read into a stored result), column maxima -> scales
   // 2. theta's row-major planes (fold form of the split: no transposed image, the score only feeds the maxima)
   if ((rc = stein_rownorms(theta, n, d, dtype, v.r, stream))) return rc;
@@ -516,15 +508,15 @@ extern "C" int stein_svgd_phi_stream(const void* theta, const void* score, int64
   // 4. the streaming contraction
   const long nblk = (long)(L.row_tiles * L.col_groups * L.jsplit);
   hipLaunchKernelGGL(k_phi_stream, dim3((unsigned)nblk), dim3(ST_THREADS), 0, s, v.T3, (int)(L.dk / 32), v.Gt3,
-                     (long)(L.nk / 32), v.r, v.sc, (int)L.dc, h2_in, O, RS, (int)n, (int)d, (int)L.row_tiles,
+                     (long)(L.nk / 32), v.r, v.sc, (int)L.dc, h2_in, v.OG, v.RS, (int)n, (int)d, (int)L.row_tiles,
                      (int)L.col_groups, (int)L.cblocks, (int)L.row_tiles, (int)L.jtiles_per);
   LAUNCH_CHECK("k_phi_stream");
   // 5. finish
   const int vec = d % 4 == 0 && (((uintptr_t)theta | (uintptr_t)phi) & 15) == 0;
-  hipLaunchKernelGGL(k_stream_finish, dim3((unsigned)L.sq_blocks), dim3(256), 0, s, O, RS, (const float*)theta, h2_in, phi,
-                     SQ, (int)n, (int)d, (int)L.jsplit, vec);
+  hipLaunchKernelGGL(k_stream_finish, dim3((unsigned)L.sq_blocks), dim3(256), 0, s, v.OG, v.RS, (const float*)theta, h2_in, phi,
+                     v.SQ, (int)n, (int)d, (int)L.jsplit, vec);
   LAUNCH_CHECK("k_stream_finish");
-  hipLaunchKernelGGL(k_stream_sqsum, dim3(1), dim3(256), 0, s, SQ, (int)L.sq_blocks, sqnorm_out);
+  hipLaunchKernelGGL(k_stream_sqsum, dim3(1), dim3(256), 0, s, v.SQ, (int)L.sq_blocks, sqnorm_out);
   LAUNCH_CHECK("k_stream_sqsum");
   return STEIN_OK;
 }
@@ -554,11 +546,11 @@ static int stream_median_make_layout(int64_t n, int64_t d, int dtype, int flags,
   if (n < 2) return fail(STEIN_E_SHAPE, "n = %lld: the median-heuristic bandwidth divides by ln n; need n >= 2", (long long)n);
   if ((rc = stream_make_layout(n, d, &M->L))) return rc;
   M->hist = M->L.wt3;
-  M->sel = M->hist + st_align(SH_HIST_BYTES, 256);
+  M->sel = M->hist + align_up(SH_HIST_BYTES, 256);
   M->total = M->sel + 256;
   const int64_t nt = M->L.row_tiles;
   M->tiles = nt * (nt + 1) / 2;
-  const int64_t want = g_stream_median_grid > 0 ? g_stream_median_grid : (int64_t)SH_WG_PER_CU * (int64_t)ST_RESIDENT;
+  const int64_t want = g_stream_median_grid > 0 ? g_stream_median_grid : (int64_t)SH_WG_PER_CU * (int64_t)RESIDENT_ONE_PER_CU;
   M->blocks = g_stream_median_grid > 0 ? want : (M->tiles < want ? M->tiles : want);
   return STEIN_OK;
 }
@@ -590,10 +582,9 @@ extern "C" int stein_stream_median_plan(int64_t n, int64_t d, size_t* hist_offse
 }
 
 template <int LEVEL>
-static void launch_stream_hist(const StreamMedianLayout& M, const StepViews& v, const SelState* st, u64* hist, int64_t n,
-                               hipStream_t s) {
+static void launch_stream_hist(const StreamMedianLayout& M, const StepViews& v, int64_t n, hipStream_t s) {
   hipLaunchKernelGGL((k_stream_hist<LEVEL>), dim3((unsigned)M.blocks), dim3(ST_THREADS), 0, s, v.T3, (int)(M.L.dk / 32), v.r,
-                     v.sc, (int)M.L.dc, st, hist + (size_t)LEVEL * 2 * STEIN_HIST_BINS, (int)n, (int)M.L.row_tiles,
+                     v.sc, (int)M.L.dc, v.sel, v.hist + (size_t)LEVEL * 2 * STEIN_HIST_BINS, (int)n, (int)M.L.row_tiles,
                      (long)M.tiles, SH_FLUSH_TILES);
 }
 
@@ -608,17 +599,7 @@ extern "C" int stein_stream_median(const void* theta, int64_t n, int64_t d, int 
   if (ws_bytes < M.total) return fail(STEIN_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, M.total);
   if ((rc = stein_take_device_error())) return rc;
   hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  StepViews v{};
-  v.L.x3_rows = L.rows; v.L.x3_dk = L.dk; v.L.x3_dc = L.dc; v.L.x3_nk = L.nk;
-  v.r = (float*)(ws + L.r);
-  v.planes = ws;
-  v.T3 = (unsigned short*)(ws + L.t3);
-  v.sc = (float*)(ws + L.sc);
-  v.cmax = (u32*)(v.sc + x3_sc_cmax(L.dc));
-  v.two_s = v.sc + x3_sc_two_s(L.dc);
-  u64* hist = (u64*)(ws + M.hist);
-  SelState* sel = (SelState*)(ws + M.sel);
+  const StepViews v = stream_views(L, workspace, M.hist, M.sel);
   // 1. row norms; 2. theta's scales and row-major planes, as the step builds them.  There is no score: the split takes a
   // NULL score as "leave that half of the column maxima alone", and k_make_scales reads both halves -- the score's only
   // feed scales this call never uses, but they are zeroed here so that nothing reads what the workspace held.
@@ -627,14 +608,14 @@ extern "C" int stein_stream_median(const void* theta, int64_t n, int64_t d, int 
   const SplitFused only_rows{nullptr, nullptr, 1};
   if ((rc = stein_x3_split(v, theta, nullptr, dtype, n, d, s, &only_rows))) return rc;
   // 3. select state for n^2 entries, histograms zeroed; 4. three levels, k_resolve between them
-  if ((rc = stein_median_begin(hist, sel, n * n, stream))) return rc;
-  launch_stream_hist<0>(M, v, sel, hist, n, s);
+  if ((rc = stein_median_begin(v.hist, v.sel, n * n, stream))) return rc;
+  launch_stream_hist<0>(M, v, n, s);
   LAUNCH_CHECK("k_stream_hist<0>");
-  if ((rc = stein_median_resolve(hist, 0, n, sel, h2_out, median_out, stream))) return rc;
-  launch_stream_hist<1>(M, v, sel, hist, n, s);
+  if ((rc = stein_median_resolve(v.hist, 0, n, v.sel, h2_out, median_out, stream))) return rc;
+  launch_stream_hist<1>(M, v, n, s);
   LAUNCH_CHECK("k_stream_hist<1>");
-  if ((rc = stein_median_resolve(hist, 1, n, sel, h2_out, median_out, stream))) return rc;
-  launch_stream_hist<2>(M, v, sel, hist, n, s);
+  if ((rc = stein_median_resolve(v.hist, 1, n, v.sel, h2_out, median_out, stream))) return rc;
+  launch_stream_hist<2>(M, v, n, s);
   LAUNCH_CHECK("k_stream_hist<2>");
-  return stein_median_resolve(hist, 2, n, sel, h2_out, median_out, stream);
+  return stein_median_resolve(v.hist, 2, n, v.sel, h2_out, median_out, stream);
 }

@@ -58,18 +58,11 @@
 #include <stdlib.h>
 
 #include "stein_x3_dev.h"
-constexpr int PEXP_H2 = 14;   // KIND 2: P = exp2(c D + 14), in (0, 2^14] (fp16 normal range down to P = 2^-28)
 template <int KIND> struct SplitTraits { static constexpr int pexp = KIND == 2 ? PEXP_H2 : 0; };
 
 #include <type_traits>
 
 __device__ __forceinline__ int xswz(int row, int chunk) { return (chunk ^ ((row >> 2) & 3)) * 16; }
-// LDS image of a P plane in the contraction: [128 rows][64 B], chunk c of row r at 16 * (c ^ g((r >> 2) & 3)) with
-// g = {0, 2, 3, 1}.  The 16x16x32 A fragment (lane l: row l & 15, chunk l >> 4) is read by ds_read_b128 in the lane
-// groups {0-3,12-15,20-27}, {4-11,16-19,28-31}, ...: each holds the 16 rows once, with chunk c for rows 0-3 / 12-15
-// and c + 1 for rows 4-11 (or the reverse); this g makes the four 16-byte slots of every row-mod-4 class distinct in
-// all four groups.  Writes (16 lanes = 2 whole rows) are conflict-free under any per-row permutation.
-__device__ __forceinline__ int pswz(int row, int chunk) { return (chunk ^ ((0x78 >> (((row >> 2) & 3) * 2)) & 3)) * 16; }
 
 // ------------------------------------------------------------------------------------------------
 // splitting
@@ -77,23 +70,6 @@ __device__ __forceinline__ int pswz(int row, int chunk) { return (chunk ^ ((0x78
 __device__ __forceinline__ u32 cvt_pk_bf16(float lo, float hi) {   // round-to-nearest-even, lo -> bits 15:0
   u32 r;
   asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-
-__device__ __forceinline__ u32 cvt_pk_f16(float lo, float hi) {    // round-to-nearest-even, lo -> bits 15:0
-  u32 r;
-  asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-// x - (fp16 in the low / high half of h), one instruction, exact
-__device__ __forceinline__ float f16_resid_lo(u32 h, float x) {
-  float r;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(x));
-  return r;
-}
-__device__ __forceinline__ float f16_resid_hi(u32 h, float x) {
-  float r;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(x));
   return r;
 }
 

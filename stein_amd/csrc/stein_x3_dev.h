@@ -1,5 +1,6 @@
-// stein_x3_dev.h -- device helpers shared by the split-precision kernels (stein_x3.hip, stein_dpanel.hip): vector types,
-// the operand-plane geometry, the 16x16x32 products and the hand-counted streamed loads.
+// stein_x3_dev.h -- device helpers shared by the split-precision kernels (stein_x3.hip, stein_dpanel.hip, stein_stream.hip):
+// vector types, the operand-plane geometry, the 16x16x32 products, the P image's swizzle and fp16 split, and the
+// hand-counted streamed loads.
 #pragma once
 #include "stein_common.h"
 
@@ -34,6 +35,32 @@ __device__ __forceinline__ f32x4 x3_products16(const u32x4 (&a)[3], const u32x4 
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(X3_HF(a[0]), X3_HF(b[0]), c, 0, 0, 0);
   }
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(X3_BF(a[0]), X3_BF(b[0]), c, 0, 0, 0);
+}
+
+// ---- the P image of the contraction and its fp16 split (stein_x3.hip's stored-D kernels and k_phi_stream: one statement,
+// so that both paths do the same arithmetic per entry) -----------------------------------------------------------------
+constexpr int PEXP_H2 = 14;   // KIND 2: P = exp2(c D + 14), in (0, 2^14] (fp16 normal range down to P = 2^-28)
+// LDS image of a P plane in the contraction: [128 rows][64 B], chunk c of row r at 16 * (c ^ g((r >> 2) & 3)) with
+// g = {0, 2, 3, 1}.  The 16x16x32 A fragment (lane l: row l & 15, chunk l >> 4) is read by ds_read_b128 in the lane
+// groups {0-3,12-15,20-27}, {4-11,16-19,28-31}, ...: each holds the 16 rows once, with chunk c for rows 0-3 / 12-15
+// and c + 1 for rows 4-11 (or the reverse); this g makes the four 16-byte slots of every row-mod-4 class distinct in
+// all four groups.  Writes (16 lanes = 2 whole rows) are conflict-free under any per-row permutation.
+__device__ __forceinline__ int pswz(int row, int chunk) { return (chunk ^ ((0x78 >> (((row >> 2) & 3) * 2)) & 3)) * 16; }
+__device__ __forceinline__ u32 cvt_pk_f16(float lo, float hi) {    // round-to-nearest-even, lo -> bits 15:0
+  u32 r;
+  asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+  return r;
+}
+// x - (fp16 in the low / high half of h), one instruction, exact
+__device__ __forceinline__ float f16_resid_lo(u32 h, float x) {
+  float r;
+  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(x));
+  return r;
+}
+__device__ __forceinline__ float f16_resid_hi(u32 h, float x) {
+  float r;
+  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(x));
+  return r;
 }
 
 // ---- streamed loads with hand-counted waits (the full story: stein_x3.hip, in front of k_phi_x3fs) -------------------

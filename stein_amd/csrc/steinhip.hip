@@ -285,8 +285,6 @@ static int sum_partials(const double* part, int count, bool ksd, double* out, hi
 // ================================================================================================
 // host side
 // ================================================================================================
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 // test hook (per calling thread; tests/test_gpu_glue.py): j ranges the folded contraction's plan asks for, 0 = its own rule.
 // A range still starts on a multiple of 128 columns and empty tails are dropped: stein_layout_fold_ranges tells the outcome.
 static thread_local int g_fold_split = 0;
@@ -299,7 +297,7 @@ extern "C" int stein_debug_fold_split(int ranges) {
 int stein_make_layout(int64_t n_local, int64_t n, int64_t d, int dtype, int flags, SteinLayout* L) {
   if (n < 2) return fail(STEIN_E_BADARG, "n = %lld: the bandwidth divides by ln(n), need n >= 2", (long long)n);
   if (d < 1 || n_local < 1 || n_local > n) return fail(STEIN_E_SHAPE, "bad shape n_local=%lld n=%lld d=%lld", (long long)n_local, (long long)n, (long long)d);
-  if (n > (1ll << 30) || d > (1ll << 24) || n * d > (1ll << 40)) return fail(STEIN_E_SHAPE, "shape too large");
+  if (int rc = stein_check_size(n, d)) return rc;
   if (dtype != STEIN_F32 && dtype != STEIN_BF16) return fail(STEIN_E_UNSUPPORTED, "dtype %d", dtype);
   if (flags & ~(STEIN_FLAG_X3 | STEIN_FLAG_TIMING | STEIN_FLAG_TILED | STEIN_FLAG_NO_WINDOW | STEIN_FLAG_RANK_WINDOW | STEIN_FLAG_TILE_DISTANCE | STEIN_FLAG_TIMING_CONTRACT | STEIN_FLAG_KSD | STEIN_FLAG_FOLD | STEIN_FLAG_NO_FOLD)) return fail(STEIN_E_BADARG, "unknown flags 0x%x", flags);
   if ((flags & STEIN_FLAG_FOLD) && (flags & STEIN_FLAG_NO_FOLD)) return fail(STEIN_E_BADARG, "STEIN_FLAG_FOLD and STEIN_FLAG_NO_FOLD exclude each other");
@@ -314,7 +312,7 @@ int stein_make_layout(int64_t n_local, int64_t n, int64_t d, int dtype, int flag
   // k_phi_partial runs 3 workgroups per CU (156 registers): 768 resident blocks.  Every block does the same
   // work, so the launch takes ceil(blocks / 768) rounds; pick the j-split that wastes least of the last round
   // (ties -> fewer splits, i.e. less partial traffic), keeping at least 8 j-tiles (256 columns) per split.
-  const double resident = x3 ? 256.0 : 768.0;
+  const double resident = x3 ? RESIDENT_ONE_PER_CU : 768.0;
   int64_t max_split = jt / 8 > 0 ? jt / 8 : 1;
   if (max_split > 16) max_split = 16;
   auto choose_split = [&](int64_t base_wgs, int64_t* jchunk_out, int64_t forced = 0) {
