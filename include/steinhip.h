@@ -190,7 +190,8 @@ int stein_svgd_phi(const void* theta_all, const void* score_all, int64_t n, int6
  *                  cannot validate a device scalar: h2 = 0 gives NaN phi, as on every other path.
  *   phi          : [n][d] float (unclipped);  sqnorm_out: double[1] = sum(phi^2), what stein_apply_* read
  *   flags        : must be 0 (STEIN_E_BADARG otherwise).  n >= 1 (no ln n here), d >= 1.
- * Limits of this entry: fp32 inputs, one rank (all n rows), no K_out / dK_out, no Stein discrepancy.  d > 256 is taken
+ * Limits of this entry: fp32 inputs, one rank (all n rows), no K_out / dK_out; the Stein discrepancy at this bandwidth is
+ * stein_svgd_phi_stream_ksd's, below.  d > 256 is taken
  * in ceil(d / 256) column groups, each of which recomputes the distance tiles: correct for any d, but the
  * stored-D path is the one for wide particles.
  * The workspace must be 16-byte aligned (STEIN_E_BADARG otherwise; hipMalloc and PyTorch allocations are).  It carries
@@ -212,6 +213,29 @@ int stein_svgd_phi_stream(const void* theta, const void* score, int64_t n, int64
                           const float* h2_in, float* phi, double* sqnorm_out,
                           void* workspace, size_t ws_bytes, int flags, void* stream);
 int stein_debug_stream_jsplit(int jsplit);
+
+/* ---- streaming step with the kernelized Stein discrepancy at its own bandwidth -------------------------------------
+ * stein_svgd_phi_stream and, from the same contraction, the two sums of STEIN_FLAG_KSD (S = sum_ij u_ij, S_diag =
+ * sum_i u_ii) of the particles under K at *h2_in.  K.theta is not formed.  With x = theta, g = score, w = g - x / h2 (the
+ * operand the step contracts), r_i = |x_i|^2 and D_ij = r_i + r_j - 2 x_i.x_j,
+ *   u_ij / k_ij = w_i.w_j - D_ij / (2 h2^2) + b_i + b_j + d / h2,      b_i = g_i.x_i / h2 - r_i / (2 h2^2)
+ * and summed over the pairs, per element e = (i, c) with ow = (K.W)_e, rs_i = sum_j k_ij, rd_i = sum_j k_ij D_ij:
+ *   S      = sum_e [ w_e ow_e + rs_i (g_e^2 - w_e^2 + 1 / h2) ] - sum_i rd_i / (2 h2^2)
+ *   S_diag = sum_e [ g_e^2 + 1 / h2 ]
+ * rd is a second running row sum of the contraction's exp phase (k_phi_stream_ksd: one multiply-add per entry of K on
+ * values it holds anyway); the finish pass reads the score rows once more and sums in fp64 from the fp32 ow, rs, rd.
+ *   phi        : [n][d] float, or NULL: the statistic alone (nothing else changes; the three sums are the same bits)
+ *   sums_out   : DEVICE double[3] = |phi|^2, S, S_diag.  KSD^2_V = S / n^2, KSD^2_U = (S - S_diag) / (n (n - 1)).
+ *   everything else as stein_svgd_phi_stream: fp32 only (STEIN_BF16: STEIN_E_UNSUPPORTED), flags == 0, a 16-byte-aligned
+ *   workspace whose contents on entry do not matter.  phi and sums_out[0] are stein_svgd_phi_stream's to the bit.
+ *   stein_stream_ksd_workspace_bytes = stein_stream_workspace_bytes + 4 jsplit n + 16 min(1024, ceil(n d / 1024)), both
+ *   terms rounded up to 256 (partial rd | the S and S_diag block partials), appended behind the plain layout: no offset
+ *   of it moves, so a buffer of this size serves stein_svgd_phi_stream, stein_stream_median and this call alike. */
+int stein_stream_ksd_workspace_bytes(int64_t n, int64_t d, int dtype, int flags, size_t* out_bytes);
+int stein_svgd_phi_stream_ksd(const void* theta, const void* score, int64_t n, int64_t d, int dtype,
+                              const float* h2_in, float* phi /* may be NULL */,
+                              double* sums_out /* [3]: |phi|^2, S, S_diag */,
+                              void* workspace, size_t ws_bytes, int flags, void* stream);
 
 /* ---- streaming median: the median-heuristic bandwidth in the streaming step's workspace -----------------------------
  * h2 = median(D) / ln n over all n^2 squared distances (compute_median.py:12-15, abstract_kernel.py:40), exact, without

@@ -77,6 +77,8 @@ _SIGNATURES = {
     "stein_stream_plan": [_i64, _i64, _c.POINTER(_int), _c.POINTER(_int), _c.POINTER(_int)],
     "stein_svgd_phi_stream": [_vp, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _sz, _int, _vp],
     "stein_debug_stream_jsplit": [_int],
+    "stein_stream_ksd_workspace_bytes": [_i64, _i64, _int, _int, _c.POINTER(_sz)],
+    "stein_svgd_phi_stream_ksd": [_vp, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _sz, _int, _vp],
     "stein_stream_median_workspace_bytes": [_i64, _i64, _int, _int, _c.POINTER(_sz)],
     "stein_stream_median_plan": [_i64, _i64, _c.POINTER(_sz), _c.POINTER(_sz), _c.POINTER(_i64), _c.POINTER(_int)],
     "stein_stream_median": [_vp, _i64, _i64, _int, _vp, _vp, _vp, _sz, _int, _vp],
@@ -195,6 +197,14 @@ def stream_workspace_bytes(n, d, dtype=F32, flags=0):
     """Workspace bytes of the streaming step (stein_svgd_phi_stream): O(n d), no distance image.  Host arithmetic."""
     total = _sz(0)
     call("stein_stream_workspace_bytes", n, d, dtype, flags, ctypes.byref(total))
+    return int(total.value)
+
+
+def stream_ksd_workspace_bytes(n, d, dtype=F32, flags=0):
+    """Workspace bytes of the streaming step with the Stein discrepancy sums (stein_svgd_phi_stream_ksd): the plain step's
+    layout with the partial rd and two more sets of block partials behind it.  Host arithmetic."""
+    total = _sz(0)
+    call("stein_stream_ksd_workspace_bytes", n, d, dtype, flags, ctypes.byref(total))
     return int(total.value)
 
 

@@ -9,6 +9,9 @@
 //   k_phi_stream        distance tile -> P = exp2(c D + 14) -> O += P.W, running rowsum(P); D and K never reach memory
 //   k_stream_finish     sums the j ranges in order, phi = (K.W + rowsum(K) theta / h2) / n, |phi|^2 block partials (fp64)
 //   k_stream_sqsum      one workgroup: the block partials -> sqnorm_out
+// stein_svgd_phi_stream_ksd, the step with the Stein discrepancy sums at its own bandwidth (include/steinhip.h), launches
+// the KSD forms of the same bodies: k_phi_stream_ksd (a second running row sum, rd = rowsum(P o D)), k_stream_finish_ksd
+// (reads the score rows too; three sets of block partials) and k_stream_sqsum3.  No K.theta, no further column space.
 // The P image's swizzle, the fp16 split and the exponent offset (pswz, cvt_pk_f16, f16_resid_lo / _hi, PEXP_H2) are
 // stein_x3_dev.h's, the ones the stored-D contraction uses; the size limits, align_up and the resident-workgroup count are
 // stein_host.h's, shared with stein_make_layout.  The finish pass stays a kernel of this file although k_phi_finish's FOLD
@@ -80,13 +83,16 @@ __device__ __forceinline__ void st_distance_tile(const u16* __restrict__ ta, con
   }
 }
 
-__global__ __launch_bounds__(ST_THREADS) void k_phi_stream(const u16* __restrict__ T3, int ntk, const u16* __restrict__ Wt3,
-                                                           long ntj, const float* __restrict__ r,
-                                                           const float* __restrict__ sc, int dc,
-                                                           const float* __restrict__ h2p, float* __restrict__ O,
-                                                           float* __restrict__ RS, int n, int d, int row_tiles,
-                                                           int col_groups, int cblocks, int jtiles, int jtiles_per) {
-  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * ST_BUF];
+// The body of k_phi_stream (KSD = false) and of k_phi_stream_ksd (KSD = true: also rd_i = sum_j P_ij D_ij, the second row sum
+// the Stein discrepancy needs -- include/steinhip.h, stein_svgd_phi_stream_ksd -- carried beside rs, reduced like rs and
+// written to RD like RS).  smem: the kernel's 2 x ST_BUF bytes of LDS.
+template <bool KSD>
+__device__ __forceinline__ void phi_stream_body(unsigned char* smem, const u16* __restrict__ T3, int ntk,
+                                                const u16* __restrict__ Wt3, long ntj, const float* __restrict__ r,
+                                                const float* __restrict__ sc, int dc, const float* __restrict__ h2p,
+                                                float* __restrict__ O, float* __restrict__ RS, float* __restrict__ RD, int n,
+                                                int d, int row_tiles, int col_groups, int cblocks, int jtiles,
+                                                int jtiles_per) {
   // column group fastest: the workgroups of one row tile are neighbours (same XCD, same T panels in its L2)
   const int logical = xcd_remap(blockIdx.x, gridDim.x);
   const int cg = logical % col_groups;
@@ -113,6 +119,7 @@ __global__ __launch_bounds__(ST_THREADS) void k_phi_stream(const u16* __restrict
 #pragma unroll
   for (int a = 0; a < 2; ++a) ri[a] = r[i0 + wr * 32 + a * 16 + l15];   // (r is padded to the row tiles; rows >= n are never stored)
   float rs[2] = {0.f, 0.f};
+  float rd[2] = {0.f, 0.f};   // (KSD)
 
   f32x4 acc[8][2];
 #pragma unroll
@@ -145,6 +152,8 @@ __global__ __launch_bounds__(ST_THREADS) void k_phi_stream(const u16* __restrict
           const float dv = (ri[ib] + rj[e]) - two_s * s[jb][ib][e];
           q[e] = __builtin_amdgcn_exp2f(__builtin_fmaf(cexp, dv, (float)PEXP_H2));
           q[e] = (j0 + jc + e < n) ? q[e] : 0.f;
+          // (the product is masked by itself: r's padding, and with it dv, may hold anything there, NaN included)
+          if constexpr (KSD) rd[ib] = __builtin_fmaf(q[e], (j0 + jc + e < n) ? dv : 0.f, rd[ib]);
         }
         rs[ib] += (q[0] + q[1]) + (q[2] + q[3]);
         const u32 h0 = cvt_pk_f16(q[0], q[1]), h1 = cvt_pk_f16(q[2], q[3]);
@@ -199,18 +208,50 @@ __global__ __launch_bounds__(ST_THREADS) void k_phi_stream(const u16* __restrict
   if (cg == 0) {
     // a row's sum: the four lane groups lq of a wave, then the two waves wc = 0, 1 (through LDS, in that order)
     __syncthreads();   // every wave is past its last read of the P images
-    float* red = reinterpret_cast<float*>(smem);   // [2][128]
+    float* red = reinterpret_cast<float*>(smem);   // [2][128] (KSD: rd's [2][128] behind it)
 #pragma unroll
     for (int ib = 0; ib < 2; ++ib) {
       float a = rs[ib];
       a += __shfl_xor(a, 16);
       a += __shfl_xor(a, 32);
       if (lq == 0) red[wc * ST_ROWS + wr * 32 + ib * 16 + l15] = a;
+      if constexpr (KSD) {
+        float b = rd[ib];
+        b += __shfl_xor(b, 16);
+        b += __shfl_xor(b, 32);
+        if (lq == 0) red[(2 + wc) * ST_ROWS + wr * 32 + ib * 16 + l15] = b;
+      }
     }
     __syncthreads();
     const int row = i0 + t;
     if (t < ST_ROWS && row < n) RS[(size_t)z * n + row] = (red[t] + red[ST_ROWS + t]) * sc[4 * dc + 2];
+    if constexpr (KSD)
+      if (t < ST_ROWS && row < n) RD[(size_t)z * n + row] = (red[2 * ST_ROWS + t] + red[3 * ST_ROWS + t]) * sc[4 * dc + 2];
   }
+}
+
+__global__ __launch_bounds__(ST_THREADS) void k_phi_stream(const u16* __restrict__ T3, int ntk, const u16* __restrict__ Wt3,
+                                                           long ntj, const float* __restrict__ r,
+                                                           const float* __restrict__ sc, int dc,
+                                                           const float* __restrict__ h2p, float* __restrict__ O,
+                                                           float* __restrict__ RS, int n, int d, int row_tiles,
+                                                           int col_groups, int cblocks, int jtiles, int jtiles_per) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * ST_BUF];
+  phi_stream_body<false>(smem, T3, ntk, Wt3, ntj, r, sc, dc, h2p, O, RS, nullptr, n, d, row_tiles, col_groups, cblocks, jtiles,
+                         jtiles_per);
+}
+
+// k_phi_stream that also leaves RD[jsplit][n], the partial sums of rd (same registers live, no scratch: __graft_entry__.py)
+__global__ __launch_bounds__(ST_THREADS) void k_phi_stream_ksd(const u16* __restrict__ T3, int ntk,
+                                                               const u16* __restrict__ Wt3, long ntj,
+                                                               const float* __restrict__ r, const float* __restrict__ sc,
+                                                               int dc, const float* __restrict__ h2p, float* __restrict__ O,
+                                                               float* __restrict__ RS, float* __restrict__ RD, int n, int d,
+                                                               int row_tiles, int col_groups, int cblocks, int jtiles,
+                                                               int jtiles_per) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * ST_BUF];
+  phi_stream_body<true>(smem, T3, ntk, Wt3, ntj, r, sc, dc, h2p, O, RS, RD, n, d, row_tiles, col_groups, cblocks, jtiles,
+                        jtiles_per);
 }
 
 // ================================================================================================
@@ -318,18 +359,31 @@ __global__ __launch_bounds__(ST_THREADS) void k_stream_hist(const u16* __restric
 }
 
 // phi = (sum_z O_z + (sum_z RS_z) theta / h2) / n (the folded finish of k_phi_finish, steinhip.hip) and this workgroup's
-// fp64 partial of |phi|^2.  vec: d % 4 == 0 and every pointer 16-byte aligned.
-__global__ __launch_bounds__(256) void k_stream_finish(const float* __restrict__ O, const float* __restrict__ RS,
-                                                       const float* __restrict__ T, const float* __restrict__ h2p,
-                                                       float* __restrict__ phi, double* __restrict__ sqpart, int n, int d,
-                                                       int jsplit, int vec) {
-  __shared__ double red[4];
+// fp64 partial of |phi|^2.  vec (bit 0): d % 4 == 0 and O, T and phi 16-byte aligned; KSD, bit 1: so is G.
+// KSD (k_stream_finish_ksd): also this workgroup's partials of the Stein discrepancy sums S and S_diag (include/steinhip.h,
+// stein_svgd_phi_stream_ksd) into kpart[0][blocks] and kpart[1][blocks], in fp64 from the fp32 ow = sum_z O_z, rs and
+// rd = sum_z RD_z (range order) and the score rows G; the rd term is added once per row, by the thread that holds its
+// column 0.  phi may then be NULL: only the store is skipped.
+__device__ __forceinline__ void stream_ksd_terms(float g, float ow, float th, float rs, double ih, double& s, double& sd) {
+  const double gd = g, t = (double)th * ih, w = gd - t;
+  s += w * (double)ow + (double)rs * (t * (2.0 * gd - t) + ih);   // g^2 - w^2 = t (2 g - t), t = theta / h2
+  sd += gd * gd + ih;
+}
+
+template <bool KSD>
+__device__ __forceinline__ void stream_finish_body(const float* __restrict__ O, const float* __restrict__ RS,
+                                                   const float* __restrict__ RD, const float* __restrict__ T,
+                                                   const float* __restrict__ G, const float* __restrict__ h2p,
+                                                   float* __restrict__ phi, double* __restrict__ sqpart,
+                                                   double* __restrict__ kpart, int n, int d, int jsplit, int vec) {
+  __shared__ double red[KSD ? 12 : 4];
   const float h2 = *h2p;
   const float fn = (float)n;
   const long total = (long)n * d;
   const size_t zs = (size_t)n * d;
-  double sq = 0.0;
-  if (vec) {
+  const double ih = 1.0 / (double)h2;   // (KSD)
+  double sq = 0.0, ks = 0.0, kd = 0.0;
+  if (vec & 1) {
     const long total4 = total >> 2;
     const int d4 = d >> 2;
     for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < total4; q += (long)gridDim.x * 256) {
@@ -346,8 +400,20 @@ __global__ __launch_bounds__(256) void k_stream_finish(const float* __restrict__
       float4 ph;
       ph.x = (og.x + rs * th.x / h2) / fn; ph.y = (og.y + rs * th.y / h2) / fn;
       ph.z = (og.z + rs * th.z / h2) / fn; ph.w = (og.w + rs * th.w / h2) / fn;
-      *reinterpret_cast<float4*>(phi + e) = ph;
+      if (!KSD || phi) *reinterpret_cast<float4*>(phi + e) = ph;
       sq += ((double)ph.x * (double)ph.x + (double)ph.y * (double)ph.y) + ((double)ph.z * (double)ph.z + (double)ph.w * (double)ph.w);
+      if constexpr (KSD) {
+        const float4 g = (vec & 2) ? *reinterpret_cast<const float4*>(G + e) : make_float4(G[e], G[e + 1], G[e + 2], G[e + 3]);
+        stream_ksd_terms(g.x, og.x, th.x, rs, ih, ks, kd);
+        stream_ksd_terms(g.y, og.y, th.y, rs, ih, ks, kd);
+        stream_ksd_terms(g.z, og.z, th.z, rs, ih, ks, kd);
+        stream_ksd_terms(g.w, og.w, th.w, rs, ih, ks, kd);
+        if (q == (long)i * d4) {   // the row's first four columns
+          float rd = 0.f;
+          for (int z = 0; z < jsplit; ++z) rd += RD[(size_t)z * n + i];
+          ks -= 0.5 * ih * ih * (double)rd;
+        }
+      }
     }
   } else {
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
@@ -357,14 +423,48 @@ __global__ __launch_bounds__(256) void k_stream_finish(const float* __restrict__
         og += O[z * zs + e];
         rs += RS[(size_t)z * n + i];
       }
-      const float ph = (og + rs * T[e] / h2) / fn;
-      phi[e] = ph;
+      const float th = T[e];
+      const float ph = (og + rs * th / h2) / fn;
+      if (!KSD || phi) phi[e] = ph;
       sq += (double)ph * (double)ph;
+      if constexpr (KSD) {
+        stream_ksd_terms(G[e], og, th, rs, ih, ks, kd);
+        if (e == (long)i * d) {   // the row's column 0
+          float rd = 0.f;
+          for (int z = 0; z < jsplit; ++z) rd += RD[(size_t)z * n + i];
+          ks -= 0.5 * ih * ih * (double)rd;
+        }
+      }
     }
   }
-  double part[1] = {sq};
-  block_sum256(part, red);
-  if (threadIdx.x == 0) sqpart[blockIdx.x] = part[0];
+  if constexpr (KSD) {
+    double part[3] = {sq, ks, kd};
+    block_sum256(part, red);
+    if (threadIdx.x == 0) {
+      sqpart[blockIdx.x] = part[0];
+      kpart[blockIdx.x] = part[1];
+      kpart[gridDim.x + blockIdx.x] = part[2];
+    }
+  } else {
+    double part[1] = {sq};
+    block_sum256(part, red);
+    if (threadIdx.x == 0) sqpart[blockIdx.x] = part[0];
+  }
+}
+
+__global__ __launch_bounds__(256) void k_stream_finish(const float* __restrict__ O, const float* __restrict__ RS,
+                                                       const float* __restrict__ T, const float* __restrict__ h2p,
+                                                       float* __restrict__ phi, double* __restrict__ sqpart, int n, int d,
+                                                       int jsplit, int vec) {
+  stream_finish_body<false>(O, RS, nullptr, T, nullptr, h2p, phi, sqpart, nullptr, n, d, jsplit, vec);
+}
+
+__global__ __launch_bounds__(256) void k_stream_finish_ksd(const float* __restrict__ O, const float* __restrict__ RS,
+                                                           const float* __restrict__ RD, const float* __restrict__ T,
+                                                           const float* __restrict__ G, const float* __restrict__ h2p,
+                                                           float* __restrict__ phi, double* __restrict__ sqpart,
+                                                           double* __restrict__ kpart, int n, int d, int jsplit, int vec) {
+  stream_finish_body<true>(O, RS, RD, T, G, h2p, phi, sqpart, kpart, n, d, jsplit, vec);
 }
 
 // the block partials of k_stream_finish, in a fixed order -> sqnorm_out[0]
@@ -374,6 +474,17 @@ __global__ __launch_bounds__(256) void k_stream_sqsum(const double* __restrict__
   for (int i = threadIdx.x; i < count; i += 256) s[0] += part[i];
   block_sum256(s, red);
   if (threadIdx.x == 0) out[0] = s[0];
+}
+
+// the same for k_stream_finish_ksd's three sets, one workgroup each: sqpart[count] -> out[0], kpart[2][count] -> out[1], out[2]
+__global__ __launch_bounds__(256) void k_stream_sqsum3(const double* __restrict__ sqpart, const double* __restrict__ kpart,
+                                                       int count, double* __restrict__ out) {
+  __shared__ double red[4];
+  const double* __restrict__ part = blockIdx.x == 0 ? sqpart : kpart + (size_t)(blockIdx.x - 1) * count;
+  double s[1] = {0.0};
+  for (int i = threadIdx.x; i < count; i += 256) s[0] += part[i];
+  block_sum256(s, red);
+  if (threadIdx.x == 0) out[blockIdx.x] = s[0];
 }
 
 // ================================================================================================
@@ -433,7 +544,7 @@ static int stream_make_layout(int64_t n, int64_t d, StreamLayout* L) {
 
 // Every address the streaming entry points use, formed once: of a stored-D layout only the planes' extents; the planes the
 // split launchers take; and the step's partial sums (K.W of the j ranges in OG, their rowsum(K) in RS, the |phi|^2 block
-// partials in SQ; no K.theta: nothing here asks for dK or the statistic).
+// partials in SQ; no K.theta: nothing here asks for dK, and the statistic does without it -- StreamKsdLayout).
 // The median passes StreamMedianLayout's hist / sel offsets: its histograms and select state lie where the step keeps W's
 // planes and partial sums, which that call never touches.
 static StepViews stream_views(const StreamLayout& L, void* workspace, size_t hist_at = 0, size_t sel_at = 0) {
@@ -455,6 +566,22 @@ static StepViews stream_views(const StreamLayout& L, void* workspace, size_t his
     v.sel = (SelState*)(ws + sel_at);
   }
   return v;
+}
+
+// The layout of stein_svgd_phi_stream_ksd: StreamLayout as it is, with RD (the j ranges' partial rd, [jsplit][n] floats) and
+// the S / S_diag block partials ([2][sq_blocks] doubles) appended behind its end.  No offset of the plain layout moves:
+// a buffer of this size serves the plain step and the median call too.
+struct StreamKsdLayout {
+  StreamLayout L;
+  size_t rd, kpart, total;
+};
+
+static int stream_ksd_make_layout(int64_t n, int64_t d, StreamKsdLayout* K) {
+  if (int rc = stream_make_layout(n, d, &K->L)) return rc;
+  K->rd = K->L.total;
+  K->kpart = K->rd + align_up((size_t)K->L.jsplit * n * 4, 256);
+  K->total = K->kpart + align_up((size_t)2 * K->L.sq_blocks * 8, 256);
+  return STEIN_OK;
 }
 
 extern "C" int stein_debug_stream_jsplit(int jsplit) {
@@ -485,6 +612,19 @@ extern "C" int stein_stream_plan(int64_t n, int64_t d, int* row_tiles, int* col_
   return STEIN_OK;
 }
 
+// The launches in front of the contraction, the same for the plain step and the one with the statistic:
+// 1. row norms (the padding rows of r are never read into a stored result), column maxima -> scales
+// 2. theta's row-major planes (fold form of the split: no transposed image, the score only feeds the maxima)
+// 3. W = G - theta / h2 at the caller's bandwidth
+static int stream_operands(const StepViews& v, const void* theta, const void* score, int64_t n, int64_t d, int dtype,
+                           const float* h2_in, hipStream_t s) {
+  int rc;
+  if ((rc = stein_rownorms(theta, n, d, dtype, v.r, (void*)s))) return rc;
+  const SplitFused only_rows{nullptr, nullptr, 1};
+  if ((rc = stein_x3_split(v, theta, score, dtype, n, d, s, &only_rows))) return rc;
+  return stein_x3_split_w(v, (const float*)theta, (const float*)score, n, d, h2_in, s);
+}
+
 extern "C" int stein_svgd_phi_stream(const void* theta, const void* score, int64_t n, int64_t d, int dtype,
                                      const float* h2_in, float* phi, double* sqnorm_out, void* workspace, size_t ws_bytes,
                                      int flags, void* stream) {
@@ -498,13 +638,7 @@ extern "C" int stein_svgd_phi_stream(const void* theta, const void* score, int64
   if ((rc = stein_take_device_error())) return rc;   // a kernel of an earlier call on this device gave up: say so now
   hipStream_t s = (hipStream_t)stream;
   const StepViews v = stream_views(L, workspace);
-  // 1. row norms (the padding rows of r are never read into a stored result), column maxima -> scales
-  // 2. theta's row-major planes (fold form of the split: no transposed image, the score only feeds the maxima)
-  if ((rc = stein_rownorms(theta, n, d, dtype, v.r, stream))) return rc;
-  const SplitFused only_rows{nullptr, nullptr, 1};
-  if ((rc = stein_x3_split(v, theta, score, dtype, n, d, s, &only_rows))) return rc;
-  // 3. W = G - theta / h2 at the caller's bandwidth
-  if ((rc = stein_x3_split_w(v, (const float*)theta, (const float*)score, n, d, h2_in, s))) return rc;
+  if ((rc = stream_operands(v, theta, score, n, d, dtype, h2_in, s))) return rc;
   // 4. the streaming contraction
   const long nblk = (long)(L.row_tiles * L.col_groups * L.jsplit);
   hipLaunchKernelGGL(k_phi_stream, dim3((unsigned)nblk), dim3(ST_THREADS), 0, s, v.T3, (int)(L.dk / 32), v.Gt3,
@@ -518,6 +652,52 @@ extern "C" int stein_svgd_phi_stream(const void* theta, const void* score, int64
   LAUNCH_CHECK("k_stream_finish");
   hipLaunchKernelGGL(k_stream_sqsum, dim3(1), dim3(256), 0, s, v.SQ, (int)L.sq_blocks, sqnorm_out);
   LAUNCH_CHECK("k_stream_sqsum");
+  return STEIN_OK;
+}
+
+// ---- the streaming step with the Stein discrepancy sums ---------------------------------------------------------------
+extern "C" int stein_stream_ksd_workspace_bytes(int64_t n, int64_t d, int dtype, int flags, size_t* out_bytes) {
+  if (!out_bytes) return fail(STEIN_E_BADARG, "out_bytes is NULL");
+  int rc = stream_check_shape(n, d, dtype, flags);
+  if (rc) return rc;
+  StreamKsdLayout K;
+  if ((rc = stream_ksd_make_layout(n, d, &K))) return rc;
+  *out_bytes = K.total;
+  return STEIN_OK;
+}
+
+extern "C" int stein_svgd_phi_stream_ksd(const void* theta, const void* score, int64_t n, int64_t d, int dtype,
+                                         const float* h2_in, float* phi, double* sums_out, void* workspace, size_t ws_bytes,
+                                         int flags, void* stream) {
+  if (!theta || !score || !h2_in || !sums_out || !workspace) return fail(STEIN_E_BADARG, "NULL pointer");   // (phi may be)
+  if ((uintptr_t)workspace & 15) return fail(STEIN_E_BADARG, "the workspace must be 16-byte aligned");
+  int rc = stream_check_shape(n, d, dtype, flags);
+  if (rc) return rc;
+  StreamKsdLayout K;
+  if ((rc = stream_ksd_make_layout(n, d, &K))) return rc;
+  const StreamLayout& L = K.L;
+  if (ws_bytes < K.total) return fail(STEIN_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, K.total);
+  if ((rc = stein_take_device_error())) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const StepViews v = stream_views(L, workspace);
+  float* RD = (float*)((char*)workspace + K.rd);
+  double* KP = (double*)((char*)workspace + K.kpart);
+  if ((rc = stream_operands(v, theta, score, n, d, dtype, h2_in, s))) return rc;
+  // 4. the streaming contraction, with the second row sum
+  const long nblk = (long)(L.row_tiles * L.col_groups * L.jsplit);
+  hipLaunchKernelGGL(k_phi_stream_ksd, dim3((unsigned)nblk), dim3(ST_THREADS), 0, s, v.T3, (int)(L.dk / 32), v.Gt3,
+                     (long)(L.nk / 32), v.r, v.sc, (int)L.dc, h2_in, v.OG, v.RS, RD, (int)n, (int)d, (int)L.row_tiles,
+                     (int)L.col_groups, (int)L.cblocks, (int)L.row_tiles, (int)L.jtiles_per);
+  LAUNCH_CHECK("k_phi_stream_ksd");
+  // 5. finish: phi (unless NULL), the three sets of block partials, their sums in a fixed order.  The 16-byte path is chosen
+  // as in the plain step (a NULL phi counts as aligned), so that |phi|^2 is summed in the plain step's order; the score's
+  // alignment only decides how its rows are loaded on that path (bit 1)
+  const int vec = (d % 4 == 0 && (((uintptr_t)theta | (uintptr_t)phi) & 15) == 0 ? 1 : 0) | (((uintptr_t)score & 15) == 0 ? 2 : 0);
+  hipLaunchKernelGGL(k_stream_finish_ksd, dim3((unsigned)L.sq_blocks), dim3(256), 0, s, v.OG, v.RS, RD, (const float*)theta,
+                     (const float*)score, h2_in, phi, v.SQ, KP, (int)n, (int)d, (int)L.jsplit, vec);
+  LAUNCH_CHECK("k_stream_finish_ksd");
+  hipLaunchKernelGGL(k_stream_sqsum3, dim3(3), dim3(256), 0, s, v.SQ, KP, (int)L.sq_blocks, sums_out);
+  LAUNCH_CHECK("k_stream_sqsum3");
   return STEIN_OK;
 }
 

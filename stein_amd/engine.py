@@ -84,6 +84,12 @@ class HipStages:
         _lib.call_on(T.device, "stein_svgd_phi_stream", _ptr(T), _ptr(G), n, d, _dt(T), _ptr(h2), _ptr(phi), _ptr(sqnorm),
                      _ptr(ws), ws.numel(), 0, _stream(T))
 
+    def svgd_phi_stream_ksd(self, T, G, n, d, h2, phi, sums, ws):
+        """the streaming step and, in the 3-element float64 device tensor sums, |phi|^2 and the Stein discrepancy sums S and
+        S_diag at that bandwidth; phi may be None: the sums alone (stein_svgd_phi_stream_ksd, include/steinhip.h)"""
+        _lib.call_on(T.device, "stein_svgd_phi_stream_ksd", _ptr(T), _ptr(G), n, d, _dt(T), _ptr(h2), _ptr(phi), _ptr(sums),
+                     _ptr(ws), ws.numel(), 0, _stream(T))
+
     def stream_median(self, T, n, d, h2, median, ws):
         """the median-heuristic bandwidth^2 (and the median) of T's n^2 distances into the 1-element device tensors h2 and
         median (median may be None), in a streaming workspace: no n x n image (stein_stream_median, include/steinhip.h)"""
@@ -214,7 +220,8 @@ class SvgdEngine:
               is -- the library reads it on the device in every step, so the caller may rewrite it in place between steps
               (an annealing schedule) or hand over another engine's `h2` (a median refreshed every k-th step and held in
               between).  Either way `self.h2` is that tensor.  fp32 inputs on the split path, one rank; K_out, dK_out,
-              dist_matrix(), ksd, mark= and group= are refused with a ValueError.
+              dist_matrix(), ksd, mark= and group= are refused with a ValueError.  The Stein discrepancy at the step's
+              bandwidth is asked for per call: compute_phi(theta, score, discrepancy=True), then stein_discrepancy().
               "median": the streaming step at the median heuristic's own bandwidth, still without the n x n image: the
               engine owns `self.h2` and `self.median` (1-element float32 device tensors) and, before the step of every
               call whose 0-based index is a multiple of `median_every`, takes the exact median of the n^2 distances in
@@ -353,7 +360,8 @@ class SvgdEngine:
         if x3 is not None and not x3:
             raise ValueError("h2=: the streaming step only exists on the split path; x3=False is not supported")
         if ksd:
-            raise ValueError("h2=: ksd=True is not supported (the Stein discrepancy at a supplied bandwidth needs K.theta)")
+            raise ValueError("h2=: ksd=True is not supported; the streaming step computes the Stein discrepancy per call: "
+                             "compute_phi(theta, score, discrepancy=True), then stein_discrepancy()")
         self.device = torch.device(device)
         if self.median_every is not None:
             if self.n < 2:
@@ -410,6 +418,33 @@ class SvgdEngine:
         if tuple(t.shape) != (self.n, self.d) or t.dtype != torch.float32 or not t.is_contiguous():
             raise ValueError("%s must be a contiguous torch.float32 [%d, %d] tensor, got %s %s" %
                              (name, self.n, self.d, tuple(t.shape), t.dtype))
+
+    def _stream_ksd_workspace(self):
+        """Grow the workspace to what stein_svgd_phi_stream_ksd needs (first use).  The larger buffer serves the plain step
+        and the median call too -- the layout only appends -- and nothing in it is carried between calls."""
+        if not hasattr(self.stages, "svgd_phi_stream_ksd"):
+            raise ValueError("discrepancy=True: the stages have no streaming step with the statistic (HipStages has)")
+        need = _lib.stream_ksd_workspace_bytes(self.n, self.d)
+        assert need >= _lib.stream_workspace_bytes(self.n, self.d)
+        if self.ws_bytes < need:
+            self.ws = None      # (release before allocating: at the largest shapes both would not fit)
+            self.ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            self.ws_bytes = need
+
+    def stream_discrepancy_sums(self, theta, score):
+        """The statistic alone (streaming engines): the three sums |phi|^2, S, S_diag of `theta`, `score` at this engine's
+        bandwidth into self._sums, phi not stored (the C entry with phi = NULL); stein_discrepancy() afterwards.  With
+        h2="median" the bandwidth is taken from `theta` first.  Outside compute_phi's refresh schedule."""
+        if not self.streaming:
+            raise ValueError("stream_discrepancy_sums needs a streaming engine (h2=)")
+        for name, t in (("theta", theta), ("score", score)):
+            self._check_stream_input(name, t)
+        self._stream_ksd_workspace()
+        if self.median_every is not None:
+            self.stages.stream_median(theta, self.n, self.d, self.h2, self.median, self.ws)
+        self.stages.svgd_phi_stream_ksd(theta, score, self.n, self.d, self.h2, None, self._sums, self.ws)
+        self._ksd_ready = True
+        return self._sums
 
     def refresh_bandwidth(self, theta):
         """h2="median": take the median-heuristic bandwidth of `theta` ([n, d] float32 device tensor) now, in this engine's
@@ -628,8 +663,16 @@ class SvgdEngine:
         """KSD^2 of the particles of the last compute_phi (ksd=True): a 0-d float64 device tensor, no host sync.
         statistic "u": the U-statistic  sum_{i != j} u_ij / (n (n - 1))  (unbiased, may be slightly negative near
         convergence); "v": the V-statistic  sum_ij u_ij / n^2.  u_ij is the Stein kernel of the step's RBF kernel with the
-        step's median bandwidth (include/steinhip.h, STEIN_FLAG_KSD)."""
-        if not self.ksd:
+        step's median bandwidth (include/steinhip.h, STEIN_FLAG_KSD).
+        A streaming engine (h2=): of the last compute_phi, which must have been called with discrepancy=True, at that
+        call's bandwidth (stein_svgd_phi_stream_ksd)."""
+        if self.streaming:
+            if not self._ksd_ready:
+                raise RuntimeError("the last compute_phi did not compute the Stein discrepancy: call "
+                                   "compute_phi(theta, score, discrepancy=True) first")
+            if statistic == "u" and self.n < 2:
+                raise ValueError("n = 1: the U-statistic needs at least two particles (statistic='v' is defined)")
+        if not self.ksd and not self.streaming:
             raise RuntimeError("the engine was built without ksd=True")
         if not self._ksd_ready:
             raise RuntimeError("no step has been computed yet")
@@ -640,7 +683,7 @@ class SvgdEngine:
             return (self._sums[1] - self._sums[2]) / (n * (n - 1.0))
         raise ValueError("statistic must be 'u' or 'v'")
 
-    def compute_phi(self, theta_local, score_local, K_out=None, dK_out=None, mark=None, timing=False):
+    def compute_phi(self, theta_local, score_local, K_out=None, dK_out=None, mark=None, timing=False, discrepancy=False):
         """theta_local, score_local: [n_local, d] float32 contiguous device tensors (this rank's rows).
 
         Returns self.phi ([n_local, d] float32, unclipped).  Afterwards self.h2 holds bandwidth^2
@@ -656,8 +699,14 @@ class SvgdEngine:
         kernels costs the step ~3 us, so a loop that is itself being timed should carry as few as it can.
         With ksd=True the step also leaves the Stein discrepancy sums (stein_discrepancy()); the staged calls (mark=, or a
         sharded step with K_out) do not compute them and are refused.
+        discrepancy: streaming engines (h2=) only.  True: this call also leaves the Stein discrepancy sums at its own
+        bandwidth (stein_discrepancy() afterwards; stein_svgd_phi_stream_ksd, no K.theta and no n x n image); phi, sqnorm
+        and h2 are bit-identical to a call without it.  The workspace grows once, by the partial sums of one more row sum.
         """
         st, n, d, nl = self.stages, self.n, self.d, self.n_local
+        if discrepancy and not self.streaming:
+            raise ValueError("discrepancy=True is the streaming engine's (h2=) per-call switch; an engine without a supplied "
+                             "bandwidth computes the Stein discrepancy in every step when built with ksd=True")
         if self.streaming:
             if K_out is not None or dK_out is not None:
                 raise ValueError("h2=: the streaming step forms neither K nor dK; K_out / dK_out are not supported")
@@ -665,11 +714,17 @@ class SvgdEngine:
                 raise ValueError("h2=: the streaming step is one call; mark= / timing= are not supported")
             for name, t in (("theta", theta_local), ("score", score_local)):
                 self._check_stream_input(name, t)
+            if discrepancy:
+                self._stream_ksd_workspace()
             if self.median_every is not None:
                 if self._stream_calls % self.median_every == 0:
                     st.stream_median(theta_local, n, d, self.h2, self.median, self.ws)
                 self._stream_calls += 1
-            st.svgd_phi_stream(theta_local, score_local, n, d, self.h2, self.phi, self.sqnorm, self.ws)
+            if discrepancy:
+                st.svgd_phi_stream_ksd(theta_local, score_local, n, d, self.h2, self.phi, self._sums, self.ws)
+            else:
+                st.svgd_phi_stream(theta_local, score_local, n, d, self.h2, self.phi, self.sqnorm, self.ws)
+            self._ksd_ready = bool(discrepancy)
             return self.phi
         if self.ksd and (mark is not None or (self.sharded and K_out is not None)):
             raise ValueError("ksd=True: the staged calls (mark=, or K_out on a sharded engine) do not compute the Stein "

@@ -29,7 +29,7 @@ class AbstractSteinSampler:
 
     def __init__(self, n_particles, log_p, theta=None, *, model_vars=None, device="cuda", dtype=torch.float32,
                  group=None, seed=None, kernel_dtype=torch.float32, x3=None, ksd=False, bandwidth=None, h2=None,
-                 median_every=1):
+                 median_every=1, ksd_every=None):
         """
         n_particles : total number of particles n (across all ranks).
         log_p       : see SteinSampler.
@@ -53,6 +53,10 @@ class AbstractSteinSampler:
                       distances taken without the n x n workspace (engine.SvgdEngine, h2="median").
         median_every : with bandwidth="median", refresh the median every this many steps (integer >= 1, default 1) and
                       hold the bandwidth in between; refused otherwise.
+        ksd_every   : with bandwidth= / h2= (the streaming path), an integer k >= 1: every k-th update_particles, starting
+                      with the first, also computes the kernelized Stein discrepancy at that step's bandwidth
+                      (stein_discrepancy() returns the latest).  None (default): never.  Refused on any other sampler, where
+                      ksd=True is the switch.
         """
         self.n_particles = int(n_particles)
         self.log_p = log_p
@@ -129,6 +133,15 @@ class AbstractSteinSampler:
                 if not math.isfinite(h) or h <= 0.0:
                     raise ValueError("bandwidth must be positive and finite, got %r" % (bandwidth,))
                 h2 = h * h
+        if ksd_every is not None:
+            if isinstance(ksd_every, bool) or not isinstance(ksd_every, int) or ksd_every < 1:
+                raise ValueError("ksd_every must be an integer >= 1 or None, got %r" % (ksd_every,))
+            if h2 is None:
+                raise ValueError("ksd_every= is the Stein discrepancy period of the streaming path (bandwidth= / h2=); a "
+                                 "sampler at the median heuristic of every step computes it with ksd=True")
+        self.ksd_every = ksd_every
+        self._updates = 0           # update_particles calls so far
+        self._ksd_sums = None       # [S, S_diag] of the latest step that computed them (streaming path; a device copy)
         self.engine = SvgdEngine(self.n_particles, self.n_params, device=self.device, group=group, x3=x3,
                                  dtype=kernel_dtype, ksd=ksd, h2=h2, median_every=median_every)
         self._theta32 = (self.theta_matrix if dtype == kernel_dtype else
@@ -171,8 +184,9 @@ class AbstractSteinSampler:
         from ..kernels import SquaredExponentialKernel
         return None if isinstance(k, SquaredExponentialKernel) else k
 
-    def compute_phi(self, theta_array, grads_array):
+    def compute_phi(self, theta_array, grads_array, discrepancy=False):
         """phi = (K . grads + dK) / n for the given particles (abstract_stein_sampler.py:100-105).
+        discrepancy=True (streaming path only): the engine also leaves the Stein discrepancy sums of these particles.
 
         NumPy in -> float64 NumPy out (values carry fp32 precision); device tensors in -> float32 tensor out.
         With a user-supplied ``self.kernel`` the reference's own lines run instead: ``K, dK =
@@ -181,6 +195,8 @@ class AbstractSteinSampler:
         was_numpy = not isinstance(theta_array, torch.Tensor)
         foreign = self._foreign_kernel()
         if foreign is not None:
+            if discrepancy:
+                raise ValueError("a user-supplied kernel computes phi on the host: no Stein discrepancy")
             if self._group is not None:
                 raise ValueError("a user-supplied kernel needs all particles on one rank")
             th = theta_array if was_numpy else theta_array.detach().double().cpu().numpy()
@@ -196,14 +212,29 @@ class AbstractSteinSampler:
         T = theta_array if not was_numpy else torch.from_numpy(np.ascontiguousarray(np.asarray(theta_array, dtype=np.float64)))
         T = T.to(device=self.device, dtype=self.kernel_dtype).contiguous()
         G = self._score_to_device(grads_array)
-        phi = self.engine.compute_phi(T, G)
+        phi = self.engine.compute_phi(T, G, discrepancy=True) if discrepancy else self.engine.compute_phi(T, G)
         return phi.double().cpu().numpy() if was_numpy else phi.clone()
 
     def stein_discrepancy(self, statistic="u"):
         """KSD^2 (a float) of the particles at the last step's score evaluation, i.e. before that step's update, under the
         step's RBF kernel and median bandwidth: statistic "u" (U-statistic, the default) or "v" (V-statistic).  Needs
         ksd=True and a step through the package's own kernel; reading it synchronises with the device.  Sharded: the
-        statistic of all n particles, the same on every rank."""
+        statistic of all n particles, the same on every rank.
+        With ksd_every=k (the streaming path): of the latest step that computed it -- every k-th, from the first -- under
+        that step's bandwidth; a RuntimeError before the first."""
+        if self.ksd_every is not None:
+            # the streaming path: the sums of the latest step that computed them, at that step's bandwidth
+            if self._ksd_sums is None:
+                raise RuntimeError("no step has computed the Stein discrepancy yet (ksd_every=%d: the first "
+                                   "update_particles does)" % self.ksd_every)
+            n = float(self.n_particles)
+            if statistic == "v":
+                return float((self._ksd_sums[0] / (n * n)).item())
+            if statistic == "u":
+                if self.n_particles < 2:
+                    raise ValueError("n = 1: the U-statistic needs at least two particles (statistic='v' is defined)")
+                return float(((self._ksd_sums[0] - self._ksd_sums[1]) / (n * (n - 1.0))).item())
+            raise ValueError("statistic must be 'u' or 'v'")
         if not self.engine.ksd:
             raise RuntimeError("build the sampler with ksd=True to get the Stein discrepancy")
         if self._foreign_kernel() is not None:
@@ -214,13 +245,19 @@ class AbstractSteinSampler:
     def update_particles(self, grads_array):
         """One SVGD step from the score matrix: phi, norm clip, optimizer apply
         (abstract_stein_sampler.py:121-127), all on device."""
+        want = self.ksd_every is not None and self._updates % self.ksd_every == 0
+        self._updates += 1
         if self._foreign_kernel() is not None or not hasattr(self.gd, "apply_"):
-            return self._update_particles_by_the_seams(grads_array)
-        G = self._score_to_device(grads_array)
-        phi = self.engine.compute_phi(self._theta_f32(), G)
-        self.gd.apply_(self.theta_matrix, phi, self.engine.sqnorm)
+            self._update_particles_by_the_seams(grads_array, want)
+        else:
+            G = self._score_to_device(grads_array)
+            phi = self.engine.compute_phi(self._theta_f32(), G, discrepancy=True) if want else \
+                self.engine.compute_phi(self._theta_f32(), G)
+            self.gd.apply_(self.theta_matrix, phi, self.engine.sqnorm)
+        if want:
+            self._ksd_sums = self.engine._sums[1:3].clone()   # (the next plain step leaves them alone, but says "not ready")
 
-    def _update_particles_by_the_seams(self, grads_array):
+    def _update_particles_by_the_seams(self, grads_array, discrepancy=False):
         """The reference's duck-typed seams, line for line (abstract_stein_sampler.py:121-127): taken when ``self.gd`` is a
         reference-style optimizer (only ``update(phi) -> step``, no fused ``apply_``) or ``self.kernel`` is a user's
         object (only ``kernel_and_grad``).  phi still comes from the HIP engine unless the kernel is foreign; the clip and
@@ -230,7 +267,7 @@ class AbstractSteinSampler:
             g, _ = convert_dictionary_to_array(g)
         g = g.detach().double().cpu().numpy() if isinstance(g, torch.Tensor) else np.asarray(g, dtype=np.float64)
         theta_array = self.theta_matrix.detach().double().cpu().numpy()      # :121 (a float64 copy, as the reference packs)
-        phi = self.compute_phi(theta_array, g)                               # :123
+        phi = self.compute_phi(theta_array, g, discrepancy) if discrepancy else self.compute_phi(theta_array, g)   # :123
         # :125 -- on one rank NumPy's norm of phi, as the reference; sharded, phi holds this rank's rows and the norm is the
         # engine's all-reduced one
         norm = np.linalg.norm(phi) if self._group is None else float(self.engine.sqnorm.sqrt().item())

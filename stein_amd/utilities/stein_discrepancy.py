@@ -2,12 +2,39 @@
 import torch
 
 
-def kernelized_stein_discrepancy(theta, score, statistic="u"):
+def _stream_bandwidth(bandwidth):
+    """bandwidth= of kernelized_stein_discrepancy -> the h2 argument of a streaming engine"""
+    import math
+    if isinstance(bandwidth, str):
+        if bandwidth == "median":
+            return "median"
+        raise ValueError("bandwidth must be None, a positive finite float or \"median\", got %r" % (bandwidth,))
+    if isinstance(bandwidth, bool):
+        raise ValueError("bandwidth must be None, a positive finite float or \"median\", got %r" % (bandwidth,))
+    try:
+        h = float(bandwidth)
+    except (TypeError, ValueError):
+        raise ValueError("bandwidth must be None, a positive finite float or \"median\", got %r" % (bandwidth,))
+    if not math.isfinite(h) or h <= 0.0:
+        raise ValueError("bandwidth must be positive and finite, got %r" % (bandwidth,))
+    return h * h
+
+
+def kernelized_stein_discrepancy(theta, score, statistic="u", bandwidth=None):
     """KSD^2 (a float) of the particles `theta` with scores `score` = d log p / d theta, both [n, d] float32 or bfloat16
     device tensors, under the RBF kernel with the median-heuristic bandwidth SVGD uses: statistic "u" (U-statistic,
     unbiased, the default) or "v" (V-statistic).  Runs the fused phi call with the statistic on a transient engine (its
-    workspace is allocated for the call: about 4 n^2 bytes for large n) and applies nothing."""
+    workspace is allocated for the call: about 4 n^2 bytes for large n) and applies nothing.
+    bandwidth: None (default) is the above.  A positive finite float h (K = exp(-D / (2 h^2)), h^2 rounded to float32) or
+    "median" (the exact median heuristic, taken without the n x n image) runs the streaming step's statistic instead
+    (stein_svgd_phi_stream_ksd with phi = NULL) in an O(n d) workspace: float32 inputs only."""
     from ..engine import SvgdEngine
+    h2 = _stream_bandwidth(bandwidth) if bandwidth is not None else None
+    if h2 is not None:
+        for name, t in (("theta", theta), ("score", score)):
+            if isinstance(t, torch.Tensor) and t.dtype == torch.bfloat16:
+                raise ValueError("bandwidth=: the streaming statistic takes float32 inputs; %s is bfloat16 (bf16 inputs "
+                                 "are only supported with bandwidth=None)" % name)
     for name, t in (("theta", theta), ("score", score)):
         if not isinstance(t, torch.Tensor):
             raise ValueError("%s must be a torch tensor" % name)
@@ -25,6 +52,11 @@ def kernelized_stein_discrepancy(theta, score, statistic="u"):
         raise ValueError("n = %d: the statistic needs at least two particles" % n)
     if statistic not in ("u", "v"):
         raise ValueError("statistic must be 'u' or 'v'")
+    if h2 is not None:
+        eng = SvgdEngine(n, d, device=theta.device, h2=h2)
+        with torch.cuda.device(theta.device):
+            eng.stream_discrepancy_sums(theta.contiguous(), score.contiguous())
+            return float(eng.stein_discrepancy(statistic).item())
     eng = SvgdEngine(n, d, device=theta.device, dtype=theta.dtype, ksd=True)
     with torch.cuda.device(theta.device):
         eng.compute_phi(theta.contiguous(), score.contiguous())
