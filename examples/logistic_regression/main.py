@@ -6,7 +6,9 @@ reference reads is not shipped with it, so the data here are synthetic with the 
     python examples/logistic_regression/main.py [--particles 100] [--iters 2000] [--autograd]
 
 The score matrix comes from the HIP score producer (stein_amd.scores.GlmScore, the closed-form gradient of the model
-below); --autograd differentiates log_posterior with torch instead.
+below) and the held-out readout from the HIP predictive producer (stein_amd.predict.GlmPredict: the ensemble mean of the
+logits and the log predictive density per test point, without the [particles, test points] matrix); --autograd
+differentiates log_posterior with torch instead and reads the particles out through a torch callable.
 """
 import argparse
 import os
@@ -18,6 +20,7 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 from stein_amd.optimizers import AdamGradientDescent  # noqa: E402
+from stein_amd.predict import GlmPredict  # noqa: E402
 from stein_amd.samplers import SteinSampler  # noqa: E402
 from stein_amd.scores import GlmScore  # noqa: E402
 
@@ -56,7 +59,7 @@ def main():
     (Xtr, ytr), (Xte, yte) = make_data()
     dev = "cuda"
     Xtr_t, ytr_t = torch.tensor(Xtr, dtype=torch.float32, device=dev), torch.tensor(ytr, dtype=torch.float32, device=dev)
-    Xte_t = torch.tensor(Xte, dtype=torch.float32, device=dev)
+    Xte_t, yte_t = torch.tensor(Xte, dtype=torch.float32, device=dev), torch.tensor(yte, dtype=torch.float32, device=dev)
     # packed columns follow the sorted variable names: log_alpha first, then the weights
     score = None if args.autograd else GlmScore("logistic", Xtr.shape[1], w_col=1, alpha_col=0, n_train=len(Xtr))
     sampler = SteinSampler(args.particles, make_log_posterior(len(Xtr), args.batch),
@@ -64,16 +67,26 @@ def main():
                            model_vars={"model/w:0": [Xtr.shape[1], 1], "model/log_alpha:0": []})
     gen = torch.Generator(device=dev).manual_seed(0)
 
-    def accuracy():
-        logits = sampler.function_posterior(lambda th, feed: (feed["X"] @ th["model/w:0"][:, :, 0].T).T, {"X": Xte_t})
-        return float(((logits.mean(axis=0) > 0) == (yte > 0.5)).mean())
+    predictive = None if args.autograd else GlmPredict("logistic", Xtr.shape[1], w_col=1)   # output "link": the logits
+
+    def held_out():
+        """-> (accuracy of the ensemble-mean logit, mean log predictive density) on the test split"""
+        if predictive is not None:
+            out = sampler.posterior_predictive(predictive, {"X": Xte_t, "y": yte_t})
+            mean_logit, lpd = out["mean"], out["lpd"]
+        else:
+            logits = sampler.function_posterior(lambda th, feed: (feed["X"] @ th["model/w:0"][:, :, 0].T).T, {"X": Xte_t})
+            mean_logit = logits.mean(axis=0)
+            log_l = yte[None, :] * logits - np.logaddexp(0.0, logits)
+            lpd = np.logaddexp.reduce(log_l, axis=0) - np.log(len(logits))
+        return float(((mean_logit > 0) == (yte > 0.5)).mean()), float(np.mean(lpd))
 
     for i in range(args.iters):
         if i % 200 == 0:
-            print("iteration %5d / %d: held-out accuracy %.4f" % (i, args.iters, accuracy()))
+            print("iteration %5d / %d: held-out accuracy %.4f, mean log predictive density %.4f" % ((i, args.iters) + held_out()))
         idx = torch.randint(0, len(Xtr), (args.batch,), device=dev, generator=gen)
         sampler.train_on_batch({"X": Xtr_t[idx], "y": ytr_t[idx]})
-    print("final held-out accuracy %.4f" % accuracy())
+    print("final held-out accuracy %.4f, mean log predictive density %.4f" % held_out())
 
 
 if __name__ == "__main__":

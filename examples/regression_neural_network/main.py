@@ -4,6 +4,10 @@ Gamma(1, 0.01) priors on the weight precision lambda and the noise precision gam
 20 particles, Adam(0.1, decay 0.999).  d = 3 H + 3 = 303 parameters per particle.
 
     python examples/regression_neural_network/main.py [--particles 20] [--iters 3000] [--autograd]
+
+The score comes from the HIP score producer (stein_amd.scores.BnnScore) and the readout -- the MSE of the ensemble mean and
+the log predictive density of the points -- from the HIP predictive producer (stein_amd.predict.BnnPredict); --autograd
+keeps the torch route for both.
 """
 import argparse
 import math
@@ -15,6 +19,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 from stein_amd.optimizers import AdamGradientDescent  # noqa: E402
+from stein_amd.predict import BnnPredict  # noqa: E402
 from stein_amd.samplers import SteinSampler  # noqa: E402
 from stein_amd.scores import BnnScore  # noqa: E402
 
@@ -71,13 +76,26 @@ def main():
     sampler = SteinSampler(args.particles, make_log_posterior(len(X), len(X)),
                            AdamGradientDescent(learning_rate=5e-2, decay=0.999), theta=init, model_vars=shapes)
     assert sampler.n_params == 3 * H + 3
+    cols = BnnScore.columns(sampler._access)
     if not args.autograd:   # closed-form backprop of the same log posterior in one HIP launch (stein_amd/scores.py)
-        sampler.score = BnnScore(1, H, BnnScore.columns(sampler._access), n_train=len(X))
+        sampler.score = BnnScore(1, H, cols, n_train=len(X))
+    predictive = None if args.autograd else BnnPredict(1, H, cols)
+
+    def readout():
+        """-> (MSE of the ensemble mean, mean log predictive density) on the 20 points"""
+        if predictive is not None:
+            out = sampler.posterior_predictive(predictive, feed)
+            return float(np.mean((y - out["mean"]) ** 2)), float(np.mean(out["lpd"]))
+        y_hat = sampler.function_posterior(lambda th, f: predict(th, f["X"]), feed)
+        log_gam = sampler.function_posterior(lambda th, f: th["model/log_gamma:0"], feed)          # [n, 1]
+        log_l = 0.5 * log_gam - 0.5 * np.exp(log_gam) * (y[None, :] - y_hat) ** 2 - 0.5 * math.log(2 * math.pi)
+        lpd = np.logaddexp.reduce(log_l, axis=0) - math.log(len(y_hat))
+        return float(np.mean((y - y_hat.mean(axis=0)) ** 2)), float(np.mean(lpd))
+
     for i in range(args.iters):
         sampler.train_on_batch(feed)
         if i % 250 == 0 or i == args.iters - 1:
-            y_hat = sampler.function_posterior(lambda th, f: predict(th, f["X"]), feed)
-            print("iteration %5d: mean squared error %.4f" % (i, float(np.mean((y - y_hat.mean(axis=0)) ** 2))))
+            print("iteration %5d: mean squared error %.4f, mean log predictive density %.4f" % ((i,) + readout()))
 
 
 if __name__ == "__main__":

@@ -489,6 +489,37 @@ int stein_score_bnn(const float* theta, int64_t n, int64_t d, int64_t n_in, int6
                     const float* X, const float* y, int64_t batch, double n_train, double gamma_a, double gamma_b,
                     float* score, void* stream);
 
+/* ---- posterior predictive producers (the step after the update) --------------------
+ * The forward pass of the same three models for every particle: what the reference's examples hand to function_posterior
+ * (stein/samplers/abstract_stein_sampler.py:157-168) and then average.  One call gives any non-empty subset of
+ *   pred [n][batch]  f_pb, row-major: the layout function_posterior returns
+ *   mean [batch]     1/n sum_p f_pb
+ *   var  [batch]     1/n sum_p (f_pb - mean_b)^2                      (np.var's default; 0 for n = 1)
+ *   lpd  [batch]     log(1/n sum_p exp(l_pb)), the log predictive density of y_b; needs y
+ * and the summaries never materialise [n][batch].  An output passed as NULL is not computed and nothing is written for it.
+ *   z_pb = x_b . w_p (GLM) or the network output relu(X w1 + b1) w2 + b2;  f_pb = z_pb with STEIN_PRED_LINK (logits,
+ *   regression mean, network output); with STEIN_PRED_MEAN f_pb = sigmoid(z_pb) for STEIN_GLM_LOGISTIC and z_pb otherwise.
+ *   l_pb: linear    1/2 log tau - 1/2 tau (y_b - z_pb)^2 - 1/2 log 2 pi, tau = noise_precision (read only for this)
+ *         logistic  y_b z_pb - softplus(z_pb)
+ *         network   1/2 lg_p - 1/2 exp(lg_p) (y_b - z_pb)^2 - 1/2 log 2 pi, lg_p = the particle's log_gamma column
+ * theta, X, y, cols as for the score producers (the same limits: n_feats <= 1024, n_in <= 4, n_hidden <= 1024:
+ * STEIN_E_UNSUPPORTED); columns outside the model are not read.  n and batch are at most 2^30 each (STEIN_E_SHAPE beyond).
+ * Workspace: a call that asks for mean, var or lpd needs stein_predict_workspace_bytes(n, batch) bytes: 20 bytes per row
+ * and particle slice, at most 20 * min(1024 * batch, 2^19 + batch); independent of d; STEIN_E_WORKSPACE without it.  It may
+ * hold anything on entry and carries nothing from call to call.  A call that only asks for pred needs none (NULL, 0).
+ * Deterministic: no atomics; the particle slices are merged in slice order, so a repeated call is bit-identical.
+ * Refused before any launch: all four outputs NULL, lpd without y, an unknown kind / output (STEIN_E_BADARG); columns that
+ * do not fit or overlap (STEIN_E_SHAPE). */
+enum { STEIN_PRED_LINK = 0, STEIN_PRED_MEAN = 1 };
+int stein_predict_workspace_bytes(int64_t n, int64_t batch, size_t* out_bytes);
+int stein_predict_glm(const float* theta, int64_t n, int64_t d, int kind, int output, int64_t w_col, int64_t n_feats,
+                      const float* X, const float* y, int64_t batch, double noise_precision,
+                      float* pred, float* mean, float* var, float* lpd,
+                      void* workspace, size_t ws_bytes, void* stream);
+int stein_predict_bnn(const float* theta, int64_t n, int64_t d, int64_t n_in, int64_t n_hidden, const int64_t* cols,
+                      int output, const float* X, const float* y, int64_t batch,
+                      float* pred, float* mean, float* var, float* lpd, void* workspace, size_t ws_bytes, void* stream);
+
 /* small helpers used by the host layer */
 int stein_cast_f64_to_f32(const double* src, float* dst, int64_t count, void* stream);
 int stein_cast_f32_to_bf16(const float* src, void* dst, int64_t count, void* stream);

@@ -33,6 +33,7 @@ FLAG_FOLD = 512     # the fused call takes the folded contraction (K.W, W = G - 
 FLAG_NO_FOLD = 1024  # ... never takes it
 FLAG_KSD = 256      # also the kernelized Stein discrepancy sums: sqnorm is double[3] = |phi|^2, S, S_diag
 GLM_LINEAR, GLM_LOGISTIC = 0, 1
+PRED_LINK, PRED_MEAN = 0, 1
 SPEC_TABLE_WORDS = 65544          # uint64 words of the rank-summed window table ...
 SPEC_TABLE_OFFSET_WORDS = 1 << 21  # ... which starts 2^21 words into the SPEC section (slots + entry buffer)
 SPEC_HIT_OFFSET, SPEC_SKIP_L0_OFFSET = 64 + 28, 64 + 52   # uint32 state words inside the SELECT section
@@ -60,6 +61,9 @@ _SIGNATURES = {
     "stein_spec_update": [_vp, _vp],
     "stein_score_glm": [_vp, _i64, _i64, _int, _i64, _i64, _i64, _vp, _vp, _i64, _dbl, _dbl, _dbl, _vp, _vp],
     "stein_score_bnn": [_vp, _i64, _i64, _i64, _i64, _c.POINTER(_i64), _vp, _vp, _i64, _dbl, _dbl, _dbl, _vp, _vp],
+    "stein_predict_workspace_bytes": [_i64, _i64, _c.POINTER(_sz)],
+    "stein_predict_glm": [_vp, _i64, _i64, _int, _int, _i64, _i64, _vp, _vp, _i64, _dbl, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    "stein_predict_bnn": [_vp, _i64, _i64, _i64, _i64, _c.POINTER(_i64), _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "stein_rank_begin": [_vp, _i64, _i64, _i64, _i64, _int, _vp, _sz, _int, _vp],
     "stein_rank_pick": [_i64, _i64, _i64, _i64, _int, _vp, _sz, _int, _vp, _vp, _vp, _vp],
     "stein_rank_radix": [_int, _int, _i64, _i64, _i64, _i64, _int, _vp, _sz, _int, _vp, _vp, _vp],
@@ -238,6 +242,14 @@ def stream_median_plan(n, d):
 def debug_stream_median_grid(blocks):
     """Test hook (per calling thread): workgroups of the streaming median's histogram launches; 0 restores the rule."""
     call("stein_debug_stream_median_grid", int(blocks))
+
+
+def predict_workspace_bytes(n, batch):
+    """Workspace bytes of a stein_predict_* call that asks for a summary (mean, var, lpd): 20 bytes per row and particle
+    slice, independent of d.  Host arithmetic."""
+    total = _sz(0)
+    call("stein_predict_workspace_bytes", n, batch, ctypes.byref(total))
+    return int(total.value)
 
 
 def version():

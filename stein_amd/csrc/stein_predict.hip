@@ -1,0 +1,434 @@
+// stein_predict.hip -- posterior predictive producers: the forward pass of the three models the score producers cover
+// (stein_score.hip), for every particle, read out as the per-particle outputs pred[n][batch] and / or as per-test-point
+// ensemble summaries that never materialise [n][batch].  This is the step immediately AFTER the SVGD update: the reference's
+// examples end in function_posterior (stein/samplers/abstract_stein_sampler.py:157-168) and average what it returns.
+//
+//   z_pb   GLM      x_b . w_p
+//          network  sum_h relu(b1_h + sum_f x_bf w1_fh) w2_h + b2          (the pred_b of stein_score.hip)
+//   f_pb   STEIN_PRED_LINK: z_pb;  STEIN_PRED_MEAN: sigmoid(z_pb) for the logistic model, z_pb otherwise
+//   mean_b = 1/n sum_p f_pb,  var_b = 1/n sum_p (f_pb - mean_b)^2,  lpd_b = log(1/n sum_p exp(l_pb))
+//   l_pb   linear    1/2 log tau - 1/2 tau (y_b - z_pb)^2 - 1/2 log 2 pi
+//          logistic  y_b z_pb - softplus(z_pb),  softplus(z) = max(z, 0) + log1p(exp(-|z|))
+//          network   1/2 lg_p - 1/2 e^lg_p (y_b - z_pb)^2 - 1/2 log 2 pi,   lg_p the particle's log_gamma
+//
+// Mapping: the reduction a summary needs runs ACROSS PARTICLES, so the rows of X go on the lanes (the score kernels put the
+// features there).  A workgroup owns a tile of PR_ROWS rows x one slice of the particles; every lane keeps its row's running
+// state (count, mean, M2 by Welford's update; running max and sum exp(l - max)) in registers and walks the slice PR_PASS
+// particles at a time, their weights staged in LDS and read at one address by every lane (broadcast, 16 bytes a read).
+// No shuffle and no atomic anywhere.  Each (slice, row) writes one partial state to the workspace; k_predict_finish merges
+// the slices in slice order (Chan et al.'s pairwise update and a max / rescaled-sum merge, both in fp64, as a fixed tree).  A slice's
+// particle count follows from its index, so it is not stored, and every workspace word that is read was written by the
+// same call: the workspace may hold anything on entry.
+#include "stein_common.h"
+
+constexpr int PR_ROWS = 256;         // rows of X per workgroup: one per lane
+constexpr int PR_PASS = 16;          // particles per pass: their outputs are 16 registers of every lane
+constexpr int PR_SLICE_CAP = 1024;   // particle slices at most: the workspace is 20 bytes per (slice, row)
+constexpr int PR_TARGET_WGS = 2048;  // workgroups wanted: eight per CU (the loops wait on LDS, so more resident workgroups
+                                     // hide it; DESIGN.md 6e on what was and was not recorded); a small batch is filled
+                                     // up with slices
+constexpr int PR_FC = 58;            // GLM: features of the X tile per LDS chunk ([256][59] floats = 59 KB)
+constexpr int PR_HC = 64;            // network: hidden units of the PR_PASS staged particles per LDS chunk
+constexpr int PR_NIN_MAX = 4;        // the score producers' own limits
+constexpr int PR_WIDTH_MAX = 1024;
+// n and batch at most: the kernels index particles and rows in int and step past the end by less than a slice (p_begin + per
+// < 2 n) or a row tile (row < batch + PR_ROWS) before they clamp, so both stay below 2^31
+constexpr int64_t PR_COUNT_MAX = (int64_t)1 << 30;
+constexpr float PR_HALF_LOG_2PI = 0.91893853320467274178f;
+
+struct PredCols { int w1, b1, w2, b2, loggam; };
+// of the particles seen so far (their count is the caller's loop index): the slice's first output as a shift, mean and M2 of
+// the outputs minus that shift (a common offset of the outputs then costs no digits), running max and sum exp(l - max)
+struct PredState { float shift, mean, m2, mx, se; };
+constexpr int PR_STATE = 5;          // floats per (slice, row) of the workspace
+
+// particle number k (0-based) of this lane's slice: its output f and, when the lpd is wanted, its log likelihood l
+__device__ __forceinline__ void pred_accumulate(PredState& st, int k, float f, float l, bool want_mv, bool want_lpd) {
+  if (want_mv) {   // Welford on g = f - shift: k = 0 gives g = 0, mean = 0, m2 = 0 exactly
+    if (k == 0) st.shift = f;
+    const float g = f - st.shift;
+    const float delta = g - st.mean;
+    st.mean = fmaf(delta, 1.f / (float)(k + 1), st.mean);
+    st.m2 = fmaf(delta, g - st.mean, st.m2);
+  }
+  if (want_lpd) {
+    if (k == 0) {   // an empty state has no max: no (-inf) - (-inf)
+      st.mx = l;
+      st.se = 1.f;
+    } else {
+      const float e = l == st.mx ? 1.f : expf(-fabsf(l - st.mx));
+      if (l > st.mx) {
+        st.se = fmaf(st.se, e, 1.f);
+        st.mx = l;
+      } else {
+        st.se += e;
+      }
+    }
+  }
+}
+
+__device__ __forceinline__ void pred_store_state(const PredState& st, float* __restrict__ part, int slice, int B, int row,
+                                                 bool want_mv, bool want_lpd) {
+  float* p = part + (size_t)slice * PR_STATE * B + row;   // [slice][shift, mean, m2, max, sum][B]
+  if (want_mv) {
+    p[0] = st.shift;
+    p[(size_t)B] = st.mean;
+    p[2 * (size_t)B] = st.m2;
+  }
+  if (want_lpd) {
+    p[3 * (size_t)B] = st.mx;
+    p[4 * (size_t)B] = st.se;
+  }
+}
+
+// fc = features per chunk (F when the whole tile fits, else PR_FC), ld = floats per staged row of X (odd: lane t reads
+// xs[t * ld + f], 64 different banks)
+__global__ __launch_bounds__(256) void k_predict_glm(const float* __restrict__ theta, int n, int d, int kind, int output,
+                                                     int w_col, int F, int fc, int ld, const float* __restrict__ X,
+                                                     const float* __restrict__ y, int B, int per, float half_tau, float c0,
+                                                     float* __restrict__ pred, float* __restrict__ part, int want_mv,
+                                                     int want_lpd) {
+  extern __shared__ float lds[];
+  float* xs = lds;                   // [PR_ROWS][ld]
+  float* ws = lds + PR_ROWS * ld;    // [fc][PR_PASS]
+  const int t = threadIdx.x;
+  const int row0 = blockIdx.x * PR_ROWS, row = row0 + t;
+  const bool live = row < B;
+  const int p_begin = blockIdx.y * per, p_end = min(n, p_begin + per);
+  const int nfc = (F + fc - 1) / fc;
+  const bool logistic = kind == STEIN_GLM_LOGISTIC, sigmoid = logistic && output == STEIN_PRED_MEAN;
+  const float yb = (want_lpd && live) ? y[row] : 0.f;
+  PredState st = {0.f, 0.f, 0.f, 0.f, 0.f};
+  auto stage_x = [&](int f0, int len) {   // rows past the batch are staged as zeros
+    for (int i = t; i < PR_ROWS * len; i += 256) {
+      const int r = i / len, f = i - r * len;
+      xs[r * ld + f] = row0 + r < B ? X[(size_t)(row0 + r) * F + f0 + f] : 0.f;
+    }
+  };
+  if (nfc == 1) stage_x(0, F);   // the whole tile fits: staged once for every particle of the slice
+  for (int p0 = p_begin; p0 < p_end; p0 += PR_PASS) {
+    const int cnt = min(PR_PASS, p_end - p0);
+    float z[PR_PASS];
+#pragma unroll
+    for (int k = 0; k < PR_PASS; ++k) z[k] = 0.f;
+    for (int c = 0; c < nfc; ++c) {
+      const int f0 = c * fc, len = min(fc, F - f0);
+      __syncthreads();   // every lane is past its last read of ws (and of xs)
+      if (nfc > 1) stage_x(f0, len);
+      for (int i = t; i < PR_PASS * len; i += 256) {
+        const int k = i / len, f = i - k * len;
+        ws[f * PR_PASS + k] = k < cnt ? theta[(size_t)(p0 + k) * d + w_col + f0 + f] : 0.f;
+      }
+      __syncthreads();
+      const float* xr = xs + t * ld;
+#pragma unroll 2
+      for (int f = 0; f < len; ++f) {
+        const float x = xr[f];
+        const float4* w4 = reinterpret_cast<const float4*>(ws + f * PR_PASS);
+#pragma unroll
+        for (int q = 0; q < PR_PASS / 4; ++q) {
+          const float4 w = w4[q];
+          z[4 * q + 0] = fmaf(x, w.x, z[4 * q + 0]);
+          z[4 * q + 1] = fmaf(x, w.y, z[4 * q + 1]);
+          z[4 * q + 2] = fmaf(x, w.z, z[4 * q + 2]);
+          z[4 * q + 3] = fmaf(x, w.w, z[4 * q + 3]);
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < PR_PASS; ++k) {
+      if (k < cnt) {   // a particle past the slice's end is no particle: it is not counted as f = 0
+        const float zz = z[k];
+        const float f = sigmoid ? 1.f / (1.f + expf(-zz)) : zz;
+        if (pred && live) pred[(size_t)(p0 + k) * B + row] = f;
+        float l = 0.f;
+        if (want_lpd) {
+          if (logistic) {
+            l = yb * zz - (fmaxf(zz, 0.f) + log1pf(expf(-fabsf(zz))));
+          } else {
+            const float r = yb - zz;
+            l = fmaf(-half_tau, r * r, c0);
+          }
+        }
+        pred_accumulate(st, p0 - p_begin + k, f, l, want_mv, want_lpd);
+      }
+    }
+  }
+  if (live && part) pred_store_state(st, part, blockIdx.y, B, row, want_mv, want_lpd);
+}
+
+// NIN input features in registers per lane; the PR_PASS staged particles' b1, w2 and w1 rows of a chunk of PR_HC hidden
+// units in LDS (hidden units past H are staged as zeros: relu(0) * 0 adds an exact zero)
+template <int NIN>
+__global__ __launch_bounds__(256) void k_predict_bnn(const float* __restrict__ theta, int n, int d, int H, PredCols c,
+                                                     const float* __restrict__ X, const float* __restrict__ y, int B, int per,
+                                                     float* __restrict__ pred, float* __restrict__ part, int want_mv,
+                                                     int want_lpd) {
+  constexpr int PW = (NIN + 2) * PR_HC;   // staged floats per particle: b1 [PR_HC], w2 [PR_HC], w1 [NIN][PR_HC]
+  __shared__ __attribute__((aligned(16))) float lw[PR_PASS * PW];
+  __shared__ float lp[PR_PASS][4];        // per particle: b2, 1/2 lg - 1/2 log 2 pi, 1/2 e^lg
+  const int t = threadIdx.x;
+  const int row = blockIdx.x * PR_ROWS + t;
+  const bool live = row < B;
+  const int p_begin = blockIdx.y * per, p_end = min(n, p_begin + per);
+  float x[NIN];
+#pragma unroll
+  for (int f = 0; f < NIN; ++f) x[f] = live ? X[(size_t)row * NIN + f] : 0.f;
+  const float yb = (want_lpd && live) ? y[row] : 0.f;
+  PredState st = {0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int p0 = p_begin; p0 < p_end; p0 += PR_PASS) {
+    const int cnt = min(PR_PASS, p_end - p0);
+    float z[PR_PASS];
+#pragma unroll
+    for (int k = 0; k < PR_PASS; ++k) z[k] = 0.f;
+    for (int h0 = 0; h0 < H; h0 += PR_HC) {
+      const int len = min(PR_HC, H - h0), len4 = (len + 3) & ~3;
+      __syncthreads();   // every lane is past its last read of lw and lp
+      for (int i = t; i < PR_PASS * len4; i += 256) {
+        const int k = i / len4, h = i - k * len4;
+        const bool ok = k < cnt && h < len;
+        const float* th = theta + (size_t)(p0 + (ok ? k : 0)) * d + h0 + h;
+        float* dst = lw + k * PW + h;
+        dst[0] = ok ? th[c.b1] : 0.f;
+        dst[PR_HC] = ok ? th[c.w2] : 0.f;
+#pragma unroll
+        for (int f = 0; f < NIN; ++f) dst[(2 + f) * PR_HC] = ok ? th[c.w1 + f * H] : 0.f;
+      }
+      if (h0 == 0 && t < cnt) {
+        const float* th = theta + (size_t)(p0 + t) * d;
+        const float lg = th[c.loggam];
+        lp[t][0] = th[c.b2];
+        lp[t][1] = fmaf(0.5f, lg, -PR_HALF_LOG_2PI);
+        lp[t][2] = 0.5f * expf(lg);
+      }
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < PR_PASS; ++k) {
+        if (k < cnt) {
+          const float* wk = lw + k * PW;
+          float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+#pragma unroll 2
+          for (int h = 0; h < len4; h += 4) {
+            float4 v = *reinterpret_cast<const float4*>(wk + h);
+            const float4 w2 = *reinterpret_cast<const float4*>(wk + PR_HC + h);
+#pragma unroll
+            for (int f = 0; f < NIN; ++f) {
+              const float4 w1 = *reinterpret_cast<const float4*>(wk + (2 + f) * PR_HC + h);
+              v.x = fmaf(x[f], w1.x, v.x);
+              v.y = fmaf(x[f], w1.y, v.y);
+              v.z = fmaf(x[f], w1.z, v.z);
+              v.w = fmaf(x[f], w1.w, v.w);
+            }
+            a0 = fmaf(fmaxf(v.x, 0.f), w2.x, a0);
+            a1 = fmaf(fmaxf(v.y, 0.f), w2.y, a1);
+            a2 = fmaf(fmaxf(v.z, 0.f), w2.z, a2);
+            a3 = fmaf(fmaxf(v.w, 0.f), w2.w, a3);
+          }
+          z[k] += (a0 + a1) + (a2 + a3);
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < PR_PASS; ++k) {
+      if (k < cnt) {
+        const float f = z[k] + lp[k][0];
+        if (pred && live) pred[(size_t)(p0 + k) * B + row] = f;
+        float l = 0.f;
+        if (want_lpd) {
+          const float r = yb - f;
+          l = fmaf(-lp[k][2], r * r, lp[k][1]);
+        }
+        pred_accumulate(st, p0 - p_begin + k, f, l, want_mv, want_lpd);
+      }
+    }
+  }
+  if (live && part) pred_store_state(st, part, blockIdx.y, B, row, want_mv, want_lpd);
+}
+
+// The slices' states merged in slice order, in fp64.  A workgroup takes PF_ROWS rows; its PF_GROUPS thread groups each merge
+// a contiguous range of the slices in order, then one thread per row merges the groups in order: a fixed tree, so the
+// result depends on nothing but the states.  (One thread walking all the slices of a row took longer than the forward
+// pass at 512 slices.)
+constexpr int PF_ROWS = 16, PF_GROUPS = 16;
+
+__global__ __launch_bounds__(256) void k_predict_finish(const float* __restrict__ part, int slices, int per, int n, int B,
+                                                        float* __restrict__ mean, float* __restrict__ var,
+                                                        float* __restrict__ lpd) {
+  __shared__ double sh[5][PF_GROUPS][PF_ROWS];   // count, mean, M2, max, sum
+  const int r = threadIdx.x % PF_ROWS, g = threadIdx.x / PF_ROWS;
+  const int b = blockIdx.x * PF_ROWS + r;
+  const int per_g = (slices + PF_GROUPS - 1) / PF_GROUPS;
+  const int s0 = g * per_g, s1 = min(slices, s0 + per_g);
+  const size_t sB = (size_t)B;
+  double cnt = 0.0, m = 0.0, m2 = 0.0, top = 0.0, sum = 0.0;
+  if (b < B && s0 < s1) {
+    const float* p = part + b;
+    if (mean || var) {   // Chan et al.: (count, mean, M2) of the union of two sets
+      for (int s = s0; s < s1; ++s) {
+        const float* ps = p + (size_t)s * PR_STATE * sB;
+        const double cs = (double)min(per, n - s * per);
+        const double ms = (double)ps[0] + (double)ps[sB], m2s = ps[2 * sB];
+        const double tot = cnt + cs, delta = ms - m;
+        m += delta * (cs / tot);
+        m2 += m2s + delta * delta * (cnt * cs / tot);
+        cnt = tot;
+      }
+    }
+    cnt = (double)(min((long)n, (long)s1 * per) - (long)s0 * per);
+    if (lpd) {
+      top = (double)p[((size_t)s0 * PR_STATE + 3) * sB];
+      for (int s = s0 + 1; s < s1; ++s) top = fmax(top, (double)p[((size_t)s * PR_STATE + 3) * sB]);
+      for (int s = s0; s < s1; ++s) {
+        const double mx = p[((size_t)s * PR_STATE + 3) * sB], se = p[((size_t)s * PR_STATE + 4) * sB];
+        sum += mx == top ? se : se * exp(mx - top);
+      }
+    }
+  }
+  sh[0][g][r] = cnt; sh[1][g][r] = m; sh[2][g][r] = m2; sh[3][g][r] = top; sh[4][g][r] = sum;
+  __syncthreads();
+  if (g != 0 || b >= B) return;
+  for (int k = 1; k < PF_GROUPS; ++k) {   // (group 0 is never empty)
+    const double cs = sh[0][k][r];
+    if (cs == 0.0) break;
+    const double tot = cnt + cs, delta = sh[1][k][r] - m;
+    m += delta * (cs / tot);
+    m2 += sh[2][k][r] + delta * delta * (cnt * cs / tot);
+    cnt = tot;
+    const double tk = sh[3][k][r], sk = sh[4][k][r];
+    if (tk > top) {
+      sum = sum * exp(top - tk) + sk;
+      top = tk;
+    } else {
+      sum += tk == top ? sk : sk * exp(tk - top);
+    }
+  }
+  if (mean) mean[b] = (float)m;
+  if (var) var[b] = (float)(m2 / (double)n);
+  if (lpd) lpd[b] = (float)(top + log(sum) - log((double)n));
+}
+
+// ---- host side -----------------------------------------------------------------------------------------
+struct PredPlan { int row_tiles, slices, per; };
+
+static PredPlan predict_plan(int64_t n, int64_t batch) {
+  PredPlan p;
+  p.row_tiles = (int)((batch + PR_ROWS - 1) / PR_ROWS);
+  int64_t s = (PR_TARGET_WGS + p.row_tiles - 1) / p.row_tiles;   // slices that fill the card at this batch
+  if (s > PR_SLICE_CAP) s = PR_SLICE_CAP;
+  const int64_t passes = (n + PR_PASS - 1) / PR_PASS;            // no slice of less than one pass
+  if (s > passes) s = passes;
+  p.per = (int)((n + s - 1) / s);
+  p.slices = (int)((n + p.per - 1) / p.per);
+  return p;
+}
+
+// An upper bound of the plan's slices * batch states, monotone in both arguments (the plan's own product is not: a row tile
+// more can cost slices).  slices <= passes, <= PR_SLICE_CAP, and <= PR_TARGET_WGS / row_tiles + 1 with row_tiles >= batch /
+// PR_ROWS, so slices * batch <= PR_TARGET_WGS * PR_ROWS + batch.
+static size_t predict_ws_bytes(int64_t n, int64_t batch) {
+  int64_t s = (n + PR_PASS - 1) / PR_PASS;
+  if (s > PR_SLICE_CAP) s = PR_SLICE_CAP;
+  int64_t states = s * batch;
+  const int64_t by_target = (int64_t)PR_TARGET_WGS * PR_ROWS + batch;
+  if (states > by_target) states = by_target;
+  return (size_t)states * PR_STATE * sizeof(float);
+}
+
+extern "C" int stein_predict_workspace_bytes(int64_t n, int64_t batch, size_t* out_bytes) {
+  if (!out_bytes) return stein_fail(STEIN_E_BADARG, "NULL pointer");
+  if (n < 1 || batch < 1 || n > PR_COUNT_MAX || batch > PR_COUNT_MAX)
+    return stein_fail(STEIN_E_SHAPE, "bad shape n=%lld batch=%lld", (long long)n, (long long)batch);
+  *out_bytes = predict_ws_bytes(n, batch);
+  return STEIN_OK;
+}
+
+// the checks the two entry points share, in the order the header lists them
+static int predict_check(const float* theta, const float* X, const float* y, int64_t n, int64_t d, int64_t batch,
+                         int64_t width, int output, const float* pred, const float* mean, const float* var,
+                         const float* lpd) {
+  if (!theta || !X) return stein_fail(STEIN_E_BADARG, "NULL pointer");
+  if (!pred && !mean && !var && !lpd) return stein_fail(STEIN_E_BADARG, "no output requested: pred, mean, var and lpd are all NULL");
+  if (lpd && !y) return stein_fail(STEIN_E_BADARG, "lpd needs y");
+  if (output != STEIN_PRED_LINK && output != STEIN_PRED_MEAN) return stein_fail(STEIN_E_BADARG, "output %d", output);
+  if (n < 1 || d < 1 || batch < 1 || width < 1 || n > PR_COUNT_MAX || d > 0x7fffffffl || batch > PR_COUNT_MAX)
+    return stein_fail(STEIN_E_SHAPE, "bad shape n=%lld d=%lld batch=%lld width=%lld", (long long)n, (long long)d,
+                      (long long)batch, (long long)width);
+  return STEIN_OK;
+}
+
+static int predict_check_ws(int64_t n, int64_t batch, bool summary, const void* workspace, size_t ws_bytes) {
+  if (!summary) return STEIN_OK;   // a call that only asks for pred needs no workspace
+  if (!workspace) return stein_fail(STEIN_E_WORKSPACE, "mean, var and lpd need a workspace (stein_predict_workspace_bytes)");
+  const size_t need = predict_ws_bytes(n, batch);
+  if (ws_bytes < need) return stein_fail(STEIN_E_WORKSPACE, "workspace too small: %zu < %zu bytes", ws_bytes, need);
+  return STEIN_OK;
+}
+
+static int predict_finish(const PredPlan& pl, int64_t n, int64_t batch, const float* part, float* mean, float* var,
+                          float* lpd, hipStream_t s) {
+  hipLaunchKernelGGL(k_predict_finish, dim3((unsigned)((batch + PF_ROWS - 1) / PF_ROWS)), dim3(256), 0, s, part, pl.slices, pl.per, (int)n,
+                     (int)batch, mean, var, lpd);
+  LAUNCH_CHECK("k_predict_finish");
+  return STEIN_OK;
+}
+
+extern "C" int stein_predict_glm(const float* theta, int64_t n, int64_t d, int kind, int output, int64_t w_col,
+                                 int64_t n_feats, const float* X, const float* y, int64_t batch, double noise_precision,
+                                 float* pred, float* mean, float* var, float* lpd, void* workspace, size_t ws_bytes,
+                                 void* stream) {
+  if (int rc = predict_check(theta, X, y, n, d, batch, n_feats, output, pred, mean, var, lpd)) return rc;
+  if (kind != STEIN_GLM_LINEAR && kind != STEIN_GLM_LOGISTIC) return stein_fail(STEIN_E_BADARG, "kind %d", kind);
+  if (w_col < 0 || w_col + n_feats > d)
+    return stein_fail(STEIN_E_SHAPE, "weights [%lld, %lld) do not fit d=%lld", (long long)w_col, (long long)(w_col + n_feats),
+                      (long long)d);
+  if (n_feats > PR_WIDTH_MAX) return stein_fail(STEIN_E_UNSUPPORTED, "more than 1024 features per particle");
+  if (lpd && kind == STEIN_GLM_LINEAR && !(noise_precision > 0.0 && noise_precision < INFINITY))
+    return stein_fail(STEIN_E_BADARG, "noise_precision must be positive and finite");
+  const bool summary = mean || var || lpd;
+  if (int rc = predict_check_ws(n, batch, summary, workspace, ws_bytes)) return rc;
+  const PredPlan pl = predict_plan(n, batch);
+  const int fc = (int)(n_feats <= PR_FC ? n_feats : PR_FC);
+  const int ld = fc | 1;
+  const size_t lds_bytes = ((size_t)PR_ROWS * ld + (size_t)fc * PR_PASS) * sizeof(float);
+  const double tau = (lpd && kind == STEIN_GLM_LINEAR) ? noise_precision : 1.0;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_predict_glm, dim3((unsigned)pl.row_tiles, (unsigned)pl.slices), dim3(256), lds_bytes, s, theta, (int)n,
+                     (int)d, kind, output, (int)w_col, (int)n_feats, fc, ld, X, y, (int)batch, pl.per, (float)(0.5 * tau),
+                     (float)(0.5 * log(tau) - (double)PR_HALF_LOG_2PI), pred, summary ? (float*)workspace : nullptr,
+                     (mean || var) ? 1 : 0, lpd ? 1 : 0);
+  LAUNCH_CHECK("k_predict_glm");
+  return summary ? predict_finish(pl, n, batch, (const float*)workspace, mean, var, lpd, s) : STEIN_OK;
+}
+
+extern "C" int stein_predict_bnn(const float* theta, int64_t n, int64_t d, int64_t n_in, int64_t n_hidden,
+                                 const int64_t* cols /*[6]: w1, b1, w2, b2, log_lambda, log_gamma*/, int output,
+                                 const float* X, const float* y, int64_t batch, float* pred, float* mean, float* var,
+                                 float* lpd, void* workspace, size_t ws_bytes, void* stream) {
+  if (!cols) return stein_fail(STEIN_E_BADARG, "NULL pointer");
+  if (int rc = predict_check(theta, X, y, n, d, batch, n_hidden, output, pred, mean, var, lpd)) return rc;
+  if (n_in < 1) return stein_fail(STEIN_E_SHAPE, "bad shape n_in=%lld", (long long)n_in);
+  if (n_in > PR_NIN_MAX) return stein_fail(STEIN_E_UNSUPPORTED, "more than %d input features", PR_NIN_MAX);
+  if (n_hidden > PR_WIDTH_MAX) return stein_fail(STEIN_E_UNSUPPORTED, "more than 1024 hidden units");
+  const int64_t len[6] = {n_in * n_hidden, n_hidden, n_hidden, 1, 1, 1};
+  for (int i = 0; i < 6; ++i) {
+    if (cols[i] < 0 || cols[i] + len[i] > d) return stein_fail(STEIN_E_SHAPE, "block %d does not fit d=%lld", i, (long long)d);
+    for (int j = 0; j < i; ++j)
+      if (cols[i] < cols[j] + len[j] && cols[j] < cols[i] + len[i]) return stein_fail(STEIN_E_SHAPE, "blocks %d and %d overlap", j, i);
+  }
+  const bool summary = mean || var || lpd;
+  if (int rc = predict_check_ws(n, batch, summary, workspace, ws_bytes)) return rc;
+  const PredPlan pl = predict_plan(n, batch);
+  const PredCols c = {(int)cols[0], (int)cols[1], (int)cols[2], (int)cols[3], (int)cols[5]};
+  hipStream_t s = (hipStream_t)stream;
+#define PR_LAUNCH_BNN(NIN)                                                                                              \
+  hipLaunchKernelGGL((k_predict_bnn<NIN>), dim3((unsigned)pl.row_tiles, (unsigned)pl.slices), dim3(256), 0, s, theta,    \
+                     (int)n, (int)d, (int)n_hidden, c, X, y, (int)batch, pl.per, pred,                                   \
+                     summary ? (float*)workspace : nullptr, (mean || var) ? 1 : 0, lpd ? 1 : 0)
+  if (n_in == 1) PR_LAUNCH_BNN(1);
+  else if (n_in == 2) PR_LAUNCH_BNN(2);
+  else if (n_in == 3) PR_LAUNCH_BNN(3);
+  else PR_LAUNCH_BNN(4);
+#undef PR_LAUNCH_BNN
+  LAUNCH_CHECK("k_predict_bnn");
+  return summary ? predict_finish(pl, n, batch, (const float*)workspace, mean, var, lpd, s) : STEIN_OK;
+}

@@ -284,8 +284,14 @@ class AbstractSteinSampler:
         [p n/P, (p + 1) n/P), so the gathered array is indexed like the reference's, all n particles: :160-162), unless
         gather=False.  The mean over `axis` is taken of that [n, out] array, as the reference does (:165-168).  Returns
         NumPy, the same array on every rank.  Collective when sharded: every rank must call it.
+
+        A callable that carries ``wants_matrix = True`` (the predictive producers of stein_amd/predict.py) is handed the
+        packed float32 [n_local, d] matrix instead of the dict of views, as the score producers are.
         """
-        arg = self.theta if self._access is not None else self.theta_matrix
+        if getattr(func, "wants_matrix", False):
+            arg = self._matrix_f32()
+        else:
+            arg = self.theta if self._access is not None else self.theta_matrix
         with torch.no_grad():
             out = func(arg, feed_dict)
         out = torch.as_tensor(out).reshape(self.n_local, -1).detach()
@@ -299,6 +305,29 @@ class AbstractSteinSampler:
             out = full
         out = out.cpu().numpy()
         return out.mean(axis=axis) if axis is not None else out
+
+    def _matrix_f32(self):
+        """the packed particles as float32: the matrix itself, or the fp32 copy of a float64 sampler"""
+        if self.dtype == torch.float32:
+            return self.theta_matrix
+        return self._theta_f32() if self.kernel_dtype == torch.float32 else self.theta_matrix.float()
+
+    def posterior_predictive(self, producer, feed):
+        """Per-test-point ensemble summaries of a predictive producer (stein_amd.predict.GlmPredict / BnnPredict) under
+        the current particles: {"mean", "var"} of its outputs over the particles and, when `feed` has a "y", "lpd", the log
+        predictive density log(1/n sum_p p(y_b | theta_p)) -- NumPy arrays of [batch].  The [n, batch] matrix that
+        function_posterior returns is never formed; only the three vectors cross to the host.  One rank only."""
+        if self._group is not None:
+            raise ValueError("posterior_predictive works on one rank only: a sharded sampler would have to merge the "
+                             "ranks' states; use function_posterior, which gathers the outputs")
+        if not hasattr(producer, "summary"):
+            raise ValueError("posterior_predictive needs a predictive producer (GlmPredict / BnnPredict)")
+        with torch.no_grad():
+            mean, var, lpd = producer.summary(self._matrix_f32(), feed)
+        out = {"mean": mean.cpu().numpy(), "var": var.cpu().numpy()}
+        if lpd is not None:
+            out["lpd"] = lpd.cpu().numpy()
+        return out
 
     def samples_all(self):
         """All n particles as one float64 [n, d] NumPy array on every rank (the reference's `samples`, stein_sampler.py:73-78,

@@ -88,3 +88,6 @@ class BnnScore:
                   y.data_ptr(), batch, self.n_train, self.gamma_a, self.gamma_b, out.data_ptr(),
                   torch.cuda.current_stream(theta.device).cuda_stream)
         return out
+
+
+from .predict import BnnPredict, GlmPredict  # noqa: E402,F401  (the producers of the step after the update, beside these)
