@@ -268,6 +268,52 @@ int stein_stream_median(const void* theta, int64_t n, int64_t d, int dtype,
                         void* workspace, size_t ws_bytes, int flags, void* stream);
 int stein_debug_stream_median_grid(int blocks);   /* test hook, per calling thread; 0 = default */
 
+/* ---- streaming step and Stein discrepancy under the inverse multiquadric (IMQ) kernel ------------------------------
+ * The SVGD direction with the heavy-tailed kernel
+ *   k_ij = (1 + D_ij / c2)^(-1/2),   c2 = 2 h2,   h2 = *h2_in,   D_ij = max(|theta_i - theta_j|^2, 0)
+ * in place of the RBF exp(-D_ij / (2 h2)): the same bandwidth (the same h2 tensor, the same median heuristic -- take it
+ * with stein_stream_median), the exponent fixed at -1/2.  Under the RBF kernel the Stein discrepancy does not control
+ * convergence for d >= 3; under this one it does (Gorham & Mackey 2017), so this is the path for the KERNEL, not a faster
+ * one: by instruction count it costs about twice stein_svgd_phi_stream (measured: README.md, profiles/imq_ab.txt).
+ * With k3 = k^3, k5 = k^5:  grad_{theta_j} k(theta_j, theta_i) = k3_ij (theta_i - theta_j) / c2, and
+ *   n phi_i = (K G)_i + [ rs3_i theta_i - (K3 theta)_i ] / c2,          rs3_i = sum_j k3_ij
+ * The gradient is not proportional to the kernel, so no folded operand exists: every 128 x 128 tile of D is turned into
+ * two images, k and k3, and contracted with G and with theta at once, then dropped (stein_amd/csrc/stein_imq.hip; the
+ * distance tiles are stein_svgd_phi_stream's and stein_stream_median's, value for value).
+ *   theta, score, h2_in, phi, sqnorm_out, flags, workspace, stream: exactly as stein_svgd_phi_stream -- fp32 only
+ *   (STEIN_BF16: STEIN_E_UNSUPPORTED), flags == 0 (STEIN_E_BADARG), n >= 1, d >= 1 (STEIN_E_SHAPE), h2_in a DEVICE float[1]
+ *   read on the device in every call, a 16-byte-aligned workspace (STEIN_E_BADARG) of at least the size below
+ *   (STEIN_E_WORKSPACE) whose contents on entry do not matter.  No K_out / dK_out, one rank.
+ * stein_svgd_phi_imq_ksd: the step and the Stein discrepancy sums under this kernel at *h2_in.  Stein kernel
+ *   u_p(i,j) = k_ij g_i.g_j + k3_ij (g_i - g_j).(theta_i - theta_j) / c2 + d k3_ij / c2 - 3 k5_ij D_ij / c2^2
+ * and summed over the pairs, per element e = (i, column), with rd5_i = sum_j k5_ij D_ij:
+ *   S      = sum_e g_e (K G)_e + (2 / c2) sum_e g_e [ rs3_i theta_e - (K3 theta)_e ] + sum_i [ d rs3_i / c2 - 3 rd5_i / c2^2 ]
+ *   S_diag = sum_e g_e^2 + n d / c2
+ *   phi        : [n][d] float, or NULL: the statistic alone (the three sums are the same bits)
+ *   sums_out   : DEVICE double[3] = |phi|^2, S, S_diag.  KSD^2_V = S / n^2, KSD^2_U = (S - S_diag) / (n (n - 1)).
+ *   phi and sums_out[0] are stein_svgd_phi_imq's to the bit.
+ * Sizes, N = roundup(n, 128), dk = roundup(d, 32), dc = roundup(d, 128), every term rounded up to 256 bytes:
+ *   stein_imq_workspace_bytes = 4 N + 4 (6 dc + 4) + 6 N dk + 2 x 6 N dc + 2 x 4 jsplit n d + 4 jsplit n + 8 min(1024, ceil(n d / 1024))
+ *   (row norms | scales | theta's planes | theta^T's planes | G^T's planes | partial K.G | partial K3.theta | partial rs3 |
+ *   |phi|^2 block partials); never smaller than stein_stream_median_workspace_bytes, so one buffer serves the median call
+ *   and then the step.
+ *   stein_imq_ksd_workspace_bytes = stein_imq_workspace_bytes + 4 jsplit n + 16 min(1024, ceil(n d / 1024)) (partial rd5 | the
+ *   S and S_diag block partials), appended: no offset of the plain layout moves.
+ * stein_imq_plan (host arithmetic): row_tiles = ceil(n / 128), col_blocks = ceil(d / 128) and
+ * jsplit = clamp(floor(256 / (row_tiles col_blocks)), 1, row_tiles) with empty tails dropped: one workgroup per (row tile,
+ * 128-column block, j range), stein_stream_plan's rule.  The ranges' partial sums are added in range order, no float atomics:
+ * a repeated call is bit-identical.  stein_debug_stream_jsplit applies to this plan too. */
+int stein_imq_workspace_bytes(int64_t n, int64_t d, int dtype, int flags, size_t* out_bytes);
+int stein_imq_ksd_workspace_bytes(int64_t n, int64_t d, int dtype, int flags, size_t* out_bytes);
+int stein_imq_plan(int64_t n, int64_t d, int* row_tiles, int* col_blocks, int* jsplit);
+int stein_svgd_phi_imq(const void* theta, const void* score, int64_t n, int64_t d, int dtype,
+                       const float* h2_in, float* phi, double* sqnorm_out,
+                       void* workspace, size_t ws_bytes, int flags, void* stream);
+int stein_svgd_phi_imq_ksd(const void* theta, const void* score, int64_t n, int64_t d, int dtype,
+                           const float* h2_in, float* phi /* may be NULL */,
+                           double* sums_out /* [3]: |phi|^2, S, S_diag */,
+                           void* workspace, size_t ws_bytes, int flags, void* stream);
+
 /* ---- staged path (tests, multi-rank: the host puts collectives between the stages) ------------ */
 
 /* r_i = sum_k theta_ik^2            abstract_kernel.py:34 */

@@ -87,6 +87,11 @@ _SIGNATURES = {
     "stein_stream_median_plan": [_i64, _i64, _c.POINTER(_sz), _c.POINTER(_sz), _c.POINTER(_i64), _c.POINTER(_int)],
     "stein_stream_median": [_vp, _i64, _i64, _int, _vp, _vp, _vp, _sz, _int, _vp],
     "stein_debug_stream_median_grid": [_int],
+    "stein_imq_workspace_bytes": [_i64, _i64, _int, _int, _c.POINTER(_sz)],
+    "stein_imq_ksd_workspace_bytes": [_i64, _i64, _int, _int, _c.POINTER(_sz)],
+    "stein_imq_plan": [_i64, _i64, _c.POINTER(_int), _c.POINTER(_int), _c.POINTER(_int)],
+    "stein_svgd_phi_imq": [_vp, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _sz, _int, _vp],
+    "stein_svgd_phi_imq_ksd": [_vp, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _sz, _int, _vp],
     "stein_rownorms": [_vp, _i64, _i64, _int, _vp, _vp],
     "stein_distance_block": [_vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _i64, _vp, _vp, _int, _vp],
     "stein_x3_prepare": [_vp, _vp, _i64, _i64, _int, _vp, _sz, _vp],
@@ -242,6 +247,28 @@ def stream_median_plan(n, d):
 def debug_stream_median_grid(blocks):
     """Test hook (per calling thread): workgroups of the streaming median's histogram launches; 0 restores the rule."""
     call("stein_debug_stream_median_grid", int(blocks))
+
+
+def imq_workspace_bytes(n, d, dtype=F32, flags=0):
+    """Workspace bytes of the IMQ step (stein_svgd_phi_imq): O(n d), never less than the streaming median's.  Host arithmetic."""
+    total = _sz(0)
+    call("stein_imq_workspace_bytes", n, d, dtype, flags, ctypes.byref(total))
+    return int(total.value)
+
+
+def imq_ksd_workspace_bytes(n, d, dtype=F32, flags=0):
+    """Workspace bytes of the IMQ step with the Stein discrepancy sums (stein_svgd_phi_imq_ksd): the plain step's layout with
+    the partial rd5 and two more sets of block partials behind it.  Host arithmetic."""
+    total = _sz(0)
+    call("stein_imq_ksd_workspace_bytes", n, d, dtype, flags, ctypes.byref(total))
+    return int(total.value)
+
+
+def imq_plan(n, d):
+    """-> (row_tiles, col_blocks, jsplit) of the IMQ step's grid.  Host arithmetic."""
+    rt, cb, js = _int(0), _int(0), _int(0)
+    call("stein_imq_plan", n, d, ctypes.byref(rt), ctypes.byref(cb), ctypes.byref(js))
+    return int(rt.value), int(cb.value), int(js.value)
 
 
 def predict_workspace_bytes(n, batch):

@@ -86,6 +86,10 @@ int stein_rank_finish_on(const StepViews& v, const BlockShape& b, const void* th
 int stein_device_error_word(u32** out);
 int stein_take_device_error(void);
 
+// stein_stream.hip: the j ranges stein_debug_stream_jsplit asked for on this thread, 0 = the plan's own rule (the IMQ step's
+// plan, stein_imq.hip, honours the same hook)
+int stein_stream_jsplit_hook(void);
+
 // stein_select.hip: the fused call's median behind its distance pass (k_spec_select, then k_hist_all unless n is small)
 // theta_all / score_all: the call's inputs, read (and dropped) by the select launch's warm slice when the operand is folded
 int stein_fused_select(const StepViews& v, int64_t n, int64_t d, float* h2_out, const void* theta_all, const void* score_all,

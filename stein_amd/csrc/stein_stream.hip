@@ -40,48 +40,18 @@
 //   stein_rownorms, k_colmax, k_make_scales, k_split (theta, row-major image only)   as in the step: the same r, T3, two_s
 //   k_sel_init, then per level:  k_stream_hist<LEVEL>  distance tile -> digit of LEVEL -> LDS histogram -> one flush
 //                                k_resolve             (stein_select.hip) -> prefixes; level 2: lo, hi, median, h2
-// k_stream_hist runs the distance phase of k_phi_stream (st_distance_tile below, one body for both), so the median is the
+// k_stream_hist runs the distance phase of k_phi_stream (st_distance_tile, stein_stream_tile.h: one body for both), so the median is the
 // median of the D values the step exponentiates.
 
 #include "stein_x3.h"
 
 #include "stein_x3_dev.h"
 
-constexpr int ST_THREADS = 512;
-constexpr int ST_ROWS = 128;              // particles per row tile
-constexpr int ST_JT = 128;                // columns of D per step (4 k tiles of the contraction)
-constexpr int ST_COLS = 256;              // columns of W per column group
-constexpr int ST_PLN = ST_ROWS * XROW;    // one plane of one 32-deep k tile of P in LDS: 8 KB
-constexpr int ST_KTB = 2 * ST_PLN;        // hi and lo plane
-constexpr int ST_BUF = (ST_JT / 32) * ST_KTB;   // one P image: 64 KB; two of them
+// the tile geometry (ST_THREADS, ST_ROWS, ST_JT, ST_PLN, ST_KTB, ST_BUF) and the distance phase st_distance_tile, shared by
+// k_phi_stream and k_stream_hist here and by k_phi_imq (stein_imq.hip)
+#include "stein_stream_tile.h"
 
-// The distance phase of one 128 x 128 tile, shared by k_phi_stream and k_stream_hist (one body: both kernels form every
-// S value in the same order, so the streaming median is the median of the very D values the step exponentiates).  Wave
-// (wr, wc) of eight: s[jb][ib] = the 16 x 16 block S^T[j = 64 wc + 16 jb ..][i = 32 wr + 16 ib ..] over all ntk k tiles;
-// ta / tb: this lane's 16 bytes of the first fragment of the row tile's rows 32 wr.. and of the column tile's rows 64 wc..
-__device__ __forceinline__ void st_distance_tile(const u16* __restrict__ ta, const u16* __restrict__ tb, int ntk,
-                                                 f32x4 (&s)[4][2]) {
-#pragma unroll
-  for (int jb = 0; jb < 4; ++jb)
-#pragma unroll
-    for (int ib = 0; ib < 2; ++ib) s[jb][ib] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int kt = 0; kt < ntk; ++kt) {
-    u32x4 fa[2][3], fb[4][3];
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-#pragma unroll
-      for (int ib = 0; ib < 2; ++ib)
-        fa[ib][p] = *reinterpret_cast<const u32x4*>(ta + ((size_t)kt * 3 + p) * XTILE_E + ib * 512);
-#pragma unroll
-      for (int jb = 0; jb < 4; ++jb)
-        fb[jb][p] = *reinterpret_cast<const u32x4*>(tb + ((size_t)kt * 3 + p) * XTILE_E + jb * 512);
-    }
-#pragma unroll
-    for (int jb = 0; jb < 4; ++jb)
-#pragma unroll
-      for (int ib = 0; ib < 2; ++ib) s[jb][ib] = x3_products16<2>(fb[jb], fa[ib], s[jb][ib]);
-  }
-}
+constexpr int ST_COLS = 256;              // columns of W per column group
 
 // The body of k_phi_stream (KSD = false) and of k_phi_stream_ksd (KSD = true: also rd_i = sum_j P_ij D_ij, the second row sum
 // the Stein discrepancy needs -- include/steinhip.h, stein_svgd_phi_stream_ksd -- carried beside rs, reduced like rs and
@@ -589,6 +559,7 @@ extern "C" int stein_debug_stream_jsplit(int jsplit) {
   g_stream_jsplit = jsplit;
   return STEIN_OK;
 }
+int stein_stream_jsplit_hook(void) { return g_stream_jsplit; }   // (stein_imq.hip's plan honours the same hook)
 
 extern "C" int stein_stream_workspace_bytes(int64_t n, int64_t d, int dtype, int flags, size_t* out_bytes) {
   if (!out_bytes) return fail(STEIN_E_BADARG, "out_bytes is NULL");

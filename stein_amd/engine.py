@@ -90,6 +90,18 @@ class HipStages:
         _lib.call_on(T.device, "stein_svgd_phi_stream_ksd", _ptr(T), _ptr(G), n, d, _dt(T), _ptr(h2), _ptr(phi), _ptr(sums),
                      _ptr(ws), ws.numel(), 0, _stream(T))
 
+    def svgd_phi_imq(self, T, G, n, d, h2, phi, sqnorm, ws):
+        """the streaming step under the inverse multiquadric kernel at the bandwidth^2 held by the 1-element device tensor
+        h2 (stein_svgd_phi_imq, include/steinhip.h)"""
+        _lib.call_on(T.device, "stein_svgd_phi_imq", _ptr(T), _ptr(G), n, d, _dt(T), _ptr(h2), _ptr(phi), _ptr(sqnorm),
+                     _ptr(ws), ws.numel(), 0, _stream(T))
+
+    def svgd_phi_imq_ksd(self, T, G, n, d, h2, phi, sums, ws):
+        """the IMQ step and, in the 3-element float64 device tensor sums, |phi|^2 and the Stein discrepancy sums S and S_diag
+        under that kernel; phi may be None: the sums alone (stein_svgd_phi_imq_ksd, include/steinhip.h)"""
+        _lib.call_on(T.device, "stein_svgd_phi_imq_ksd", _ptr(T), _ptr(G), n, d, _dt(T), _ptr(h2), _ptr(phi), _ptr(sums),
+                     _ptr(ws), ws.numel(), 0, _stream(T))
+
     def stream_median(self, T, n, d, h2, median, ws):
         """the median-heuristic bandwidth^2 (and the median) of T's n^2 distances into the 1-element device tensors h2 and
         median (median may be None), in a streaming workspace: no n x n image (stein_stream_median, include/steinhip.h)"""
@@ -229,12 +241,24 @@ class SvgdEngine:
               held in between.  refresh_bandwidth(theta) does the same on demand.  Needs n >= 2.
     median_every : with h2="median", the step period of the median refresh: an integer >= 1 (default 1: every step).
               Refused with a ValueError on any other engine.
+    kernel  : "rbf" (default): exp(-D / (2 h2)), everything above.  "imq": the inverse multiquadric kernel
+              (1 + D / (2 h2))^(-1/2), the heavy-tailed kernel whose Stein discrepancy detects non-convergence for d >= 3
+              (Gorham & Mackey 2017) -- the SAME bandwidth h2, by the same median heuristic.  It exists as a streaming step
+              only (stein_svgd_phi_imq / _ksd; about twice the cost of the RBF streaming step), so h2= is required
+              (h2="median" for the heuristic) and everything a streaming engine offers works as there: discrepancy=True,
+              stein_discrepancy(), stream_discrepancy_sums(), refresh_bandwidth(), median_every=.
     """
 
     def __init__(self, n, d, device="cuda", group=None, stages=None, x3=None, dtype=torch.float32, small=True,
                  window=True, force_collectives=False, comm="auto", tile_distance=False, dist_window=None, ksd=False,
-                 fold=None, h2=None, median_every=1):
+                 fold=None, h2=None, median_every=1, kernel="rbf"):
         self.n, self.d = int(n), int(d)
+        if kernel not in ("rbf", "imq"):
+            raise ValueError("kernel must be \"rbf\" or \"imq\", got %r" % (kernel,))
+        if kernel == "imq" and h2 is None:
+            raise ValueError("kernel=\"imq\": the IMQ kernel exists as a streaming step only (no stored-D path); pass h2= "
+                             "(h2=\"median\" for the median heuristic's bandwidth)")
+        self.kernel = kernel
         self.streaming = h2 is not None
         stream_median = isinstance(h2, str) and h2 == "median"
         if isinstance(median_every, bool) or not isinstance(median_every, int) or median_every < 1:
@@ -353,6 +377,13 @@ class SvgdEngine:
 
     def _init_stream(self, h2, device, group, stages, x3, dtype, ksd):
         """The engine of the streaming step (h2 given): what it cannot do is refused here, by name."""
+        imq = self.kernel == "imq"
+        if imq and (group is not None or dtype != torch.float32 or (x3 is not None and not x3) or ksd):
+            what = "group=" if group is not None else "bf16" if dtype != torch.float32 else \
+                "x3=False" if (x3 is not None and not x3) else "ksd=True"
+            raise ValueError("kernel=\"imq\": %s is not supported; the IMQ step is the streaming step's shape: one rank, float32 "
+                             "inputs, the split path, and the Stein discrepancy per call (compute_phi(theta, score, "
+                             "discrepancy=True), then stein_discrepancy())" % what)
         if group is not None:
             raise ValueError("h2=: the streaming step runs on one rank; group= is not supported with a supplied bandwidth")
         if dtype != torch.float32:
@@ -387,7 +418,7 @@ class SvgdEngine:
         self.dtype, self.x3, self.ksd, self.fold = torch.float32, True, False, False
         self.flags = 0
         self.stages = stages if stages is not None else HipStages()
-        if not hasattr(self.stages, "svgd_phi_stream"):
+        if not hasattr(self.stages, "svgd_phi_imq" if imq else "svgd_phi_stream"):
             raise ValueError("h2=: the stages have no streaming step (HipStages has)")
         if self.median_every is not None and not hasattr(self.stages, "stream_median"):
             raise ValueError("h2=\"median\": the stages have no streaming median (HipStages has)")
@@ -397,8 +428,17 @@ class SvgdEngine:
         self.dist_window, self.window_hit = False, None
         self._ksd_ready = False
         self._have_dist, self._one_kernel, self.dist_upper = False, False, False
-        self.row_tiles, self.col_groups, self.jsplit = _lib.stream_plan(self.n, self.d)
-        self.ws_bytes = _lib.stream_workspace_bytes(self.n, self.d)
+        if imq:
+            # (col_groups: 128-column blocks here).  The workspace serves the largest of the calls made: the median call too
+            self.row_tiles, self.col_groups, self.jsplit = _lib.imq_plan(self.n, self.d)
+            self.ws_bytes = _lib.imq_workspace_bytes(self.n, self.d)
+            if self.median_every is not None:
+                self.ws_bytes = max(self.ws_bytes, _lib.stream_median_workspace_bytes(self.n, self.d))
+            self._step_name = "svgd_phi_imq"
+        else:
+            self.row_tiles, self.col_groups, self.jsplit = _lib.stream_plan(self.n, self.d)
+            self.ws_bytes = _lib.stream_workspace_bytes(self.n, self.d)
+            self._step_name = "svgd_phi_stream"
         dev = self.device
         self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)   # nothing in it is read before it is written
         self.phi = torch.empty(self.n, self.d, dtype=torch.float32, device=dev)
@@ -422,10 +462,14 @@ class SvgdEngine:
     def _stream_ksd_workspace(self):
         """Grow the workspace to what stein_svgd_phi_stream_ksd needs (first use).  The larger buffer serves the plain step
         and the median call too -- the layout only appends -- and nothing in it is carried between calls."""
-        if not hasattr(self.stages, "svgd_phi_stream_ksd"):
+        if not hasattr(self.stages, self._step_name + "_ksd"):
             raise ValueError("discrepancy=True: the stages have no streaming step with the statistic (HipStages has)")
-        need = _lib.stream_ksd_workspace_bytes(self.n, self.d)
-        assert need >= _lib.stream_workspace_bytes(self.n, self.d)
+        if self.kernel == "imq":
+            need = _lib.imq_ksd_workspace_bytes(self.n, self.d)
+            assert need >= _lib.imq_workspace_bytes(self.n, self.d)
+        else:
+            need = _lib.stream_ksd_workspace_bytes(self.n, self.d)
+            assert need >= _lib.stream_workspace_bytes(self.n, self.d)
         if self.ws_bytes < need:
             self.ws = None      # (release before allocating: at the largest shapes both would not fit)
             self.ws = torch.empty(need, dtype=torch.uint8, device=self.device)
@@ -442,7 +486,7 @@ class SvgdEngine:
         self._stream_ksd_workspace()
         if self.median_every is not None:
             self.stages.stream_median(theta, self.n, self.d, self.h2, self.median, self.ws)
-        self.stages.svgd_phi_stream_ksd(theta, score, self.n, self.d, self.h2, None, self._sums, self.ws)
+        getattr(self.stages, self._step_name + "_ksd")(theta, score, self.n, self.d, self.h2, None, self._sums, self.ws)
         self._ksd_ready = True
         return self._sums
 
@@ -721,9 +765,9 @@ class SvgdEngine:
                     st.stream_median(theta_local, n, d, self.h2, self.median, self.ws)
                 self._stream_calls += 1
             if discrepancy:
-                st.svgd_phi_stream_ksd(theta_local, score_local, n, d, self.h2, self.phi, self._sums, self.ws)
+                getattr(st, self._step_name + "_ksd")(theta_local, score_local, n, d, self.h2, self.phi, self._sums, self.ws)
             else:
-                st.svgd_phi_stream(theta_local, score_local, n, d, self.h2, self.phi, self.sqnorm, self.ws)
+                getattr(st, self._step_name)(theta_local, score_local, n, d, self.h2, self.phi, self.sqnorm, self.ws)
             self._ksd_ready = bool(discrepancy)
             return self.phi
         if self.ksd and (mark is not None or (self.sharded and K_out is not None)):

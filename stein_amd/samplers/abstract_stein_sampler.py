@@ -29,7 +29,7 @@ class AbstractSteinSampler:
 
     def __init__(self, n_particles, log_p, theta=None, *, model_vars=None, device="cuda", dtype=torch.float32,
                  group=None, seed=None, kernel_dtype=torch.float32, x3=None, ksd=False, bandwidth=None, h2=None,
-                 median_every=1, ksd_every=None):
+                 median_every=1, ksd_every=None, kernel="rbf"):
         """
         n_particles : total number of particles n (across all ranks).
         log_p       : see SteinSampler.
@@ -57,6 +57,9 @@ class AbstractSteinSampler:
                       with the first, also computes the kernelized Stein discrepancy at that step's bandwidth
                       (stein_discrepancy() returns the latest).  None (default): never.  Refused on any other sampler, where
                       ksd=True is the switch.
+        kernel      : "rbf" (default) or "imq": the inverse multiquadric kernel (1 + D / (2 h^2))^(-1/2) at the same bandwidth
+                      h, for the SVGD direction and for the Stein discrepancy of ksd_every= (engine.SvgdEngine, kernel=).
+                      It exists on the streaming path only: give bandwidth= (a float, or "median") or h2=.
         """
         self.n_particles = int(n_particles)
         self.log_p = log_p
@@ -119,6 +122,12 @@ class AbstractSteinSampler:
         self.theta_matrix = packed.to(device=self.device, dtype=dtype).contiguous()
         self.n_params = self.theta_matrix.shape[1]
         self.kernel_dtype = kernel_dtype
+        if kernel not in ("rbf", "imq"):
+            raise ValueError("kernel must be \"rbf\" or \"imq\", got %r" % (kernel,))
+        if kernel == "imq" and bandwidth is None and h2 is None:
+            raise ValueError("kernel=\"imq\": the IMQ kernel exists on the streaming path only; pass bandwidth= (a float h, or "
+                             "\"median\" for the median heuristic) or h2=")
+        self.kernel_name = kernel
         if bandwidth is not None:
             if h2 is not None:
                 raise ValueError("give bandwidth= (a float h) or h2= (a device tensor holding h^2), not both")
@@ -143,7 +152,7 @@ class AbstractSteinSampler:
         self._updates = 0           # update_particles calls so far
         self._ksd_sums = None       # [S, S_diag] of the latest step that computed them (streaming path; a device copy)
         self.engine = SvgdEngine(self.n_particles, self.n_params, device=self.device, group=group, x3=x3,
-                                 dtype=kernel_dtype, ksd=ksd, h2=h2, median_every=median_every)
+                                 dtype=kernel_dtype, ksd=ksd, h2=h2, median_every=median_every, kernel=kernel)
         self._theta32 = (self.theta_matrix if dtype == kernel_dtype else
                          torch.empty(self.n_local, self.n_params, dtype=kernel_dtype, device=self.device))
 

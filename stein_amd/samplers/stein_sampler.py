@@ -28,7 +28,7 @@ class SteinSampler(AbstractSteinSampler):
         # compute_phi call it exactly as the reference does (abstract_stein_sampler.py:103)
         from ..kernels import SquaredExponentialKernel
         self.kernel = SquaredExponentialKernel(self.n_particles, None, device=self.device) \
-            if self._group is None else None
+            if self._group is None and self.kernel_name == "rbf" else None   # (kernel="imq": no n x n kernel_and_grad exists)
 
     def score_matrix(self, batch_feed=None):
         """[n_local, d] float32 device tensor of d log_p / d theta for every particle."""

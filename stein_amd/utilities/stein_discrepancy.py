@@ -20,15 +20,22 @@ def _stream_bandwidth(bandwidth):
     return h * h
 
 
-def kernelized_stein_discrepancy(theta, score, statistic="u", bandwidth=None):
+def kernelized_stein_discrepancy(theta, score, statistic="u", bandwidth=None, kernel="rbf"):
     """KSD^2 (a float) of the particles `theta` with scores `score` = d log p / d theta, both [n, d] float32 or bfloat16
     device tensors, under the RBF kernel with the median-heuristic bandwidth SVGD uses: statistic "u" (U-statistic,
     unbiased, the default) or "v" (V-statistic).  Runs the fused phi call with the statistic on a transient engine (its
     workspace is allocated for the call: about 4 n^2 bytes for large n) and applies nothing.
     bandwidth: None (default) is the above.  A positive finite float h (K = exp(-D / (2 h^2)), h^2 rounded to float32) or
     "median" (the exact median heuristic, taken without the n x n image) runs the streaming step's statistic instead
-    (stein_svgd_phi_stream_ksd with phi = NULL) in an O(n d) workspace: float32 inputs only."""
+    (stein_svgd_phi_stream_ksd with phi = NULL) in an O(n d) workspace: float32 inputs only.
+    kernel: "rbf" (default) or "imq": the statistic under the inverse multiquadric kernel (1 + D / (2 h^2))^(-1/2) at the
+    same bandwidth (stein_svgd_phi_imq_ksd with phi = NULL) -- the kernel whose discrepancy detects non-convergence for
+    d >= 3.  It runs on the streaming path only: bandwidth=None then means "median"."""
     from ..engine import SvgdEngine
+    if kernel not in ("rbf", "imq"):
+        raise ValueError("kernel must be \"rbf\" or \"imq\", got %r" % (kernel,))
+    if kernel == "imq" and bandwidth is None:
+        bandwidth = "median"
     h2 = _stream_bandwidth(bandwidth) if bandwidth is not None else None
     if h2 is not None:
         for name, t in (("theta", theta), ("score", score)):
@@ -53,7 +60,7 @@ def kernelized_stein_discrepancy(theta, score, statistic="u", bandwidth=None):
     if statistic not in ("u", "v"):
         raise ValueError("statistic must be 'u' or 'v'")
     if h2 is not None:
-        eng = SvgdEngine(n, d, device=theta.device, h2=h2)
+        eng = SvgdEngine(n, d, device=theta.device, h2=h2, kernel=kernel)
         with torch.cuda.device(theta.device):
             eng.stream_discrepancy_sums(theta.contiguous(), score.contiguous())
             return float(eng.stein_discrepancy(statistic).item())
