@@ -86,8 +86,8 @@ int stein_rank_finish_on(const StepViews& v, const BlockShape& b, const void* th
 int stein_device_error_word(u32** out);
 int stein_take_device_error(void);
 
-// stein_stream.hip: the j ranges stein_debug_stream_jsplit asked for on this thread, 0 = the plan's own rule (the IMQ step's
-// plan, stein_imq.hip, honours the same hook)
+// stein_stream.hip: the j ranges stein_debug_stream_jsplit asked for on this thread, 0 = the plan's own rule (read by
+// stream_make_layout, stein_stream_host.h: the plan of the RBF streaming step and of the IMQ step, stein_imq.hip)
 int stein_stream_jsplit_hook(void);
 
 // stein_select.hip: the fused call's median behind its distance pass (k_spec_select, then k_hist_all unless n is small)

@@ -3,20 +3,23 @@
 // With h2 known before the step starts nothing needs all of D at once: the folded operand W = G - theta / h2 (stein_x3.hip,
 // "folded operand") is built first, and a tile of D is exponentiated and contracted with W the moment its accumulators are
 // complete, then dropped.  The workspace is O(n d): row norms, scales, theta's row-major planes, W's transposed planes and
-// the partial sums (stein_stream_make_layout below).
+// the partial sums (stream_make_layout, stein_stream_host.h).
 //
 //   stein_rownorms, k_colmax, k_make_scales, k_split (theta, row-major image only), k_split_w   as they are (stein_x3.hip)
 //   k_phi_stream        distance tile -> P = exp2(c D + 14) -> O += P.W, running rowsum(P); D and K never reach memory
 //   k_stream_finish     sums the j ranges in order, phi = (K.W + rowsum(K) theta / h2) / n, |phi|^2 block partials (fp64)
-//   k_stream_sqsum      one workgroup: the block partials -> sqnorm_out
+//   k_stream_sum        (stein_stream_tile.h) one workgroup: the block partials -> sqnorm_out
 // stein_svgd_phi_stream_ksd, the step with the Stein discrepancy sums at its own bandwidth (include/steinhip.h), launches
 // the KSD forms of the same bodies: k_phi_stream_ksd (a second running row sum, rd = rowsum(P o D)), k_stream_finish_ksd
-// (reads the score rows too; three sets of block partials) and k_stream_sqsum3.  No K.theta, no further column space.
+// (reads the score rows too; three sets of block partials) and k_stream_sum on a grid of three.  No K.theta, no further
+// column space.
 // The P image's swizzle, the fp16 split and the exponent offset (pswz, cvt_pk_f16, f16_resid_lo / _hi, PEXP_H2) are
 // stein_x3_dev.h's, the ones the stored-D contraction uses; the size limits, align_up and the resident-workgroup count are
-// stein_host.h's, shared with stein_make_layout.  The finish pass stays a kernel of this file although k_phi_finish's FOLD
-// form (steinhip.hip) gives the same bits: at 8 j ranges that kernel takes its generic loop and the step measured slower
-// ("streaming step").
+// stein_host.h's, shared with stein_make_layout.  The tile phases other than the element function, the frame of the finish
+// pass (st_finish_body) and k_stream_sum are stein_stream_tile.h's, and the host side around the launches is
+// stein_stream_host.h's: the IMQ step (stein_imq.hip) runs the same code.  The finish pass stays a kernel of this file
+// although k_phi_finish's FOLD form (steinhip.hip) gives the same bits: at 8 j ranges that kernel takes its generic loop and
+// the step measured slower ("streaming step").
 //
 // k_phi_stream: a 512-thread workgroup (8 waves, two per SIMD) owns 128 rows of particles x one column group of W (two
 // 128-column blocks) x one range of 128-column j tiles.  Per j tile:
@@ -40,18 +43,16 @@
 //   stein_rownorms, k_colmax, k_make_scales, k_split (theta, row-major image only)   as in the step: the same r, T3, two_s
 //   k_sel_init, then per level:  k_stream_hist<LEVEL>  distance tile -> digit of LEVEL -> LDS histogram -> one flush
 //                                k_resolve             (stein_select.hip) -> prefixes; level 2: lo, hi, median, h2
-// k_stream_hist runs the distance phase of k_phi_stream (st_distance_tile, stein_stream_tile.h: one body for both), so the median is the
-// median of the D values the step exponentiates.
+// k_stream_hist runs the distance phase of k_phi_stream (st_distance_tile, stein_stream_tile.h: one body for both), so the
+// median is the median of the D values the step exponentiates.
 
 #include "stein_x3.h"
 
 #include "stein_x3_dev.h"
 
-// the tile geometry (ST_THREADS, ST_ROWS, ST_JT, ST_PLN, ST_KTB, ST_BUF) and the distance phase st_distance_tile, shared by
-// k_phi_stream and k_stream_hist here and by k_phi_imq (stein_imq.hip)
-#include "stein_stream_tile.h"
-
-constexpr int ST_COLS = 256;              // columns of W per column group
+// the tile geometry (ST_THREADS, ST_ROWS, ST_JT, ST_PLN, ST_KTB, ST_BUF) and the tile phases (stein_stream_tile.h), the layout
+// and the entry points' prologue: shared with the IMQ step (stein_imq.hip)
+#include "stein_stream_host.h"
 
 // The body of k_phi_stream (KSD = false) and of k_phi_stream_ksd (KSD = true: also rd_i = sum_j P_ij D_ij, the second row sum
 // the Stein discrepancy needs -- include/steinhip.h, stein_svgd_phi_stream_ksd -- carried beside rs, reduced like rs and
@@ -71,17 +72,14 @@ __device__ __forceinline__ void phi_stream_body(unsigned char* smem, const u16* 
   const int i0 = tile_m * ST_ROWS;
   const int jt0 = z * jtiles_per, jt1 = min(jtiles, jt0 + jtiles_per);
 
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int l15 = lane & 15, lq = lane >> 4;
-  // distance role: rows [32 wr, 32 wr + 32) x columns [64 wc, 64 wc + 64) of the 128 x 128 tile
-  const int wr = w >> 1, wc = w & 1;
-  // contraction role: all 128 rows x 32 columns at wcol of 128-column block g.  A block past the matrix's last (an odd block
-  // count: d <= 128, or the last column group) has nothing to contract: its four waves only take part in the distance
-  // tiles and the barriers (wave-uniform test)
+  const StRoles ro = st_roles();
+  const int lane = ro.lane, w = ro.w, l15 = ro.l15, lq = ro.lq, wr = ro.wr, wc = ro.wc, wcol = ro.wcol;
+  // contraction role: the 32 columns at wcol of 128-column block g.  A block past the matrix's last (an odd block count:
+  // d <= 128, or the last column group) has nothing to contract: its four waves only take part in the distance tiles and
+  // the barriers (wave-uniform test)
   const int g = 2 * cg + (w >> 2);
   const bool live = g < cblocks;
   const int gl = min(g, cblocks - 1);
-  const int wcol = (w & 3) * 32;
 
   const float cexp = -1.44269504088896341f / (2.f * *h2p);   // exp(-D / (2 h2)) = exp2(cexp D)
   const float two_s = sc[4 * dc + 1];
@@ -126,78 +124,21 @@ __device__ __forceinline__ void phi_stream_body(unsigned char* smem, const u16* 
           if constexpr (KSD) rd[ib] = __builtin_fmaf(q[e], (j0 + jc + e < n) ? dv : 0.f, rd[ib]);
         }
         rs[ib] += (q[0] + q[1]) + (q[2] + q[3]);
-        const u32 h0 = cvt_pk_f16(q[0], q[1]), h1 = cvt_pk_f16(q[2], q[3]);
-        const u32 o0 = cvt_pk_f16(f16_resid_lo(h0, q[0]), f16_resid_hi(h0, q[1]));
-        const u32 o1 = cvt_pk_f16(f16_resid_lo(h1, q[2]), f16_resid_hi(h1, q[3]));
-        const int row = wr * 32 + ib * 16 + l15;
-        unsigned char* dst = buf + (jc >> 5) * ST_KTB + row * XROW + pswz(row, (jc & 31) >> 3) + (jc & 4) * 2;
-        *reinterpret_cast<uint2*>(dst) = make_uint2(h0, h1);
-        *reinterpret_cast<uint2*>(dst + ST_PLN) = make_uint2(o0, o1);
+        const StSplit4 p = st_split4(q);
+        st_stage4(st_image_dst(buf, wr * 32 + ib * 16 + l15, jc), p);
       }
     }
     __syncthreads();
     // ---- contraction: O += P . W_j over the tile's (up to) four 32-deep k tiles
     for (int kt = 0; live && kt < ST_JT / 32; ++kt) {
       if (j0 + kt * 32 >= n) break;   // P is zero there
-      u32x4 b[2][3];
-      const u16* __restrict__ src = wb + ((size_t)jt * (ST_JT / 32) + kt) * 3 * XTILE_E;
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int p = 0; p < 2; ++p) b[j][p] = *reinterpret_cast<const u32x4*>(src + p * XTILE_E + j * 512);
-      const unsigned char* As = buf + kt * ST_KTB + aoff;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        u32x4 a[3];
-#pragma unroll
-        for (int p = 0; p < 2; ++p) a[p] = *reinterpret_cast<const u32x4*>(As + i * 16 * XROW + p * ST_PLN);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = x3_products16<2>(a, b[j], acc[i][j]);
-      }
+      st_contract_ktile(acc, buf + kt * ST_KTB + aoff, wb + ((size_t)jt * (ST_JT / 32) + kt) * 3 * XTILE_E);
     }
   }
 
   // ---- partial O of this j range (out-scaled), partial row sums
-  if (live) {
-    float* __restrict__ Oz = O + (size_t)z * n * d;
-    const float* __restrict__ osc = sc + 2 * dc;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int col = g * 128 + wcol + j * 16 + l15;
-      if (col >= d) continue;
-      const float os = osc[col];
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int row = i0 + i * 16 + 4 * lq + e;
-          if (row < n) Oz[(size_t)row * d + col] = acc[i][j][e] * os;
-        }
-    }
-  }
-  if (cg == 0) {
-    // a row's sum: the four lane groups lq of a wave, then the two waves wc = 0, 1 (through LDS, in that order)
-    __syncthreads();   // every wave is past its last read of the P images
-    float* red = reinterpret_cast<float*>(smem);   // [2][128] (KSD: rd's [2][128] behind it)
-#pragma unroll
-    for (int ib = 0; ib < 2; ++ib) {
-      float a = rs[ib];
-      a += __shfl_xor(a, 16);
-      a += __shfl_xor(a, 32);
-      if (lq == 0) red[wc * ST_ROWS + wr * 32 + ib * 16 + l15] = a;
-      if constexpr (KSD) {
-        float b = rd[ib];
-        b += __shfl_xor(b, 16);
-        b += __shfl_xor(b, 32);
-        if (lq == 0) red[(2 + wc) * ST_ROWS + wr * 32 + ib * 16 + l15] = b;
-      }
-    }
-    __syncthreads();
-    const int row = i0 + t;
-    if (t < ST_ROWS && row < n) RS[(size_t)z * n + row] = (red[t] + red[ST_ROWS + t]) * sc[4 * dc + 2];
-    if constexpr (KSD)
-      if (t < ST_ROWS && row < n) RD[(size_t)z * n + row] = (red[2 * ST_ROWS + t] + red[3 * ST_ROWS + t]) * sc[4 * dc + 2];
-  }
+  if (live) st_store_partial(O + (size_t)z * n * d, sc + 2 * dc, acc, g * 128 + wcol, i0, lq, l15, n, d);
+  if (cg == 0) st_reduce_rows<KSD>(smem, rs, rd, RS, RD, z, i0, n, sc + 4 * dc + 2, ro);
 }
 
 __global__ __launch_bounds__(ST_THREADS) void k_phi_stream(const u16* __restrict__ T3, int ntk, const u16* __restrict__ Wt3,
@@ -284,9 +225,8 @@ __global__ __launch_bounds__(ST_THREADS) void k_stream_hist(const u16* __restric
                                                             const SelState* __restrict__ st, u64* __restrict__ hist, int n,
                                                             int nt, long tiles, int flush_tiles) {
   __shared__ u32 h[2 * STEIN_HIST_BINS];
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int l15 = lane & 15, lq = lane >> 4;
-  const int wr = w >> 1, wc = w & 1;   // rows [32 wr, 32 wr + 32) x columns [64 wc, 64 wc + 64) of the tile
+  const StRoles ro = st_roles();   // (the distance role only)
+  const int t = ro.t, lane = ro.lane, l15 = ro.l15, lq = ro.lq, wr = ro.wr, wc = ro.wc;
   const u32 pa = st->prefix[0], pb = st->prefix[1];
   const bool two = LEVEL > 0 && st->diverged != 0u;
   const int nbins = (two ? 2 : 1) * STEIN_HIST_BINS;
@@ -328,105 +268,28 @@ __global__ __launch_bounds__(ST_THREADS) void k_stream_hist(const u16* __restric
     if (h[b]) atomicAdd(&hist[b], (u64)h[b]);
 }
 
-// phi = (sum_z O_z + (sum_z RS_z) theta / h2) / n (the folded finish of k_phi_finish, steinhip.hip) and this workgroup's
-// fp64 partial of |phi|^2.  vec (bit 0): d % 4 == 0 and O, T and phi 16-byte aligned; KSD, bit 1: so is G.
-// KSD (k_stream_finish_ksd): also this workgroup's partials of the Stein discrepancy sums S and S_diag (include/steinhip.h,
-// stein_svgd_phi_stream_ksd) into kpart[0][blocks] and kpart[1][blocks], in fp64 from the fp32 ow = sum_z O_z, rs and
-// rd = sum_z RD_z (range order) and the score rows G; the rd term is added once per row, by the thread that holds its
-// column 0.  phi may then be NULL: only the store is skipped.
-__device__ __forceinline__ void stream_ksd_terms(float g, float ow, float th, float rs, double ih, double& s, double& sd) {
-  const double gd = g, t = (double)th * ih, w = gd - t;
-  s += w * (double)ow + (double)rs * (t * (2.0 * gd - t) + ih);   // g^2 - w^2 = t (2 g - t), t = theta / h2
-  sd += gd * gd + ih;
-}
-
-template <bool KSD>
-__device__ __forceinline__ void stream_finish_body(const float* __restrict__ O, const float* __restrict__ RS,
-                                                   const float* __restrict__ RD, const float* __restrict__ T,
-                                                   const float* __restrict__ G, const float* __restrict__ h2p,
-                                                   float* __restrict__ phi, double* __restrict__ sqpart,
-                                                   double* __restrict__ kpart, int n, int d, int jsplit, int vec) {
-  __shared__ double red[KSD ? 12 : 4];
-  const float h2 = *h2p;
-  const float fn = (float)n;
-  const long total = (long)n * d;
-  const size_t zs = (size_t)n * d;
-  const double ih = 1.0 / (double)h2;   // (KSD)
-  double sq = 0.0, ks = 0.0, kd = 0.0;
-  if (vec & 1) {
-    const long total4 = total >> 2;
-    const int d4 = d >> 2;
-    for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < total4; q += (long)gridDim.x * 256) {
-      const int i = (int)(q / d4);
-      const long e = q << 2;
-      float4 og = make_float4(0.f, 0.f, 0.f, 0.f);
-      float rs = 0.f;
-      for (int z = 0; z < jsplit; ++z) {
-        const float4 a = *reinterpret_cast<const float4*>(O + z * zs + e);
-        og.x += a.x; og.y += a.y; og.z += a.z; og.w += a.w;
-        rs += RS[(size_t)z * n + i];
-      }
-      const float4 th = *reinterpret_cast<const float4*>(T + e);
-      float4 ph;
-      ph.x = (og.x + rs * th.x / h2) / fn; ph.y = (og.y + rs * th.y / h2) / fn;
-      ph.z = (og.z + rs * th.z / h2) / fn; ph.w = (og.w + rs * th.w / h2) / fn;
-      if (!KSD || phi) *reinterpret_cast<float4*>(phi + e) = ph;
-      sq += ((double)ph.x * (double)ph.x + (double)ph.y * (double)ph.y) + ((double)ph.z * (double)ph.z + (double)ph.w * (double)ph.w);
-      if constexpr (KSD) {
-        const float4 g = (vec & 2) ? *reinterpret_cast<const float4*>(G + e) : make_float4(G[e], G[e + 1], G[e + 2], G[e + 3]);
-        stream_ksd_terms(g.x, og.x, th.x, rs, ih, ks, kd);
-        stream_ksd_terms(g.y, og.y, th.y, rs, ih, ks, kd);
-        stream_ksd_terms(g.z, og.z, th.z, rs, ih, ks, kd);
-        stream_ksd_terms(g.w, og.w, th.w, rs, ih, ks, kd);
-        if (q == (long)i * d4) {   // the row's first four columns
-          float rd = 0.f;
-          for (int z = 0; z < jsplit; ++z) rd += RD[(size_t)z * n + i];
-          ks -= 0.5 * ih * ih * (double)rd;
-        }
-      }
-    }
-  } else {
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-      const int i = (int)(e / d);
-      float og = 0.f, rs = 0.f;
-      for (int z = 0; z < jsplit; ++z) {
-        og += O[z * zs + e];
-        rs += RS[(size_t)z * n + i];
-      }
-      const float th = T[e];
-      const float ph = (og + rs * th / h2) / fn;
-      if (!KSD || phi) phi[e] = ph;
-      sq += (double)ph * (double)ph;
-      if constexpr (KSD) {
-        stream_ksd_terms(G[e], og, th, rs, ih, ks, kd);
-        if (e == (long)i * d) {   // the row's column 0
-          float rd = 0.f;
-          for (int z = 0; z < jsplit; ++z) rd += RD[(size_t)z * n + i];
-          ks -= 0.5 * ih * ih * (double)rd;
-        }
-      }
-    }
+// The RBF step's part of the finish pass (st_finish_body, stein_stream_tile.h): one operand, ow = sum_z O_z;
+// phi = (ow + rs theta / h2) / n (the folded finish of k_phi_finish, steinhip.hip); the statistic's terms (include/steinhip.h,
+// stein_svgd_phi_stream_ksd) per element, and per row -rd / (2 h2^2).
+struct RbfFinish {
+  static constexpr int NO = 1;
+  float h2, fn;
+  double ih;   // (KSD)
+  __device__ RbfFinish(const float* __restrict__ h2p, int n, int) : h2(*h2p), fn((float)n), ih(1.0 / (double)*h2p) {}
+  __device__ float phi(const float (&o)[NO], float th, float rs) const { return (o[0] + rs * th / h2) / fn; }
+  __device__ void ksd_terms(float g, const float (&o)[NO], float th, float rs, double& s, double& sd) const {
+    const double gd = g, t = (double)th * ih, w = gd - t;
+    s += w * (double)o[0] + (double)rs * (t * (2.0 * gd - t) + ih);   // g^2 - w^2 = t (2 g - t), t = theta / h2
+    sd += gd * gd + ih;
   }
-  if constexpr (KSD) {
-    double part[3] = {sq, ks, kd};
-    block_sum256(part, red);
-    if (threadIdx.x == 0) {
-      sqpart[blockIdx.x] = part[0];
-      kpart[blockIdx.x] = part[1];
-      kpart[gridDim.x + blockIdx.x] = part[2];
-    }
-  } else {
-    double part[1] = {sq};
-    block_sum256(part, red);
-    if (threadIdx.x == 0) sqpart[blockIdx.x] = part[0];
-  }
-}
+  __device__ double row_term(float, float rd) const { return -0.5 * ih * ih * (double)rd; }
+};
 
 __global__ __launch_bounds__(256) void k_stream_finish(const float* __restrict__ O, const float* __restrict__ RS,
                                                        const float* __restrict__ T, const float* __restrict__ h2p,
                                                        float* __restrict__ phi, double* __restrict__ sqpart, int n, int d,
                                                        int jsplit, int vec) {
-  stream_finish_body<false>(O, RS, nullptr, T, nullptr, h2p, phi, sqpart, nullptr, n, d, jsplit, vec);
+  st_finish_body<RbfFinish, false>(O, nullptr, RS, nullptr, T, nullptr, h2p, phi, sqpart, nullptr, n, d, jsplit, vec);
 }
 
 __global__ __launch_bounds__(256) void k_stream_finish_ksd(const float* __restrict__ O, const float* __restrict__ RS,
@@ -434,153 +297,32 @@ __global__ __launch_bounds__(256) void k_stream_finish_ksd(const float* __restri
                                                            const float* __restrict__ G, const float* __restrict__ h2p,
                                                            float* __restrict__ phi, double* __restrict__ sqpart,
                                                            double* __restrict__ kpart, int n, int d, int jsplit, int vec) {
-  stream_finish_body<true>(O, RS, RD, T, G, h2p, phi, sqpart, kpart, n, d, jsplit, vec);
-}
-
-// the block partials of k_stream_finish, in a fixed order -> sqnorm_out[0]
-__global__ __launch_bounds__(256) void k_stream_sqsum(const double* __restrict__ part, int count, double* __restrict__ out) {
-  __shared__ double red[4];
-  double s[1] = {0.0};
-  for (int i = threadIdx.x; i < count; i += 256) s[0] += part[i];
-  block_sum256(s, red);
-  if (threadIdx.x == 0) out[0] = s[0];
-}
-
-// the same for k_stream_finish_ksd's three sets, one workgroup each: sqpart[count] -> out[0], kpart[2][count] -> out[1], out[2]
-__global__ __launch_bounds__(256) void k_stream_sqsum3(const double* __restrict__ sqpart, const double* __restrict__ kpart,
-                                                       int count, double* __restrict__ out) {
-  __shared__ double red[4];
-  const double* __restrict__ part = blockIdx.x == 0 ? sqpart : kpart + (size_t)(blockIdx.x - 1) * count;
-  double s[1] = {0.0};
-  for (int i = threadIdx.x; i < count; i += 256) s[0] += part[i];
-  block_sum256(s, red);
-  if (threadIdx.x == 0) out[blockIdx.x] = s[0];
+  st_finish_body<RbfFinish, true>(O, nullptr, RS, RD, T, G, h2p, phi, sqpart, kpart, n, d, jsplit, vec);
 }
 
 // ================================================================================================
 // host side
 // ================================================================================================
+// (shape check, layout, views, sizes, plan, the entry points' prologue and last launch: stein_stream_host.h, the IMQ step's too)
 static thread_local int g_stream_jsplit = 0;   // stein_debug_stream_jsplit: 0 = the plan's own rule
-
-struct StreamLayout {
-  int64_t row_tiles, col_groups, cblocks, jsplit, jtiles_per, sq_blocks;
-  int64_t rows, dk, dc, nk;                      // padded extents of the planes (the x3_* of SteinLayout)
-  size_t r, sc, t3, wt3, o, rs, sq, total;       // byte offsets, 256-byte aligned
-};
-
-static int stream_check_shape(int64_t n, int64_t d, int dtype, int flags) {
-  if (dtype == STEIN_BF16) return fail(STEIN_E_UNSUPPORTED, "the streaming step takes fp32 inputs (STEIN_F32), not bf16");
-  if (dtype != STEIN_F32) return fail(STEIN_E_UNSUPPORTED, "dtype %d", dtype);
-  if (flags != 0) return fail(STEIN_E_BADARG, "the streaming step takes no flags, got 0x%x", flags);
-  if (n < 1 || d < 1) return fail(STEIN_E_SHAPE, "bad shape n=%lld d=%lld", (long long)n, (long long)d);
-  return stein_check_size(n, d);
-}
-
-// The plan: one workgroup per (row tile, column group, j range).  The j ranges fill the resident grid (one workgroup per CU)
-// when the row tiles and column groups alone do not: jsplit = floor(resident / (row_tiles col_groups)), at most one range
-// per 128-column j tile; ranges are whole j tiles and empty tails are dropped.  So jsplit > 1 only while
-// jsplit row_tiles col_groups <= resident: the partial sums then hold at most resident x 128 x 256 floats (32 MiB),
-// whatever n and d; beyond that there is one range and they are n d floats.
-static int stream_make_layout(int64_t n, int64_t d, StreamLayout* L) {
-  L->row_tiles = (n + ST_ROWS - 1) / ST_ROWS;
-  L->cblocks = (d + 127) / 128;
-  L->col_groups = (d + ST_COLS - 1) / ST_COLS;
-  const int64_t jtiles = L->row_tiles;
-  int64_t want = g_stream_jsplit > 0 ? g_stream_jsplit : (int64_t)(RESIDENT_ONE_PER_CU / (double)(L->row_tiles * L->col_groups));
-  if (want < 1) want = 1;
-  if (want > jtiles) want = jtiles;
-  L->jtiles_per = (jtiles + want - 1) / want;
-  L->jsplit = (jtiles + L->jtiles_per - 1) / L->jtiles_per;
-  L->rows = L->row_tiles * ST_ROWS;
-  L->nk = L->rows;
-  L->dk = (int64_t)align_up((size_t)d, 32);
-  L->dc = (int64_t)align_up((size_t)d, 128);
-  int64_t sqb = (n * d + 1023) / 1024;
-  if (sqb > 1024) sqb = 1024;
-  L->sq_blocks = sqb;
-  size_t at = 0;
-  auto put = [&](size_t bytes) { const size_t o = at; at = align_up(at + bytes, 256); return o; };
-  L->r = put((size_t)L->rows * 4);
-  L->sc = put((size_t)(6 * L->dc + 4) * 4);
-  L->t3 = put((size_t)3 * L->rows * L->dk * 2);
-  L->wt3 = put((size_t)3 * L->dc * L->nk * 2);
-  L->o = put((size_t)L->jsplit * n * d * 4);
-  L->rs = put((size_t)L->jsplit * n * 4);
-  L->sq = put((size_t)sqb * 8);
-  L->total = at;
-  if (L->row_tiles * L->col_groups * L->jsplit > 0x7fffffffll) return fail(STEIN_E_SHAPE, "too many tiles");
-  return STEIN_OK;
-}
-
-// Every address the streaming entry points use, formed once: of a stored-D layout only the planes' extents; the planes the
-// split launchers take; and the step's partial sums (K.W of the j ranges in OG, their rowsum(K) in RS, the |phi|^2 block
-// partials in SQ; no K.theta: nothing here asks for dK, and the statistic does without it -- StreamKsdLayout).
-// The median passes StreamMedianLayout's hist / sel offsets: its histograms and select state lie where the step keeps W's
-// planes and partial sums, which that call never touches.
-static StepViews stream_views(const StreamLayout& L, void* workspace, size_t hist_at = 0, size_t sel_at = 0) {
-  char* ws = (char*)workspace;
-  StepViews v{};
-  v.L.x3_rows = L.rows; v.L.x3_dk = L.dk; v.L.x3_dc = L.dc; v.L.x3_nk = L.nk;
-  v.r = (float*)(ws + L.r);
-  v.planes = ws;
-  v.T3 = (unsigned short*)(ws + L.t3);
-  v.Gt3 = (unsigned short*)(ws + L.wt3);
-  v.sc = (float*)(ws + L.sc);
-  v.cmax = (u32*)(v.sc + x3_sc_cmax(L.dc));
-  v.two_s = v.sc + x3_sc_two_s(L.dc);
-  v.OG = (float*)(ws + L.o);
-  v.RS = (float*)(ws + L.rs);
-  v.SQ = (double*)(ws + L.sq);
-  if (sel_at) {
-    v.hist = (u64*)(ws + hist_at);
-    v.sel = (SelState*)(ws + sel_at);
-  }
-  return v;
-}
-
-// The layout of stein_svgd_phi_stream_ksd: StreamLayout as it is, with RD (the j ranges' partial rd, [jsplit][n] floats) and
-// the S / S_diag block partials ([2][sq_blocks] doubles) appended behind its end.  No offset of the plain layout moves:
-// a buffer of this size serves the plain step and the median call too.
-struct StreamKsdLayout {
-  StreamLayout L;
-  size_t rd, kpart, total;
-};
-
-static int stream_ksd_make_layout(int64_t n, int64_t d, StreamKsdLayout* K) {
-  if (int rc = stream_make_layout(n, d, &K->L)) return rc;
-  K->rd = K->L.total;
-  K->kpart = K->rd + align_up((size_t)K->L.jsplit * n * 4, 256);
-  K->total = K->kpart + align_up((size_t)2 * K->L.sq_blocks * 8, 256);
-  return STEIN_OK;
-}
 
 extern "C" int stein_debug_stream_jsplit(int jsplit) {
   if (jsplit < 0) return fail(STEIN_E_BADARG, "jsplit < 0");
   g_stream_jsplit = jsplit;
   return STEIN_OK;
 }
-int stein_stream_jsplit_hook(void) { return g_stream_jsplit; }   // (stein_imq.hip's plan honours the same hook)
+int stein_stream_jsplit_hook(void) { return g_stream_jsplit; }   // (stream_make_layout reads it in either step's file)
 
 extern "C" int stein_stream_workspace_bytes(int64_t n, int64_t d, int dtype, int flags, size_t* out_bytes) {
-  if (!out_bytes) return fail(STEIN_E_BADARG, "out_bytes is NULL");
-  int rc = stream_check_shape(n, d, dtype, flags);
-  if (rc) return rc;
-  StreamLayout L;
-  if ((rc = stream_make_layout(n, d, &L))) return rc;
-  *out_bytes = L.total;
-  return STEIN_OK;
+  return stream_workspace_bytes(STREAM_RBF, false, n, d, dtype, flags, out_bytes);
+}
+
+extern "C" int stein_stream_ksd_workspace_bytes(int64_t n, int64_t d, int dtype, int flags, size_t* out_bytes) {
+  return stream_workspace_bytes(STREAM_RBF, true, n, d, dtype, flags, out_bytes);
 }
 
 extern "C" int stein_stream_plan(int64_t n, int64_t d, int* row_tiles, int* col_groups, int* jsplit) {
-  if (!row_tiles || !col_groups || !jsplit) return fail(STEIN_E_BADARG, "NULL output");
-  int rc = stream_check_shape(n, d, STEIN_F32, 0);
-  if (rc) return rc;
-  StreamLayout L;
-  if ((rc = stream_make_layout(n, d, &L))) return rc;
-  *row_tiles = (int)L.row_tiles;
-  *col_groups = (int)L.col_groups;
-  *jsplit = (int)L.jsplit;
-  return STEIN_OK;
+  return stream_plan(STREAM_RBF, n, d, row_tiles, col_groups, jsplit);
 }
 
 // The launches in front of the contraction, the same for the plain step and the one with the statistic:
@@ -599,77 +341,44 @@ static int stream_operands(const StepViews& v, const void* theta, const void* sc
 extern "C" int stein_svgd_phi_stream(const void* theta, const void* score, int64_t n, int64_t d, int dtype,
                                      const float* h2_in, float* phi, double* sqnorm_out, void* workspace, size_t ws_bytes,
                                      int flags, void* stream) {
-  if (!theta || !score || !h2_in || !phi || !sqnorm_out || !workspace) return fail(STEIN_E_BADARG, "NULL pointer");
-  if ((uintptr_t)workspace & 15) return fail(STEIN_E_BADARG, "the workspace must be 16-byte aligned");   // (16-byte loads of its sections)
-  int rc = stream_check_shape(n, d, dtype, flags);
+  StreamCall c;
+  int rc = stream_begin(STREAM_RBF, false, theta, score, n, d, dtype, h2_in, phi, sqnorm_out, workspace, ws_bytes, flags, stream, &c);
   if (rc) return rc;
-  StreamLayout L;
-  if ((rc = stream_make_layout(n, d, &L))) return rc;
-  if (ws_bytes < L.total) return fail(STEIN_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L.total);
-  if ((rc = stein_take_device_error())) return rc;   // a kernel of an earlier call on this device gave up: say so now
-  hipStream_t s = (hipStream_t)stream;
-  const StepViews v = stream_views(L, workspace);
-  if ((rc = stream_operands(v, theta, score, n, d, dtype, h2_in, s))) return rc;
+  const StreamLayout& L = c.L;
+  const StepViews& v = c.v;
+  if ((rc = stream_operands(v, theta, score, n, d, dtype, h2_in, c.s))) return rc;
   // 4. the streaming contraction
-  const long nblk = (long)(L.row_tiles * L.col_groups * L.jsplit);
-  hipLaunchKernelGGL(k_phi_stream, dim3((unsigned)nblk), dim3(ST_THREADS), 0, s, v.T3, (int)(L.dk / 32), v.Gt3,
-                     (long)(L.nk / 32), v.r, v.sc, (int)L.dc, h2_in, v.OG, v.RS, (int)n, (int)d, (int)L.row_tiles,
-                     (int)L.col_groups, (int)L.cblocks, (int)L.row_tiles, (int)L.jtiles_per);
+  hipLaunchKernelGGL(k_phi_stream, dim3(c.nblk), dim3(ST_THREADS), 0, c.s, v.T3, (int)(L.dk / 32), v.Gt3, (long)(L.nk / 32),
+                     v.r, v.sc, (int)L.dc, h2_in, v.OG, v.RS, (int)n, (int)d, (int)L.row_tiles, (int)L.col_units,
+                     (int)L.cblocks, (int)L.row_tiles, (int)L.jtiles_per);
   LAUNCH_CHECK("k_phi_stream");
-  // 5. finish
-  const int vec = d % 4 == 0 && (((uintptr_t)theta | (uintptr_t)phi) & 15) == 0;
-  hipLaunchKernelGGL(k_stream_finish, dim3((unsigned)L.sq_blocks), dim3(256), 0, s, v.OG, v.RS, (const float*)theta, h2_in, phi,
-                     v.SQ, (int)n, (int)d, (int)L.jsplit, vec);
+  // 5. finish: phi, the |phi|^2 block partials, their sum in a fixed order
+  hipLaunchKernelGGL(k_stream_finish, dim3((unsigned)L.sq_blocks), dim3(256), 0, c.s, v.OG, v.RS, (const float*)theta, h2_in,
+                     phi, v.SQ, (int)n, (int)d, (int)L.jsplit, c.vec);
   LAUNCH_CHECK("k_stream_finish");
-  hipLaunchKernelGGL(k_stream_sqsum, dim3(1), dim3(256), 0, s, v.SQ, (int)L.sq_blocks, sqnorm_out);
-  LAUNCH_CHECK("k_stream_sqsum");
-  return STEIN_OK;
+  return stream_sum(c, sqnorm_out);
 }
 
 // ---- the streaming step with the Stein discrepancy sums ---------------------------------------------------------------
-extern "C" int stein_stream_ksd_workspace_bytes(int64_t n, int64_t d, int dtype, int flags, size_t* out_bytes) {
-  if (!out_bytes) return fail(STEIN_E_BADARG, "out_bytes is NULL");
-  int rc = stream_check_shape(n, d, dtype, flags);
-  if (rc) return rc;
-  StreamKsdLayout K;
-  if ((rc = stream_ksd_make_layout(n, d, &K))) return rc;
-  *out_bytes = K.total;
-  return STEIN_OK;
-}
-
 extern "C" int stein_svgd_phi_stream_ksd(const void* theta, const void* score, int64_t n, int64_t d, int dtype,
                                          const float* h2_in, float* phi, double* sums_out, void* workspace, size_t ws_bytes,
                                          int flags, void* stream) {
-  if (!theta || !score || !h2_in || !sums_out || !workspace) return fail(STEIN_E_BADARG, "NULL pointer");   // (phi may be)
-  if ((uintptr_t)workspace & 15) return fail(STEIN_E_BADARG, "the workspace must be 16-byte aligned");
-  int rc = stream_check_shape(n, d, dtype, flags);
+  StreamCall c;
+  int rc = stream_begin(STREAM_RBF, true, theta, score, n, d, dtype, h2_in, phi, sums_out, workspace, ws_bytes, flags, stream, &c);
   if (rc) return rc;
-  StreamKsdLayout K;
-  if ((rc = stream_ksd_make_layout(n, d, &K))) return rc;
-  const StreamLayout& L = K.L;
-  if (ws_bytes < K.total) return fail(STEIN_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, K.total);
-  if ((rc = stein_take_device_error())) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const StepViews v = stream_views(L, workspace);
-  float* RD = (float*)((char*)workspace + K.rd);
-  double* KP = (double*)((char*)workspace + K.kpart);
-  if ((rc = stream_operands(v, theta, score, n, d, dtype, h2_in, s))) return rc;
+  const StreamLayout& L = c.L;
+  const StepViews& v = c.v;
+  if ((rc = stream_operands(v, theta, score, n, d, dtype, h2_in, c.s))) return rc;
   // 4. the streaming contraction, with the second row sum
-  const long nblk = (long)(L.row_tiles * L.col_groups * L.jsplit);
-  hipLaunchKernelGGL(k_phi_stream_ksd, dim3((unsigned)nblk), dim3(ST_THREADS), 0, s, v.T3, (int)(L.dk / 32), v.Gt3,
-                     (long)(L.nk / 32), v.r, v.sc, (int)L.dc, h2_in, v.OG, v.RS, RD, (int)n, (int)d, (int)L.row_tiles,
-                     (int)L.col_groups, (int)L.cblocks, (int)L.row_tiles, (int)L.jtiles_per);
+  hipLaunchKernelGGL(k_phi_stream_ksd, dim3(c.nblk), dim3(ST_THREADS), 0, c.s, v.T3, (int)(L.dk / 32), v.Gt3,
+                     (long)(L.nk / 32), v.r, v.sc, (int)L.dc, h2_in, v.OG, v.RS, c.RD, (int)n, (int)d, (int)L.row_tiles,
+                     (int)L.col_units, (int)L.cblocks, (int)L.row_tiles, (int)L.jtiles_per);
   LAUNCH_CHECK("k_phi_stream_ksd");
-  // 5. finish: phi (unless NULL), the three sets of block partials, their sums in a fixed order.  The 16-byte path is chosen
-  // as in the plain step (a NULL phi counts as aligned), so that |phi|^2 is summed in the plain step's order; the score's
-  // alignment only decides how its rows are loaded on that path (bit 1)
-  const int vec = (d % 4 == 0 && (((uintptr_t)theta | (uintptr_t)phi) & 15) == 0 ? 1 : 0) | (((uintptr_t)score & 15) == 0 ? 2 : 0);
-  hipLaunchKernelGGL(k_stream_finish_ksd, dim3((unsigned)L.sq_blocks), dim3(256), 0, s, v.OG, v.RS, RD, (const float*)theta,
-                     (const float*)score, h2_in, phi, v.SQ, KP, (int)n, (int)d, (int)L.jsplit, vec);
+  // 5. finish: phi (unless NULL), the three sets of block partials, their sums in a fixed order
+  hipLaunchKernelGGL(k_stream_finish_ksd, dim3((unsigned)L.sq_blocks), dim3(256), 0, c.s, v.OG, v.RS, c.RD, (const float*)theta,
+                     (const float*)score, h2_in, phi, v.SQ, c.KP, (int)n, (int)d, (int)L.jsplit, c.vec);
   LAUNCH_CHECK("k_stream_finish_ksd");
-  hipLaunchKernelGGL(k_stream_sqsum3, dim3(3), dim3(256), 0, s, v.SQ, KP, (int)L.sq_blocks, sums_out);
-  LAUNCH_CHECK("k_stream_sqsum3");
-  return STEIN_OK;
+  return stream_sum(c, sums_out);
 }
 
 // ---- the streaming median -------------------------------------------------------------------------------------------
@@ -692,11 +401,11 @@ struct StreamMedianLayout {
 };
 
 static int stream_median_make_layout(int64_t n, int64_t d, int dtype, int flags, StreamMedianLayout* M) {
-  int rc = stream_check_shape(n, d, dtype, flags);
+  int rc = stream_check_shape(STREAM_RBF, n, d, dtype, flags);
   if (rc) return rc;
   if (n < 2) return fail(STEIN_E_SHAPE, "n = %lld: the median-heuristic bandwidth divides by ln n; need n >= 2", (long long)n);
-  if ((rc = stream_make_layout(n, d, &M->L))) return rc;
-  M->hist = M->L.wt3;
+  if ((rc = stream_make_layout(STREAM_RBF, n, d, &M->L))) return rc;
+  M->hist = M->L.planes[0];
   M->sel = M->hist + align_up(SH_HIST_BYTES, 256);
   M->total = M->sel + 256;
   const int64_t nt = M->L.row_tiles;
