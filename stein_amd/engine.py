@@ -16,12 +16,16 @@ Rank p owns rows [p*n/P, (p+1)*n/P) of theta / score / phi / optimizer state and
 never sees more than its own [n/P, n] block of the distance matrix; K and D never
 cross a link.  Mirrors the single call at
 stein/samplers/abstract_stein_sampler.py:103-105 (K, dK = kernel_and_grad; phi).
+
+SvgdEngine here is the stored-D engine; the streaming step's is stream_engine.StreamEngine, which SvgdEngine(h2=...) yields.
 """
 import ctypes
+import functools
 
 import torch
 
 from . import _lib
+from ._checks import check_engine_switches, ksd_statistic
 
 
 def _ptr(t):
@@ -79,28 +83,16 @@ class HipStages:
         _lib.call_on(T.device, "stein_svgd_phi", _ptr(T), _ptr(G), n, d, 0, n, _dt(T), _ptr(phi), _ptr(h2), _ptr(sqnorm),
                   _ptr(K), _ptr(dK), _ptr(ws), ws.numel(), flags, _stream(T))
 
-    def svgd_phi_stream(self, T, G, n, d, h2, phi, sqnorm, ws):
-        """the streaming step at the bandwidth^2 held by the 1-element device tensor h2 (include/steinhip.h)"""
-        _lib.call_on(T.device, "stein_svgd_phi_stream", _ptr(T), _ptr(G), n, d, _dt(T), _ptr(h2), _ptr(phi), _ptr(sqnorm),
-                     _ptr(ws), ws.numel(), 0, _stream(T))
+    def _stream_step(self, symbol, T, G, n, d, h2, phi, out, ws):
+        """The streaming step at the bandwidth^2 in the 1-element device tensor h2, under four C names (include/steinhip.h).
+        out: the float64 device tensor sqnorm[1]; the _ksd forms: sums[3] = |phi|^2, S, S_diag, and phi may be None."""
+        _lib.call_on(T.device, symbol, _ptr(T), _ptr(G), n, d, _dt(T), _ptr(h2), _ptr(phi), _ptr(out), _ptr(ws), ws.numel(), 0,
+                     _stream(T))
 
-    def svgd_phi_stream_ksd(self, T, G, n, d, h2, phi, sums, ws):
-        """the streaming step and, in the 3-element float64 device tensor sums, |phi|^2 and the Stein discrepancy sums S and
-        S_diag at that bandwidth; phi may be None: the sums alone (stein_svgd_phi_stream_ksd, include/steinhip.h)"""
-        _lib.call_on(T.device, "stein_svgd_phi_stream_ksd", _ptr(T), _ptr(G), n, d, _dt(T), _ptr(h2), _ptr(phi), _ptr(sums),
-                     _ptr(ws), ws.numel(), 0, _stream(T))
-
-    def svgd_phi_imq(self, T, G, n, d, h2, phi, sqnorm, ws):
-        """the streaming step under the inverse multiquadric kernel at the bandwidth^2 held by the 1-element device tensor
-        h2 (stein_svgd_phi_imq, include/steinhip.h)"""
-        _lib.call_on(T.device, "stein_svgd_phi_imq", _ptr(T), _ptr(G), n, d, _dt(T), _ptr(h2), _ptr(phi), _ptr(sqnorm),
-                     _ptr(ws), ws.numel(), 0, _stream(T))
-
-    def svgd_phi_imq_ksd(self, T, G, n, d, h2, phi, sums, ws):
-        """the IMQ step and, in the 3-element float64 device tensor sums, |phi|^2 and the Stein discrepancy sums S and S_diag
-        under that kernel; phi may be None: the sums alone (stein_svgd_phi_imq_ksd, include/steinhip.h)"""
-        _lib.call_on(T.device, "stein_svgd_phi_imq_ksd", _ptr(T), _ptr(G), n, d, _dt(T), _ptr(h2), _ptr(phi), _ptr(sums),
-                     _ptr(ws), ws.numel(), 0, _stream(T))
+    svgd_phi_stream = functools.partialmethod(_stream_step, "stein_svgd_phi_stream")
+    svgd_phi_stream_ksd = functools.partialmethod(_stream_step, "stein_svgd_phi_stream_ksd")
+    svgd_phi_imq = functools.partialmethod(_stream_step, "stein_svgd_phi_imq")
+    svgd_phi_imq_ksd = functools.partialmethod(_stream_step, "stein_svgd_phi_imq_ksd")
 
     def stream_median(self, T, n, d, h2, median, ws):
         """the median-heuristic bandwidth^2 (and the median) of T's n^2 distances into the 1-element device tensors h2 and
@@ -225,51 +217,23 @@ class SvgdEngine:
               on its own RCCL communicator, the whole step one C call (stein_rank_step; 68 us of host time per step
               against ~190).  Native is opt-in until a run on two or more GPUs has passed bench.py's native-vs-torch
               cross-check: so far it has only ever seen one-rank groups, where every collective is a self-copy.
-    h2      : None (default): the bandwidth is the median heuristic's, taken from all n^2 distances in every step, and
-              nothing here changes.  Otherwise the SQUARED bandwidth is the caller's and the engine takes the streaming
-              step (stein_svgd_phi_stream): no median, no n x n distance image, a workspace of O(n d) bytes.  A positive
-              finite float is stored once in a 1-element device tensor; a 1-element float32 device tensor is used as it
-              is -- the library reads it on the device in every step, so the caller may rewrite it in place between steps
-              (an annealing schedule) or hand over another engine's `h2` (a median refreshed every k-th step and held in
-              between).  Either way `self.h2` is that tensor.  fp32 inputs on the split path, one rank; K_out, dK_out,
-              dist_matrix(), ksd, mark= and group= are refused with a ValueError.  The Stein discrepancy at the step's
-              bandwidth is asked for per call: compute_phi(theta, score, discrepancy=True), then stein_discrepancy().
-              "median": the streaming step at the median heuristic's own bandwidth, still without the n x n image: the
-              engine owns `self.h2` and `self.median` (1-element float32 device tensors) and, before the step of every
-              call whose 0-based index is a multiple of `median_every`, takes the exact median of the n^2 distances in
-              its own O(n d) workspace (stein_stream_median: the distance tiles recomputed once per radix level); h2 is
-              held in between.  refresh_bandwidth(theta) does the same on demand.  Needs n >= 2.
-    median_every : with h2="median", the step period of the median refresh: an integer >= 1 (default 1: every step).
-              Refused with a ValueError on any other engine.
-    kernel  : "rbf" (default): exp(-D / (2 h2)), everything above.  "imq": the inverse multiquadric kernel
-              (1 + D / (2 h2))^(-1/2), the heavy-tailed kernel whose Stein discrepancy detects non-convergence for d >= 3
-              (Gorham & Mackey 2017) -- the SAME bandwidth h2, by the same median heuristic.  It exists as a streaming step
-              only (stein_svgd_phi_imq / _ksd; about twice the cost of the RBF streaming step), so h2= is required
-              (h2="median" for the heuristic) and everything a streaming engine offers works as there: discrepancy=True,
-              stein_discrepancy(), stream_discrepancy_sums(), refresh_bandwidth(), median_every=.
+    h2      : None (default): the median heuristic's bandwidth, from all n^2 distances in every step: this class.  Anything
+              else yields a stream_engine.StreamEngine: see there for h2, median_every and kernel (here: the defaults only).
     """
+
+    streaming, kernel, median_every = False, "rbf", None
+
+    def __new__(cls, *args, h2=None, **kwargs):
+        if h2 is None:
+            return super().__new__(cls)
+        from .stream_engine import StreamEngine      # (no SvgdEngine: Python does not run __init__ below on it)
+        return StreamEngine(*args, h2=h2, **kwargs)
 
     def __init__(self, n, d, device="cuda", group=None, stages=None, x3=None, dtype=torch.float32, small=True,
                  window=True, force_collectives=False, comm="auto", tile_distance=False, dist_window=None, ksd=False,
-                 fold=None, h2=None, median_every=1, kernel="rbf"):
+                 fold=None, *, h2=None, median_every=1, kernel="rbf"):
         self.n, self.d = int(n), int(d)
-        if kernel not in ("rbf", "imq"):
-            raise ValueError("kernel must be \"rbf\" or \"imq\", got %r" % (kernel,))
-        if kernel == "imq" and h2 is None:
-            raise ValueError("kernel=\"imq\": the IMQ kernel exists as a streaming step only (no stored-D path); pass h2= "
-                             "(h2=\"median\" for the median heuristic's bandwidth)")
-        self.kernel = kernel
-        self.streaming = h2 is not None
-        stream_median = isinstance(h2, str) and h2 == "median"
-        if isinstance(median_every, bool) or not isinstance(median_every, int) or median_every < 1:
-            raise ValueError("median_every must be an integer >= 1, got %r" % (median_every,))
-        if median_every != 1 and not stream_median:
-            raise ValueError("median_every= is the refresh period of h2=\"median\" (the streaming step at the median "
-                             "heuristic's bandwidth); it is not supported on any other engine")
-        self.median_every = median_every if stream_median else None
-        if self.streaming:
-            self._init_stream(h2, device, group, stages, x3, dtype, ksd)
-            return
+        check_engine_switches(kernel, h2, median_every)      # (h2 is None here: refuses everything but the defaults)
         # dtype of the theta / score tensors handed to compute_phi: float32, or bfloat16 (BASELINE config 2: the
         # values are used as they are, K is rounded to bf16, one bf16 MFMA per product, fp32 accumulation)
         if dtype not in (torch.float32, torch.bfloat16):
@@ -375,131 +339,6 @@ class SvgdEngine:
                 raise RuntimeError("comm='native': " + self.comm_error)
         self.comm = "native" if self._comm is not None else ("torch" if self.sharded else None)
 
-    def _init_stream(self, h2, device, group, stages, x3, dtype, ksd):
-        """The engine of the streaming step (h2 given): what it cannot do is refused here, by name."""
-        imq = self.kernel == "imq"
-        if imq and (group is not None or dtype != torch.float32 or (x3 is not None and not x3) or ksd):
-            what = "group=" if group is not None else "bf16" if dtype != torch.float32 else \
-                "x3=False" if (x3 is not None and not x3) else "ksd=True"
-            raise ValueError("kernel=\"imq\": %s is not supported; the IMQ step is the streaming step's shape: one rank, float32 "
-                             "inputs, the split path, and the Stein discrepancy per call (compute_phi(theta, score, "
-                             "discrepancy=True), then stein_discrepancy())" % what)
-        if group is not None:
-            raise ValueError("h2=: the streaming step runs on one rank; group= is not supported with a supplied bandwidth")
-        if dtype != torch.float32:
-            raise ValueError("h2=: the streaming step takes float32 inputs; bf16 is not supported with a supplied bandwidth")
-        if x3 is not None and not x3:
-            raise ValueError("h2=: the streaming step only exists on the split path; x3=False is not supported")
-        if ksd:
-            raise ValueError("h2=: ksd=True is not supported; the streaming step computes the Stein discrepancy per call: "
-                             "compute_phi(theta, score, discrepancy=True), then stein_discrepancy()")
-        self.device = torch.device(device)
-        if self.median_every is not None:
-            if self.n < 2:
-                raise ValueError("n_particles = %d: the median-heuristic bandwidth divides by ln(n); need n >= 2" % self.n)
-            self.h2 = torch.zeros(1, dtype=torch.float32, device=self.device)     # written by the median call, on the device
-        elif isinstance(h2, torch.Tensor):
-            if h2.numel() != 1 or h2.dtype != torch.float32 or h2.device.type != self.device.type or \
-                    (self.device.index is not None and h2.device.index != self.device.index):
-                raise ValueError("h2 must be a positive finite float or a 1-element float32 tensor on %s, got %s %s on %s" %
-                                 (self.device, tuple(h2.shape), h2.dtype, h2.device))
-            self.h2 = h2       # read on the device in every step: never copied, never checked (that would synchronise)
-        else:
-            import math
-            try:
-                value = float(h2)
-            except (TypeError, ValueError):
-                raise ValueError("h2 must be a positive finite float or a 1-element float32 device tensor, got %r" % (h2,))
-            if not math.isfinite(value) or value <= 0.0:
-                raise ValueError("h2 (the squared bandwidth) must be positive and finite, got %r" % (h2,))
-            self.h2 = torch.full((1,), value, dtype=torch.float32, device=self.device)
-        if self.n < 1 or self.d < 1:
-            raise ValueError("need n >= 1 and d >= 1, got n = %d, d = %d" % (self.n, self.d))
-        self.dtype, self.x3, self.ksd, self.fold = torch.float32, True, False, False
-        self.flags = 0
-        self.stages = stages if stages is not None else HipStages()
-        if not hasattr(self.stages, "svgd_phi_imq" if imq else "svgd_phi_stream"):
-            raise ValueError("h2=: the stages have no streaming step (HipStages has)")
-        if self.median_every is not None and not hasattr(self.stages, "stream_median"):
-            raise ValueError("h2=\"median\": the stages have no streaming median (HipStages has)")
-        self.group, self.world, self.rank, self.sharded = None, 1, 0, False
-        self.n_local, self.row0 = self.n, 0
-        self.comm, self._comm, self.comm_error = None, None, None
-        self.dist_window, self.window_hit = False, None
-        self._ksd_ready = False
-        self._have_dist, self._one_kernel, self.dist_upper = False, False, False
-        if imq:
-            # (col_groups: 128-column blocks here).  The workspace serves the largest of the calls made: the median call too
-            self.row_tiles, self.col_groups, self.jsplit = _lib.imq_plan(self.n, self.d)
-            self.ws_bytes = _lib.imq_workspace_bytes(self.n, self.d)
-            if self.median_every is not None:
-                self.ws_bytes = max(self.ws_bytes, _lib.stream_median_workspace_bytes(self.n, self.d))
-            self._step_name = "svgd_phi_imq"
-        else:
-            self.row_tiles, self.col_groups, self.jsplit = _lib.stream_plan(self.n, self.d)
-            self.ws_bytes = _lib.stream_workspace_bytes(self.n, self.d)
-            self._step_name = "svgd_phi_stream"
-        dev = self.device
-        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)   # nothing in it is read before it is written
-        self.phi = torch.empty(self.n, self.d, dtype=torch.float32, device=dev)
-        self._sums = torch.zeros(3, dtype=torch.float64, device=dev)
-        self.sqnorm = self._sums[:1]
-        # what the stored-D engine has and this one does not: named, so that a stray use fails on None and not on a
-        # missing attribute (the workspace views refuse with a ValueError: _section)
-        self._offs, self.ld_dist, self.split, self.median = None, 0, 0, None
-        self._flags_host, self._flags_event = None, None
-        self._stream_calls = 0
-        if self.median_every is not None:
-            # the median call works in a prefix-compatible subset of the step's layout: one buffer serves both
-            assert _lib.stream_median_workspace_bytes(self.n, self.d) <= self.ws_bytes
-            self.median = torch.zeros(1, dtype=torch.float32, device=dev)
-
-    def _check_stream_input(self, name, t):
-        if tuple(t.shape) != (self.n, self.d) or t.dtype != torch.float32 or not t.is_contiguous():
-            raise ValueError("%s must be a contiguous torch.float32 [%d, %d] tensor, got %s %s" %
-                             (name, self.n, self.d, tuple(t.shape), t.dtype))
-
-    def _stream_ksd_workspace(self):
-        """Grow the workspace to what stein_svgd_phi_stream_ksd needs (first use).  The larger buffer serves the plain step
-        and the median call too -- the layout only appends -- and nothing in it is carried between calls."""
-        if not hasattr(self.stages, self._step_name + "_ksd"):
-            raise ValueError("discrepancy=True: the stages have no streaming step with the statistic (HipStages has)")
-        if self.kernel == "imq":
-            need = _lib.imq_ksd_workspace_bytes(self.n, self.d)
-            assert need >= _lib.imq_workspace_bytes(self.n, self.d)
-        else:
-            need = _lib.stream_ksd_workspace_bytes(self.n, self.d)
-            assert need >= _lib.stream_workspace_bytes(self.n, self.d)
-        if self.ws_bytes < need:
-            self.ws = None      # (release before allocating: at the largest shapes both would not fit)
-            self.ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            self.ws_bytes = need
-
-    def stream_discrepancy_sums(self, theta, score):
-        """The statistic alone (streaming engines): the three sums |phi|^2, S, S_diag of `theta`, `score` at this engine's
-        bandwidth into self._sums, phi not stored (the C entry with phi = NULL); stein_discrepancy() afterwards.  With
-        h2="median" the bandwidth is taken from `theta` first.  Outside compute_phi's refresh schedule."""
-        if not self.streaming:
-            raise ValueError("stream_discrepancy_sums needs a streaming engine (h2=)")
-        for name, t in (("theta", theta), ("score", score)):
-            self._check_stream_input(name, t)
-        self._stream_ksd_workspace()
-        if self.median_every is not None:
-            self.stages.stream_median(theta, self.n, self.d, self.h2, self.median, self.ws)
-        getattr(self.stages, self._step_name + "_ksd")(theta, score, self.n, self.d, self.h2, None, self._sums, self.ws)
-        self._ksd_ready = True
-        return self._sums
-
-    def refresh_bandwidth(self, theta):
-        """h2="median": take the median-heuristic bandwidth of `theta` ([n, d] float32 device tensor) now, in this engine's
-        own workspace; returns self.h2 (self.median holds the median).  Nothing syncs with the host.  The refresh
-        schedule of compute_phi (median_every) is not affected."""
-        if self.median_every is None:
-            raise ValueError("refresh_bandwidth needs an engine built with h2=\"median\"")
-        self._check_stream_input("theta", theta)
-        self.stages.stream_median(theta, self.n, self.d, self.h2, self.median, self.ws)
-        return self.h2
-
     def _make_native_comm(self):
         """Group rank 0 makes the 128-byte RCCL id, the group broadcasts it, every rank joins -- collective, and
         collective in failure too: every rank takes part in the same two torch collectives whatever happens to it, so
@@ -549,9 +388,6 @@ class SvgdEngine:
 
     # views into the workspace -------------------------------------------------------------
     def _section(self, sec, nbytes, dtype):
-        if self.streaming:
-            raise ValueError("h2=: the streaming step's workspace has no sections of the stored-D layout (row norms, distance "
-                             "image, histograms, select state, planes); use an engine without a supplied bandwidth")
         o = self._offs[sec]
         return self.ws[o:o + nbytes].view(dtype)
 
@@ -569,9 +405,6 @@ class SvgdEngine:
     def dist_matrix(self):
         """Row-major [n_local, n] copy of the distance block (de-tiled; for inspection and tests).  After a single-rank
         step on the split path only the tiles on and above the diagonal are stored; the rest is mirrored in here."""
-        if self.streaming:
-            raise ValueError("h2=: the streaming step never stores the distance matrix; dist_matrix() needs an engine "
-                             "without a supplied bandwidth")
         if not self._have_dist:
             raise RuntimeError("no distance image: this engine's fused call takes the one-kernel path (n <= 160), which "
                                "keeps D in LDS; build the engine with small=False to get one")
@@ -599,14 +432,12 @@ class SvgdEngine:
 
     @property
     def spec_section(self):
-        self._section(_lib.WS_SPEC, 0, torch.uint8)      # (refuses on a streaming engine)
         o = self._offs[_lib.WS_SPEC]
         return self.ws[o:self._offs[_lib.WS_PLANES]]
 
     @property
     def spec_table(self):
         """the rank-summed window table (int64 view), behind the slots and the entry buffer of the SPEC section"""
-        self._section(_lib.WS_SPEC, 0, torch.uint8)      # (refuses on a streaming engine)
         o = self._offs[_lib.WS_SPEC] + 8 * _lib.SPEC_TABLE_OFFSET_WORDS
         return self.ws[o:o + 8 * _lib.SPEC_TABLE_WORDS].view(torch.int64)
 
@@ -615,7 +446,6 @@ class SvgdEngine:
         """split-precision operand planes and scales (None unless x3)"""
         if not self.x3:
             return None
-        self._section(_lib.WS_PLANES, 0, torch.uint8)    # (refuses on a streaming engine)
         o = self._offs[_lib.WS_PLANES]
         return self.ws[o:self.ws_bytes]
 
@@ -707,25 +537,12 @@ class SvgdEngine:
         """KSD^2 of the particles of the last compute_phi (ksd=True): a 0-d float64 device tensor, no host sync.
         statistic "u": the U-statistic  sum_{i != j} u_ij / (n (n - 1))  (unbiased, may be slightly negative near
         convergence); "v": the V-statistic  sum_ij u_ij / n^2.  u_ij is the Stein kernel of the step's RBF kernel with the
-        step's median bandwidth (include/steinhip.h, STEIN_FLAG_KSD).
-        A streaming engine (h2=): of the last compute_phi, which must have been called with discrepancy=True, at that
-        call's bandwidth (stein_svgd_phi_stream_ksd)."""
-        if self.streaming:
-            if not self._ksd_ready:
-                raise RuntimeError("the last compute_phi did not compute the Stein discrepancy: call "
-                                   "compute_phi(theta, score, discrepancy=True) first")
-            if statistic == "u" and self.n < 2:
-                raise ValueError("n = 1: the U-statistic needs at least two particles (statistic='v' is defined)")
-        if not self.ksd and not self.streaming:
+        step's median bandwidth (include/steinhip.h, STEIN_FLAG_KSD)."""
+        if not self.ksd:
             raise RuntimeError("the engine was built without ksd=True")
         if not self._ksd_ready:
             raise RuntimeError("no step has been computed yet")
-        n = float(self.n)
-        if statistic == "v":
-            return self._sums[1] / (n * n)
-        if statistic == "u":
-            return (self._sums[1] - self._sums[2]) / (n * (n - 1.0))
-        raise ValueError("statistic must be 'u' or 'v'")
+        return ksd_statistic(self._sums[1], self._sums[2], self.n, statistic)
 
     def compute_phi(self, theta_local, score_local, K_out=None, dK_out=None, mark=None, timing=False, discrepancy=False):
         """theta_local, score_local: [n_local, d] float32 contiguous device tensors (this rank's rows).
@@ -743,33 +560,12 @@ class SvgdEngine:
         kernels costs the step ~3 us, so a loop that is itself being timed should carry as few as it can.
         With ksd=True the step also leaves the Stein discrepancy sums (stein_discrepancy()); the staged calls (mark=, or a
         sharded step with K_out) do not compute them and are refused.
-        discrepancy: streaming engines (h2=) only.  True: this call also leaves the Stein discrepancy sums at its own
-        bandwidth (stein_discrepancy() afterwards; stein_svgd_phi_stream_ksd, no K.theta and no n x n image); phi, sqnorm
-        and h2 are bit-identical to a call without it.  The workspace grows once, by the partial sums of one more row sum.
+        discrepancy: the per-call switch of StreamEngine.compute_phi; refused here.
         """
         st, n, d, nl = self.stages, self.n, self.d, self.n_local
-        if discrepancy and not self.streaming:
+        if discrepancy:
             raise ValueError("discrepancy=True is the streaming engine's (h2=) per-call switch; an engine without a supplied "
                              "bandwidth computes the Stein discrepancy in every step when built with ksd=True")
-        if self.streaming:
-            if K_out is not None or dK_out is not None:
-                raise ValueError("h2=: the streaming step forms neither K nor dK; K_out / dK_out are not supported")
-            if mark is not None or timing:
-                raise ValueError("h2=: the streaming step is one call; mark= / timing= are not supported")
-            for name, t in (("theta", theta_local), ("score", score_local)):
-                self._check_stream_input(name, t)
-            if discrepancy:
-                self._stream_ksd_workspace()
-            if self.median_every is not None:
-                if self._stream_calls % self.median_every == 0:
-                    st.stream_median(theta_local, n, d, self.h2, self.median, self.ws)
-                self._stream_calls += 1
-            if discrepancy:
-                getattr(st, self._step_name + "_ksd")(theta_local, score_local, n, d, self.h2, self.phi, self._sums, self.ws)
-            else:
-                getattr(st, self._step_name)(theta_local, score_local, n, d, self.h2, self.phi, self.sqnorm, self.ws)
-            self._ksd_ready = bool(discrepancy)
-            return self.phi
         if self.ksd and (mark is not None or (self.sharded and K_out is not None)):
             raise ValueError("ksd=True: the staged calls (mark=, or K_out on a sharded engine) do not compute the Stein "
                              "discrepancy; use the fused call / rank segments")

@@ -20,6 +20,7 @@ from abc import abstractmethod
 import numpy as np
 import torch
 
+from .._checks import bandwidth_to_h2, check_kernel_name, ksd_statistic
 from ..engine import SvgdEngine
 from ..utilities.converters import convert_array_to_dictionary, convert_dictionary_to_array
 
@@ -122,8 +123,7 @@ class AbstractSteinSampler:
         self.theta_matrix = packed.to(device=self.device, dtype=dtype).contiguous()
         self.n_params = self.theta_matrix.shape[1]
         self.kernel_dtype = kernel_dtype
-        if kernel not in ("rbf", "imq"):
-            raise ValueError("kernel must be \"rbf\" or \"imq\", got %r" % (kernel,))
+        check_kernel_name(kernel)
         if kernel == "imq" and bandwidth is None and h2 is None:
             raise ValueError("kernel=\"imq\": the IMQ kernel exists on the streaming path only; pass bandwidth= (a float h, or "
                              "\"median\" for the median heuristic) or h2=")
@@ -131,17 +131,7 @@ class AbstractSteinSampler:
         if bandwidth is not None:
             if h2 is not None:
                 raise ValueError("give bandwidth= (a float h) or h2= (a device tensor holding h^2), not both")
-            if isinstance(bandwidth, str) and bandwidth == "median":
-                h2 = "median"
-            else:
-                import math
-                try:
-                    h = float(bandwidth)
-                except (TypeError, ValueError):
-                    raise ValueError("bandwidth must be a positive finite float or \"median\", got %r" % (bandwidth,))
-                if not math.isfinite(h) or h <= 0.0:
-                    raise ValueError("bandwidth must be positive and finite, got %r" % (bandwidth,))
-                h2 = h * h
+            h2 = bandwidth_to_h2(bandwidth, "a positive finite float or \"median\"")
         if ksd_every is not None:
             if isinstance(ksd_every, bool) or not isinstance(ksd_every, int) or ksd_every < 1:
                 raise ValueError("ksd_every must be an integer >= 1 or None, got %r" % (ksd_every,))
@@ -236,14 +226,7 @@ class AbstractSteinSampler:
             if self._ksd_sums is None:
                 raise RuntimeError("no step has computed the Stein discrepancy yet (ksd_every=%d: the first "
                                    "update_particles does)" % self.ksd_every)
-            n = float(self.n_particles)
-            if statistic == "v":
-                return float((self._ksd_sums[0] / (n * n)).item())
-            if statistic == "u":
-                if self.n_particles < 2:
-                    raise ValueError("n = 1: the U-statistic needs at least two particles (statistic='v' is defined)")
-                return float(((self._ksd_sums[0] - self._ksd_sums[1]) / (n * (n - 1.0))).item())
-            raise ValueError("statistic must be 'u' or 'v'")
+            return float(ksd_statistic(self._ksd_sums[0], self._ksd_sums[1], self.n_particles, statistic).item())
         if not self.engine.ksd:
             raise RuntimeError("build the sampler with ksd=True to get the Stein discrepancy")
         if self._foreign_kernel() is not None:

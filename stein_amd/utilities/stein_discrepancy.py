@@ -1,23 +1,7 @@
 """Kernelized Stein discrepancy of any particle set, by the step's own fused call (include/steinhip.h, STEIN_FLAG_KSD)."""
 import torch
 
-
-def _stream_bandwidth(bandwidth):
-    """bandwidth= of kernelized_stein_discrepancy -> the h2 argument of a streaming engine"""
-    import math
-    if isinstance(bandwidth, str):
-        if bandwidth == "median":
-            return "median"
-        raise ValueError("bandwidth must be None, a positive finite float or \"median\", got %r" % (bandwidth,))
-    if isinstance(bandwidth, bool):
-        raise ValueError("bandwidth must be None, a positive finite float or \"median\", got %r" % (bandwidth,))
-    try:
-        h = float(bandwidth)
-    except (TypeError, ValueError):
-        raise ValueError("bandwidth must be None, a positive finite float or \"median\", got %r" % (bandwidth,))
-    if not math.isfinite(h) or h <= 0.0:
-        raise ValueError("bandwidth must be positive and finite, got %r" % (bandwidth,))
-    return h * h
+from .._checks import bandwidth_to_h2, check_kernel_name
 
 
 def kernelized_stein_discrepancy(theta, score, statistic="u", bandwidth=None, kernel="rbf"):
@@ -32,11 +16,10 @@ def kernelized_stein_discrepancy(theta, score, statistic="u", bandwidth=None, ke
     same bandwidth (stein_svgd_phi_imq_ksd with phi = NULL) -- the kernel whose discrepancy detects non-convergence for
     d >= 3.  It runs on the streaming path only: bandwidth=None then means "median"."""
     from ..engine import SvgdEngine
-    if kernel not in ("rbf", "imq"):
-        raise ValueError("kernel must be \"rbf\" or \"imq\", got %r" % (kernel,))
+    check_kernel_name(kernel)
     if kernel == "imq" and bandwidth is None:
         bandwidth = "median"
-    h2 = _stream_bandwidth(bandwidth) if bandwidth is not None else None
+    h2 = bandwidth_to_h2(bandwidth, "None, a positive finite float or \"median\"") if bandwidth is not None else None
     if h2 is not None:
         for name, t in (("theta", theta), ("score", score)):
             if isinstance(t, torch.Tensor) and t.dtype == torch.bfloat16:
