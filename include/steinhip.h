@@ -314,6 +314,40 @@ int stein_svgd_phi_imq_ksd(const void* theta, const void* score, int64_t n, int6
                            double* sums_out /* [3]: |phi|^2, S, S_diag */,
                            void* workspace, size_t ws_bytes, int flags, void* stream);
 
+/* ---- Stein thinning: the m particles that best represent all n ------------------------------------------------------
+ * Riabiz et al. 2022: greedily, m times and with replacement, pick the particle that most lowers the kernelized Stein
+ * discrepancy of the picked set.  The reference has no counterpart (a run's particles are used whole).  With the Stein
+ * kernel u_p of the chosen kernel at *h2_in (c2 = 2 h2, D = |x - y|^2, cross = (g_x - g_y).(x - y), gg = g_x.g_y):
+ *   STEIN_KERNEL_IMQ  k = (1 + D / c2)^(-1/2):  u_p = k gg + k^3 cross / c2 + d k^3 / c2 - 3 k^5 D / c2^2   (as above)
+ *   STEIN_KERNEL_RBF  k = exp(-D / c2):         u_p = k (gg + cross / h2 + d / h2 - D / h2^2)               (STEIN_FLAG_KSD's)
+ *   obj_t[j] = u_p(j, j) / 2 + sum_{i < t} u_p(x_{s_i}, x_j),   s_t = argmin_j obj_t[j], the LOWEST index on equal value,
+ *   S_t = S_{t-1} + 2 obj_t[s_t]  (t = 1 .. m; an index may repeat, so m > n is meaningful)
+ *   theta, score : [n][d] float (STEIN_F32; STEIN_BF16 / STEIN_F64 return STEIN_E_UNSUPPORTED)
+ *   h2_in        : DEVICE float[1], bandwidth^2, read on the device (take the median heuristic's with stein_stream_median)
+ *   idx_out      : DEVICE int64[m], the picks in order
+ *   ksd2_out     : DEVICE double[m] or NULL: KSD^2_V of the first t picks, S_t / t^2; idx_out is the same bits without it
+ *   flags        : must be 0 (STEIN_E_BADARG).  n >= 1, d >= 1, 1 <= m <= 2^30 (STEIN_E_SHAPE); an unknown kernel id: STEIN_E_BADARG
+ * One kernel (k_thin_step, stein_amd/csrc/stein_thin.hip), launched m + 1 times on `stream`: per pick ONE row of the n x n
+ * Stein-kernel matrix, that of an index only the device knows, from the differences x_s - x_j, g_s - g_j in fp32 and added
+ * to the objective in fp64; theta and the score are read once per pick (8 n d bytes), the matrix is never formed.  No host
+ * read, no allocation, no workgroup waits for another (the launch boundary is the barrier), no atomics: a repeated call
+ * is bit-identical, for any workspace contents.
+ * The workspace must be 16-byte aligned (STEIN_E_BADARG); it carries nothing between calls.  It depends on n alone:
+ *   stein_thin_workspace_bytes = 8 n + 2 x 1024 x 16 + 8, every term rounded up to 256 bytes
+ *   (the fp64 objective, u_p(j, j) / 2 folded in by launch 0 | two alternating sets of at most 1024 per-workgroup
+ *   (value, index) partials | the running S).
+ * Grid: min(1024, ceil(n / rows per workgroup)) workgroups of 256 threads; a row is taken by the power-of-two group of
+ * lanes that covers its 16-byte units (4-byte units where d % 4 != 0 or a base pointer is not 16-byte aligned).
+ * stein_debug_thin_grid(k) (test hook, per calling thread): k > 0 launches min(k, 1024) workgroups, 0 restores the rule;
+ * the picks do not depend on it. */
+enum { STEIN_KERNEL_RBF = 0, STEIN_KERNEL_IMQ = 1 };
+int stein_thin_workspace_bytes(int64_t n, int64_t d, int dtype, int flags, size_t* out_bytes);
+int stein_thin(const void* theta, const void* score, int64_t n, int64_t d, int dtype,
+               const float* h2_in, int kernel /* STEIN_KERNEL_RBF | STEIN_KERNEL_IMQ */, int64_t m,
+               int64_t* idx_out /* DEVICE [m] */, double* ksd2_out /* DEVICE [m], may be NULL */,
+               void* workspace, size_t ws_bytes, int flags, void* stream);
+int stein_debug_thin_grid(int blocks);   /* test hook, per calling thread; 0 = default */
+
 /* ---- staged path (tests, multi-rank: the host puts collectives between the stages) ------------ */
 
 /* r_i = sum_k theta_ik^2            abstract_kernel.py:34 */

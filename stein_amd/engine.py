@@ -100,6 +100,13 @@ class HipStages:
         _lib.call_on(T.device, "stein_stream_median", _ptr(T), n, d, _dt(T), _ptr(h2), _ptr(median), _ptr(ws), ws.numel(), 0,
                      _stream(T))
 
+    def thin(self, T, G, n, d, h2, kernel, m, idx, ksd2, ws):
+        """Stein thinning (stein_thin, include/steinhip.h): the m greedy picks of the [n, d] float32 particles T with scores
+        G at the bandwidth^2 in the 1-element device tensor h2 into the int64 device tensor idx[m]; ksd2: a float64
+        device tensor [m] for KSD^2_V after each pick, or None.  kernel: _lib.KERNEL_RBF / _lib.KERNEL_IMQ."""
+        _lib.call_on(T.device, "stein_thin", _ptr(T), _ptr(G), n, d, _dt(T), _ptr(h2), kernel, m, _ptr(idx), _ptr(ksd2),
+                     _ptr(ws), ws.numel(), 0, _stream(T))
+
     def x3_prepare(self, T, G, n, d, planes):
         """T or G may be None: only the other matrix's scales and planes are rebuilt."""
         ref = T if T is not None else G

@@ -59,6 +59,17 @@ class SteinSampler(AbstractSteinSampler):
         """One SVGD iteration on a batch (stein_sampler.py:50-71)."""
         self.update_particles(self.score_matrix(batch_feed))
 
+    def thin(self, m, batch_feed=None, bandwidth="median", kernel="imq", return_ksd=False):
+        """Stein thinning of the sampler's own particles at their current scores (score_matrix(batch_feed)): the indices,
+        an int64 device tensor [m], of the m greedy picks (stein_amd.utilities.stein_thinning, which see for bandwidth,
+        kernel and return_ksd).  `theta_matrix[idx]` is the thinned particle set.  One rank only."""
+        if self._group is not None:
+            raise ValueError("thin works on one rank only: a pick is an argmin over all n particles; gather them "
+                             "(samples_all) and call stein_amd.utilities.stein_thinning")
+        from ..utilities.stein_thinning import stein_thinning
+        return stein_thinning(self._matrix_f32().detach(), self.score_matrix(batch_feed).detach(), m, bandwidth=bandwidth,
+                              kernel=kernel, return_ksd=return_ksd)
+
     @property
     def samples(self):
         """Packed [n_local, d] particle matrix as NumPy (stein_sampler.py:73-78)."""
