@@ -348,6 +348,44 @@ int stein_thin(const void* theta, const void* score, int64_t n, int64_t d, int d
                void* workspace, size_t ws_bytes, int flags, void* stream);
 int stein_debug_thin_grid(int blocks);   /* test hook, per calling thread; 0 = default */
 
+/* ---- KSD goodness-of-fit test: the bootstrap's quadratic forms without the n x n matrix -----------------------------
+ * Chwialkowski et al. 2016, Liu et al. 2016 (Gorham & Mackey 2017 for the IMQ kernel): the V-statistic sum_ij u_p(x_i, x_j)
+ * is judged against replicates sum_ij w_bi w_bj u_p(x_i, x_j) under random weights.  The reference has no counterpart.
+ *   q_out[b] = sum_ij weights[b][i] weights[b][j] u_p(x_i, x_j),  b = 0 .. reps - 1   (u_p as in stein_thin, at *h2_in)
+ *   diag_out = sum_i u_p(x_i, x_i) = sum_i |g_i|^2 + n d / h2 (RBF) or n d / (2 h2) (IMQ), in fp64 from the rows; may be NULL
+ *   theta, score : [n][d] float (STEIN_F32; STEIN_BF16 / STEIN_F64 return STEIN_E_UNSUPPORTED)
+ *   h2_in        : DEVICE float[1], bandwidth^2, read on the device
+ *   weights      : DEVICE float[reps][n], row-major, any finite values (signs, centred multinomial counts, a row of ones
+ *                  for the statistic itself)
+ *   q_out        : DEVICE double[reps];  diag_out : DEVICE double[1] or NULL
+ *   flags        : must be 0 (STEIN_E_BADARG).  n >= 2, d >= 1, reps >= 1, n <= 2^24 (STEIN_E_SHAPE); an unknown kernel id:
+ *                  STEIN_E_BADARG
+ * The Stein-kernel matrix is formed one 128 x 128 tile at a time from three (RBF: two) Gram products on the matrix cores
+ * (fp16 hi + lo operands, fp32 accumulation), scaled by a power of two derived on the device from a bound on |u_p|, split
+ * into hi + lo fp16 and contracted with all replicates' weights at once (k_ksd_boot, stein_amd/csrc/stein_boot.hip); the
+ * weights are split at ONE power-of-two scale for the whole matrix.  No host read, no allocation, no atomics, no workgroup
+ * waits for another: a repeated call is bit-identical, for any workspace contents; negating a row of weights leaves its
+ * q_out bits unchanged (by construction: the matrix cores' sums are not sign-symmetric, so each row is contracted in the
+ * sign that makes its first nonzero entry positive), and so does its position among the rows.
+ * The workspace must be 16-byte aligned (STEIN_E_BADARG); it carries nothing between calls.  With R = n rounded up to 128,
+ * dk = d rounded up to 32, dc = d rounded up to 128, C = reps rounded up to 128 and P = reps rounded up to 32,
+ *   stein_ksd_boot_workspace_bytes = 4 R + 4 (6 dc + 4) + 6 R dk + 4 n d + 4 (6 dc + 4) + 6 R dk + 4 (6 R + 4) + 6 C R
+ *                                    + 4 R + 4 R + 8 R + 256 + 4 jsplit row_tiles P + 4 reps n,   every term rounded up to 256 bytes
+ *   (row norms | theta's scales | theta's planes | W = G - theta / h2 (RBF) | the score-side operand's scales | its planes |
+ *   the weights' scales | their planes | b_i | |m_i|^2 | |g_i|^2 (fp64) | the image's scales | the partial sums | every row of
+ *   weights times the sign of its first nonzero entry: what is contracted, so that w and -w are one operand).
+ * stein_ksd_boot_plan: the grid, row_tiles = ceil(n / 128) x col_groups = ceil(reps / 256) x jsplit ranges of 128-column
+ * j tiles, jsplit = min(row_tiles, max(1, floor(256 / (row_tiles col_groups)))) with empty tails dropped (the streaming
+ * step's rule).  stein_debug_boot_jsplit(k) (test hook, per calling thread): k > 0 asks for k ranges, 0 restores the rule;
+ * it changes the workspace size with the plan. */
+int stein_ksd_boot_workspace_bytes(int64_t n, int64_t d, int64_t reps, int dtype, int flags, size_t* out_bytes);
+int stein_ksd_boot_plan(int64_t n, int64_t d, int64_t reps, int* row_tiles, int* col_groups, int* jsplit);
+int stein_ksd_boot(const void* theta, const void* score, int64_t n, int64_t d, int dtype, const float* h2_in, int kernel,
+                   const float* weights /* [reps][n], row-major */, int64_t reps,
+                   double* q_out /* [reps] */, double* diag_out /* 1, may be NULL */,
+                   void* workspace, size_t ws_bytes, int flags, void* stream);
+int stein_debug_boot_jsplit(int jsplit);   /* test hook, per calling thread; 0 = default */
+
 /* ---- staged path (tests, multi-rank: the host puts collectives between the stages) ------------ */
 
 /* r_i = sum_k theta_ik^2            abstract_kernel.py:34 */

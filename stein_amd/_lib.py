@@ -34,7 +34,7 @@ FLAG_NO_FOLD = 1024  # ... never takes it
 FLAG_KSD = 256      # also the kernelized Stein discrepancy sums: sqnorm is double[3] = |phi|^2, S, S_diag
 GLM_LINEAR, GLM_LOGISTIC = 0, 1
 PRED_LINK, PRED_MEAN = 0, 1
-KERNEL_RBF, KERNEL_IMQ = 0, 1     # STEIN_KERNEL_* (stein_thin)
+KERNEL_RBF, KERNEL_IMQ = 0, 1     # STEIN_KERNEL_* (stein_thin, stein_ksd_boot)
 SPEC_TABLE_WORDS = 65544          # uint64 words of the rank-summed window table ...
 SPEC_TABLE_OFFSET_WORDS = 1 << 21  # ... which starts 2^21 words into the SPEC section (slots + entry buffer)
 SPEC_HIT_OFFSET, SPEC_SKIP_L0_OFFSET = 64 + 28, 64 + 52   # uint32 state words inside the SELECT section
@@ -96,6 +96,10 @@ _SIGNATURES = {
     "stein_thin_workspace_bytes": [_i64, _i64, _int, _int, _c.POINTER(_sz)],
     "stein_thin": [_vp, _vp, _i64, _i64, _int, _vp, _int, _i64, _vp, _vp, _vp, _sz, _int, _vp],
     "stein_debug_thin_grid": [_int],
+    "stein_ksd_boot_workspace_bytes": [_i64, _i64, _i64, _int, _int, _c.POINTER(_sz)],
+    "stein_ksd_boot_plan": [_i64, _i64, _i64, _c.POINTER(_int), _c.POINTER(_int), _c.POINTER(_int)],
+    "stein_ksd_boot": [_vp, _vp, _i64, _i64, _int, _vp, _int, _vp, _i64, _vp, _vp, _vp, _sz, _int, _vp],
+    "stein_debug_boot_jsplit": [_int],
     "stein_rownorms": [_vp, _i64, _i64, _int, _vp, _vp],
     "stein_distance_block": [_vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _i64, _vp, _vp, _int, _vp],
     "stein_x3_prepare": [_vp, _vp, _i64, _i64, _int, _vp, _sz, _vp],
@@ -285,6 +289,25 @@ def thin_workspace_bytes(n, d, dtype=F32, flags=0):
 def debug_thin_grid(blocks):
     """Test hook (per calling thread): workgroups of Stein thinning's launches (at most 1024); 0 restores the rule."""
     call("stein_debug_thin_grid", int(blocks))
+
+
+def ksd_boot_workspace_bytes(n, d, reps, dtype=F32, flags=0):
+    """Workspace bytes of the KSD test's quadratic forms (stein_ksd_boot): O(n d + n reps).  Host arithmetic."""
+    total = _sz(0)
+    call("stein_ksd_boot_workspace_bytes", n, d, reps, dtype, flags, ctypes.byref(total))
+    return int(total.value)
+
+
+def ksd_boot_plan(n, d, reps):
+    """-> (row_tiles, col_groups, jsplit) of stein_ksd_boot's grid.  Host arithmetic."""
+    rt, cg, js = _int(0), _int(0), _int(0)
+    call("stein_ksd_boot_plan", n, d, reps, ctypes.byref(rt), ctypes.byref(cg), ctypes.byref(js))
+    return int(rt.value), int(cg.value), int(js.value)
+
+
+def debug_boot_jsplit(jsplit):
+    """Test hook (per calling thread): j ranges stein_ksd_boot's plan asks for; 0 restores the plan's own rule."""
+    call("stein_debug_boot_jsplit", int(jsplit))
 
 
 def predict_workspace_bytes(n, batch):

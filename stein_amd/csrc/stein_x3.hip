@@ -89,14 +89,7 @@ __device__ __forceinline__ void split_pair(float x, float y, u32 (&w)[3]) {
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ u32 abs_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
 __device__ __forceinline__ u32 abs_bits(u16 v) { return ((u32)v << 16) & 0x7fffffffu; }
-__device__ __forceinline__ float pow2i(int e) { return __uint_as_float((u32)(e + 127) << 23); }   // -126 <= e <= 127
-// exponent s with  max * 2^s in [2^13, 2^14); 0 for an all-zero / subnormal / non-finite column
-__device__ __forceinline__ int scale_exp(u32 maxbits, int lim) {
-  const int E = (int)((maxbits >> 23) & 0xffu);
-  if (E == 0 || E == 255) return 0;
-  const int sft = 140 - E;
-  return sft < -lim ? -lim : (sft > lim ? lim : sft);
-}
+// (pow2i and scale_exp: stein_x3_dev.h, the bootstrap kernel scales its image with them too)
 
 // maxima -> the scales area (see the header), by one workgroup of 256 threads.  enable = 0 writes the neutral scales.
 __device__ __forceinline__ void make_scales_body(const u32* cmax, int dc, float* __restrict__ sc, int pexp, int enable,

@@ -63,6 +63,16 @@ __device__ __forceinline__ float f16_resid_hi(u32 h, float x) {
   return r;
 }
 
+// ---- power-of-two scales of the fp16 split (k_make_scales, k_split_w; the Stein-kernel image of stein_boot.hip) ---------
+__device__ __forceinline__ float pow2i(int e) { return __uint_as_float((u32)(e + 127) << 23); }   // -126 <= e <= 127
+// exponent s with  max * 2^s in [2^13, 2^14); 0 for an all-zero / subnormal / non-finite column
+__device__ __forceinline__ int scale_exp(u32 maxbits, int lim) {
+  const int E = (int)((maxbits >> 23) & 0xffu);
+  if (E == 0 || E == 255) return 0;
+  const int sft = 140 - E;
+  return sft < -lim ? -lim : (sft > lim ? lim : sft);
+}
+
 // ---- streamed loads with hand-counted waits (the full story: stein_x3.hip, in front of k_phi_x3fs) -------------------
 typedef float f32x4g __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void stream_load16(f32x4g& dst, const void* base /* wave-uniform */, u32 byte_off) {

@@ -107,6 +107,13 @@ class HipStages:
         _lib.call_on(T.device, "stein_thin", _ptr(T), _ptr(G), n, d, _dt(T), _ptr(h2), kernel, m, _ptr(idx), _ptr(ksd2),
                      _ptr(ws), ws.numel(), 0, _stream(T))
 
+    def ksd_boot(self, T, G, n, d, h2, kernel, weights, reps, q, diag, ws):
+        """The KSD test's quadratic forms (stein_ksd_boot, include/steinhip.h): q[b] = sum_ij weights[b, i] weights[b, j]
+        u_p(x_i, x_j) for the float32 device tensor weights [reps, n] into the float64 device tensor q[reps]; diag: a
+        1-element float64 device tensor for sum_i u_p(x_i, x_i), or None.  kernel: _lib.KERNEL_RBF / _lib.KERNEL_IMQ."""
+        _lib.call_on(T.device, "stein_ksd_boot", _ptr(T), _ptr(G), n, d, _dt(T), _ptr(h2), kernel, _ptr(weights), reps,
+                     _ptr(q), _ptr(diag), _ptr(ws), ws.numel(), 0, _stream(T))
+
     def x3_prepare(self, T, G, n, d, planes):
         """T or G may be None: only the other matrix's scales and planes are rebuilt."""
         ref = T if T is not None else G

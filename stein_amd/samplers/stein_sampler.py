@@ -70,6 +70,18 @@ class SteinSampler(AbstractSteinSampler):
         return stein_thinning(self._matrix_f32().detach(), self.score_matrix(batch_feed).detach(), m, bandwidth=bandwidth,
                               kernel=kernel, return_ksd=return_ksd)
 
+    def goodness_of_fit(self, batch_feed=None, **kw):
+        """The KSD goodness-of-fit test of the sampler's own particles at their current scores (score_matrix(batch_feed)):
+        (statistic, p_value) from stein_amd.utilities.stein_goodness_of_fit, which takes the keyword arguments.
+        Caveat: SVGD particles interact, and the test's level is only guaranteed for (possibly dependent) DRAWS from a
+        distribution.  For particles the p-value is a calibrated scale for the statistic -- how large it is against
+        what sign-flipped copies of the same sample give -- not a proof of convergence.  One rank only."""
+        if self._group is not None:
+            raise ValueError("goodness_of_fit works on one rank only: the statistic couples all n particles; gather "
+                             "them (samples_all) and call stein_amd.utilities.stein_goodness_of_fit")
+        from ..utilities.stein_test import stein_goodness_of_fit
+        return stein_goodness_of_fit(self._matrix_f32().detach(), self.score_matrix(batch_feed).detach(), **kw)
+
     @property
     def samples(self):
         """Packed [n_local, d] particle matrix as NumPy (stein_sampler.py:73-78)."""
