@@ -246,6 +246,27 @@ def reference(T, G, h2, row0=0, n_local=None, ranges=None, chunk=1024):
     return out
 
 
+def tiles(x):
+    """[r, c] -> the Frobenius norms of its 128 x 128 tiles, [ceil(r / 128), ceil(c / 128)] (torch, on x's device)"""
+    import torch
+    r, c = x.shape
+    rp, cp = (r + 127) // 128 * 128, (c + 127) // 128 * 128
+    full = torch.zeros(rp, cp, dtype=torch.float64, device=x.device)
+    full[:r, :c] = x
+    return full.view(rp // 128, 128, cp // 128, 128).pow(2).sum(dim=(1, 3)).sqrt()
+
+
+def assert_finite(tag, what, got):
+    """the poison check: what a call left unwritten still holds NaN, and is named by its 128 x 128 tiles"""
+    import torch
+    bad = ~torch.isfinite(got)
+    if bool(bad.any()):
+        x = bad if bad.dim() == 2 else bad.reshape(-1, 1)
+        where = (tiles(x.double()) > 0).nonzero().tolist()
+        raise AssertionError((tag, what, "%d non-finite entries in %d tiles (row tile, column block), the first %s" %
+                              (int(bad.sum()), len(where), where[:6])))
+
+
 def fold_sections(n, d, fsplit, offs, total):
     """Byte offsets (fold_ow, fold_ot, fold_rs) of the folded contraction's partial sums K.W [fsplit][n][d], K.theta [n][d]
     and rowsum(K) [fsplit][n] inside a folding workspace -- stein_make_layout's rule restated (the ABI has no call for

@@ -60,23 +60,7 @@ def _tol(c):
     return TOL_BF16 if c.form == "bf16" else TOL
 
 
-def _tiles(x):
-    """[r, c] -> the Frobenius norms of its 128 x 128 tiles, [ceil(r / 128), ceil(c / 128)]"""
-    r, c = x.shape
-    rp, cp = (r + 127) // 128 * 128, (c + 127) // 128 * 128
-    full = torch.zeros(rp, cp, dtype=torch.float64, device=x.device)
-    full[:r, :c] = x
-    return full.view(rp // 128, 128, cp // 128, 128).pow(2).sum(dim=(1, 3)).sqrt()
-
-
-def _assert_finite(tag, what, got):
-    """the poison check: what a call left unwritten still holds NaN, and is named by its 128 x 128 tiles"""
-    bad = ~torch.isfinite(got)
-    if bool(bad.any()):
-        x = bad if bad.dim() == 2 else bad.reshape(-1, 1)
-        tiles = (_tiles(x.double()) > 0).nonzero().tolist()
-        raise AssertionError((tag, what, "%d non-finite entries in %d tiles (row tile, column block), the first %s" %
-                              (int(bad.sum()), len(tiles), tiles[:6])))
+_tiles, _assert_finite = cc.tiles, cc.assert_finite      # (shared with test_gpu_stream_matrix.py)
 
 
 def _check_matrix(c, tag, what, got, ref, tol, elementwise=True):
