@@ -514,11 +514,12 @@ __global__ __launch_bounds__(NTHREADS, 3) void k_distance_x3(const u16* __restri
 constexpr int FS_THREADS = 768;
 
 // ---- streamed loads with hand-counted waits ---------------------------------------------------------------------
-// The contraction's two roles each keep global loads in flight ACROSS loop iterations (D tiles four k tiles ahead, V
-// fragments one k tile ahead).  hipcc counts its own loads' s_waitcnt conservatively across a loop back-edge: in front
-// of the first use of a tile it emitted vmcnt(3) ... vmcnt(0), which also waits for the loads issued a moment earlier
-// for LATER tiles -- every k tile then paid a full memory latency and the "prefetch" was one tile deep at best (round-2
-// finding: the producers needed 1900 cycles per k tile for 500 cycles of work, the matrix waves idled 40 % of the time).
+// The contraction's two roles each keep global loads in flight ACROSS loop iterations (D tiles four k tiles ahead -- two on
+// the folded path, see PD --, V fragments one k tile ahead).  hipcc counts its own loads' s_waitcnt conservatively across
+// a loop back-edge: in front of the first use of a tile it emitted vmcnt(3) ... vmcnt(0), which also waits for the loads
+// issued a moment earlier for LATER tiles -- every k tile then paid a full memory latency and the "prefetch" was one tile
+// deep at best (round-2 finding: the producers needed 1900 cycles per k tile for 500 cycles of work, the matrix waves
+// idled 40 % of the time).
 // So these loads are inline asm, which the compiler neither counts nor waits for (cdna_hip_programming.md 5.7), and the
 // waits are written by hand: stream_wait<N> lets the N youngest loads of the wave stay in flight; the scheduling fence
 // behind it keeps every use of the loaded registers below the wait (an MFMA is not a memory operation: "memory" alone
@@ -605,6 +606,10 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
   // FOLD: the halved grid is split over j to fill the chip (C3: two ranges of 64 stages), and every range is walked this way:
   // stage v of a range is its block v ^ (tile_m & ~(group - 1) & (nstage - 1)).  The two reads of a stored tile, by row tiles
   // I and J in whichever ranges, are then (I ^ J) & (group - 1) < group stages apart as before, all ranges running at once.
+  // (Folded C3 has wpm = 1, group = 32: the two reads lie 10.7 stages apart on average.  Groups of 16 and of 8 row tiles
+  // halve and quarter that and were measured equal and 1 % slower: the launch's 1.13 GB from beyond the L2 are every D
+  // tile twice plus V, whatever the order, and the launch does not wait for where they come from;
+  // profiles/contract_feed_ab.txt, 1. and 3.)
   const int group = wpm <= 32 ? 32 / wpm : 1;
   const bool permute = upper != 0 && (FOLD || (jbeg == 0 && jend == n && nstage == tiles_m)) && (wpm & (wpm - 1)) == 0 &&
                        wpm <= 4 && nstage * FS_KT == ntile && (nstage & (nstage - 1)) == 0 && nstage >= 2 * group;
@@ -635,8 +640,13 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
 #pragma unroll
     for (int p = 0; p < PR; ++p) rs[p] = 0.f;
     // PD register sets (tile index mod PD picks the set): the loads of tile t + PD are issued as soon as tile t has been
-    // turned into LDS data.  D streams from HBM (never re-used), so the loads need several tiles of lead
-    constexpr int PD = FS_KT;   // 4; FS_KT % PD == 0 keeps the set index static
+    // turned into LDS data.  D streams from beyond the L2, so the loads need more than one tile of lead -- and no more than
+    // the CU can hold in flight.  FOLD: 2.  A folded workgroup is the only reader of its D tiles on its XCD (unfolded,
+    // `rot` lets the workgroups of a row tile find every other tile in the L2), so all 16 KB per k tile come from beyond
+    // the L2; four tiles ahead that is 64 KB per CU, and the launch was 17 us (4.7 %) SLOWER at C3 than two tiles ahead
+    // (one tile ahead: 1 % slower than four; profiles/contract_feed_ab.txt, 3.).  Unfolded the lead stays at 4: 8192 x 128
+    // measured 1 % slower with 2.
+    constexpr int PD = FOLD ? 2 : FS_KT;   // FS_KT % PD == 0 keeps the set index static
     f32x4g rd[PD][PR];
     u32 doff[PR];
     const float cexp = -1.44269504088896341f / (2.f * *h2p);   // exp(-D/(2 h2)) = exp2(cexp * D)
@@ -666,19 +676,25 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
       for (int p = 0; p < PR; ++p) stream_load16(rd[p], tile, tr ? doff_tr[p] : doff[p] * 4u);
     };
     // before tile number v (in visit order) of the ntile is turned into LDS data: its PR loads must have landed, the loads
-    // of the up to three later tiles already requested (PR each) stay in flight
+    // of the up to PD - 1 later tiles already requested (PR each) stay in flight
     auto wait_loads = [&](int v, f32x4g (&rd)[PR]) {
       const int later = ntile - v - 1;
       (void)rd;
       // (nested, the loosest wait first and unconditional: every path from a request to its use passes a wait, which is
       // what stein_amd/csrc/isa_check.py verifies on the assembly)
-      stream_wait<3 * PR>();
-      if (later < 3) {
-        stream_wait<2 * PR>();
-        if (later < 2) {
-          stream_wait<PR>();
-          if (later < 1) stream_wait<0>();
+      if constexpr (PD == 4) {
+        stream_wait<3 * PR>();
+        if (later < 3) {
+          stream_wait<2 * PR>();
+          if (later < 2) {
+            stream_wait<PR>();
+            if (later < 1) stream_wait<0>();
+          }
         }
+      } else {
+        static_assert(PD == 2 || PD == 4, "wait_loads is written out for these two leads");
+        stream_wait<PR>();
+        if (later < 1) stream_wait<0>();
       }
     };
     // registers of tile j0 -> LDS stage `buf`
@@ -794,17 +810,19 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
       }
     };
     auto jt = [&](int tile) { return jbeg + tile * BK; };   // tile index -> first column (jbeg % 32 == 0)
-    // A pipeline stage holds FS_KT consecutive k tiles, so the workgroup synchronises once per FS_KT tiles.  Tile
-    // parity picks the register set (X even, Y odd); a tile's loads are issued two tiles ahead, right after the set is free.
+    // A pipeline stage holds FS_KT consecutive k tiles, so the workgroup synchronises once per FS_KT tiles.  The tile's
+    // position mod PD picks the register set; a tile's loads are issued PD tiles ahead, right after the set is free.
 #pragma unroll
     for (int u = 0; u < PD; ++u)
       if (tile_at(0, u) < ntile) request(jt(tile_at(0, u)), stage_of(0) < ntr, rd[u]);
-    // stage st: turn the registers of its tiles into LDS data (slot u <- tile_at(st, u)), then request the next stage's
+    // stage st: turn the registers of its tiles into LDS data (slot u <- tile_at(st, u)); behind each, request the tile PD
+    // positions on (slot u + PD: of the next stage from u + PD >= FS_KT on, with that stage's source)
     auto produce_stage = [&](int st, unsigned char* buf) {
-      const bool tr_now = stage_of(st) < ntr, tr_next = stage_of(st + 1) < ntr;   // workgroup-uniform
+      const bool tr_now = stage_of(st) < ntr;   // workgroup-uniform
 #pragma unroll
       for (int u = 0; u < FS_KT; ++u) {
-        const int tile_u = tile_at(st, u), next_u = tile_at(st + 1, u);
+        const int tile_u = tile_at(st, u), next_u = tile_at(st, u + PD);
+        const bool tr_next = stage_of(st + (u + PD) / FS_KT) < ntr;
         if (tile_u < ntile) {
           wait_loads(st * FS_KT + u, rd[u % PD]);   // (tiles are requested in visit order: position = st * FS_KT + u)
           if (tr_now) produce_tr(buf + u * FS_KTB, rd[u % PD]);
