@@ -386,6 +386,68 @@ int stein_ksd_boot(const void* theta, const void* score, int64_t n, int64_t d, i
                    void* workspace, size_t ws_bytes, int flags, void* stream);
 int stein_debug_boot_jsplit(int jsplit);   /* test hook, per calling thread; 0 = default */
 
+/* ---- Stein-kernel products: V U without the n x n matrix ------------------------------------------------------------
+ * What stein_ksd_boot forms per workgroup and reduces away, stored: the products Stein importance weights (below) and
+ * control variates are built from.  The reference has no counterpart.
+ *   out[b][i] = sum_j u_p(x_i, x_j) V[b][j],  b = 0 .. reps - 1, i = 0 .. n - 1   (u_p as in stein_thin, at *h2_in)
+ *   theta, score, h2_in, kernel : as stein_ksd_boot
+ *   V   : DEVICE float[reps][n], row-major, any finite values;  out : DEVICE float[reps][n]
+ *   flags must be 0 (STEIN_E_BADARG).  n >= 2, d >= 1, reps >= 1, n <= 2^24 (STEIN_E_SHAPE); fp32 only (STEIN_E_UNSUPPORTED)
+ * The kernel is k_ksd_boot's j loop with a second tail (k_ksd_boot<Kern, true>, stein_amd/csrc/stein_boot.hip): the 128 x 32
+ * accumulators of a wave are not multiplied by w_bi and reduced over the rows but stored as this j range's partial of
+ * T = U V^T, one float per (j range, replicate, row < n), four consecutive rows of a lane as one 16-byte store;
+ * k_boot_product_sum adds the ranges in range order in fp64, applies the out-scale and writes floats.  The plan and its test
+ * hook are the bootstrap's (stein_ksd_boot_plan, stein_debug_boot_jsplit).  Every slot is written by exactly one wave, no
+ * atomics: a repeated call is bit-identical, for any workspace contents; rows >= n and replicates >= reps are never written.
+ * V is split as given: the sign canonicalisation of the quadratic forms is not needed here and NOT promised -- out(-V) may
+ * differ from -out(V) in the last bit of a partial.
+ * The workspace must be 16-byte aligned (STEIN_E_BADARG); it carries nothing between calls.  With R, dk, dc, C, P as above it
+ * is the bootstrap's layout with the partial block holding T's partials and without the canonical weights:
+ *   stein_ksd_matmul_workspace_bytes = 4 R + 4 (6 dc + 4) + 6 R dk + 4 n d + 4 (6 dc + 4) + 6 R dk + 4 (6 R + 4) + 6 C R
+ *                                      + 4 R + 4 R + 8 R + 256 + 4 jsplit P R,   every term rounded up to 256 bytes. */
+int stein_ksd_matmul_workspace_bytes(int64_t n, int64_t d, int64_t reps, int dtype, int flags, size_t* out_bytes);
+int stein_ksd_matmul(const void* theta, const void* score, int64_t n, int64_t d, int dtype,
+                     const float* h2_in, int kernel,
+                     const float* V /* DEVICE [reps][n] */, int64_t reps,
+                     float* out /* DEVICE [reps][n] */,
+                     void* workspace, size_t ws_bytes, int flags, void* stream);
+
+/* ---- Stein importance weights ----------------------------------------------------------------------------------------
+ * Black-box importance sampling (Liu & Lee 2017): the weights w on the simplex that minimise w^T U w, the KSD^2 of the
+ * weighted sample; sum_i w_i f(x_i) then corrects a biased or unconverged sample (SVGD particles stopped early, MCMC
+ * output, a warm start from another posterior) while keeping every particle.  The reference has no counterpart.
+ * Frank-Wolfe on the simplex with an exact line search, from w = 1 / n and g = U w; for t = 1 .. iters
+ *   f = sum_j w_j g_j,  s = argmin_j g_j (lowest index on equal value),  num = f - g_s,  den = f - 2 g_s + u_p(s, s)
+ *   gamma = 0 if num <= 0 or den <= 0, else min(1, num / den);   w <- (1 - gamma) w + gamma e_s,  g <- (1 - gamma) g + gamma U[s, :]
+ * f never increases, and f(w) - min over the simplex <= 2 (w^T g - min g): the certificate in stats_out[1].
+ *   w_out     : DEVICE double[n], >= 0, sum 1
+ *   stats_out : DEVICE double[3]: f(w) = w^T U w, gap = w^T g - min_i g_i (g = U w), f(uniform)
+ *   idx_out   : DEVICE int64[iters] or NULL: the vertex s of every step;  gamma_out : DEVICE double[iters] or NULL: its length
+ *   iters     : 0 .. 2^30 (STEIN_E_SHAPE); 0 returns the uniform weights, their gap and f(uniform) = f(w)
+ *   flags must be 0 (STEIN_E_BADARG).  n >= 2, d >= 1, n <= 2^24 (STEIN_E_SHAPE); fp32 only (STEIN_E_UNSUPPORTED)
+ * Launches (stein_amd/csrc/stein_weights.hip), no host read, no allocation: stein_ksd_matmul of the float row 1 / n -> g;
+ * k_weights_step iters + 1 times -- per step ONE row of U, that of an index only the device knows, in fp32 from the
+ * differences as stein_thin evaluates it (the device code is shared), g and w updated in fp64, u_p(s, s) summed in fp64;
+ * then stein_ksd_matmul of the final weights (as floats) and a one-workgroup finish that takes stats_out[0 .. 1] from that
+ * FRESH product: the certificate does not inherit the iteration's drift.  The launch boundary is the only barrier between
+ * workgroups, no atomics; the per-workgroup partials (min g, index, sum w_j g_j) belong to min(1024, row batches) virtual
+ * workgroups fixed by n and d, so a repeated call is bit-identical, for any workspace contents and any grid.
+ * The workspace must be 16-byte aligned (STEIN_E_BADARG); it carries nothing between calls and is O(n d):
+ *   stein_weights_workspace_bytes = stein_ksd_matmul_workspace_bytes(n, d, 1) + 8 n + 8 n + 4 n + 4 n + 2 x 1024 x 24,
+ *   every term rounded up to 256 bytes   (the products' workspace | g | w (fp64) | w as floats | U w as floats | two
+ *   alternating sets of partials); it follows stein_debug_boot_jsplit through its first term.
+ * stein_debug_weights_grid(k) (test hook, per calling thread): k > 0 launches min(k, 1024) workgroups, 0 restores one per
+ * virtual workgroup; no bit of the result depends on it. */
+int stein_weights_workspace_bytes(int64_t n, int64_t d, int dtype, int flags, size_t* out_bytes);
+int stein_weights(const void* theta, const void* score, int64_t n, int64_t d, int dtype,
+                  const float* h2_in, int kernel, int64_t iters,
+                  double* w_out     /* DEVICE [n] */,
+                  double* stats_out /* DEVICE [3]: f(w) = w^T U w, gap = w^T g - min_i g_i (g = U w), f(uniform) */,
+                  int64_t* idx_out  /* DEVICE [iters] or NULL: the vertex of every step */,
+                  double* gamma_out /* DEVICE [iters] or NULL: the step length of every step */,
+                  void* workspace, size_t ws_bytes, int flags, void* stream);
+int stein_debug_weights_grid(int blocks);   /* test hook, per calling thread; 0 = default */
+
 /* ---- staged path (tests, multi-rank: the host puts collectives between the stages) ------------ */
 
 /* r_i = sum_k theta_ik^2            abstract_kernel.py:34 */

@@ -34,7 +34,7 @@ FLAG_NO_FOLD = 1024  # ... never takes it
 FLAG_KSD = 256      # also the kernelized Stein discrepancy sums: sqnorm is double[3] = |phi|^2, S, S_diag
 GLM_LINEAR, GLM_LOGISTIC = 0, 1
 PRED_LINK, PRED_MEAN = 0, 1
-KERNEL_RBF, KERNEL_IMQ = 0, 1     # STEIN_KERNEL_* (stein_thin, stein_ksd_boot)
+KERNEL_RBF, KERNEL_IMQ = 0, 1     # STEIN_KERNEL_* (stein_thin, stein_ksd_boot, stein_ksd_matmul, stein_weights)
 SPEC_TABLE_WORDS = 65544          # uint64 words of the rank-summed window table ...
 SPEC_TABLE_OFFSET_WORDS = 1 << 21  # ... which starts 2^21 words into the SPEC section (slots + entry buffer)
 SPEC_HIT_OFFSET, SPEC_SKIP_L0_OFFSET = 64 + 28, 64 + 52   # uint32 state words inside the SELECT section
@@ -100,6 +100,11 @@ _SIGNATURES = {
     "stein_ksd_boot_plan": [_i64, _i64, _i64, _c.POINTER(_int), _c.POINTER(_int), _c.POINTER(_int)],
     "stein_ksd_boot": [_vp, _vp, _i64, _i64, _int, _vp, _int, _vp, _i64, _vp, _vp, _vp, _sz, _int, _vp],
     "stein_debug_boot_jsplit": [_int],
+    "stein_ksd_matmul_workspace_bytes": [_i64, _i64, _i64, _int, _int, _c.POINTER(_sz)],
+    "stein_ksd_matmul": [_vp, _vp, _i64, _i64, _int, _vp, _int, _vp, _i64, _vp, _vp, _sz, _int, _vp],
+    "stein_weights_workspace_bytes": [_i64, _i64, _int, _int, _c.POINTER(_sz)],
+    "stein_weights": [_vp, _vp, _i64, _i64, _int, _vp, _int, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _int, _vp],
+    "stein_debug_weights_grid": [_int],
     "stein_rownorms": [_vp, _i64, _i64, _int, _vp, _vp],
     "stein_distance_block": [_vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _i64, _vp, _vp, _int, _vp],
     "stein_x3_prepare": [_vp, _vp, _i64, _i64, _int, _vp, _sz, _vp],
@@ -308,6 +313,27 @@ def ksd_boot_plan(n, d, reps):
 def debug_boot_jsplit(jsplit):
     """Test hook (per calling thread): j ranges stein_ksd_boot's plan asks for; 0 restores the plan's own rule."""
     call("stein_debug_boot_jsplit", int(jsplit))
+
+
+def ksd_matmul_workspace_bytes(n, d, reps, dtype=F32, flags=0):
+    """Workspace bytes of the Stein-kernel products (stein_ksd_matmul): O(n d + n reps jsplit).  Host arithmetic."""
+    total = _sz(0)
+    call("stein_ksd_matmul_workspace_bytes", n, d, reps, dtype, flags, ctypes.byref(total))
+    return int(total.value)
+
+
+def weights_workspace_bytes(n, d, dtype=F32, flags=0):
+    """Workspace bytes of the Stein importance weights (stein_weights): O(n d), independent of the iteration count.  Host
+    arithmetic."""
+    total = _sz(0)
+    call("stein_weights_workspace_bytes", n, d, dtype, flags, ctypes.byref(total))
+    return int(total.value)
+
+
+def debug_weights_grid(blocks):
+    """Test hook (per calling thread): workgroups of the importance weights' step launches (at most 1024); 0 restores the
+    rule.  No bit of the result depends on it."""
+    call("stein_debug_weights_grid", int(blocks))
 
 
 def predict_workspace_bytes(n, batch):

@@ -16,6 +16,9 @@
 //   k_boot_scale        one workgroup: a bound on |u_p| -> the power-of-two scale of the image; sum_i u_p(i, i) -> diag_out
 //   k_ksd_boot<Kern>    the streaming kernel (below)
 //   k_boot_sum          adds the (j range, row tile) partials of every replicate in fixed order in fp64 -> q_out
+// stein_ksd_matmul (out = V U, the products Stein importance weights and control variates need) is the
+// same sequence without k_boot_canon, with k_ksd_boot<Kern, true> -- the same j loop, whose tail stores the accumulators as
+// this j range's partial of T instead of reducing them -- and k_boot_product_sum, which adds the ranges in fp64 -> out.
 //
 // k_ksd_boot: k_phi_stream's shape (stein_stream.hip).  A 512-thread workgroup owns 128 rows x one group of 256 weight
 // columns (replicates) x one range of 128-column j tiles; the LDS image is double-buffered, one barrier per j tile.  Per tile:
@@ -86,7 +89,8 @@ __device__ __forceinline__ void boot_gram_add(const u16* __restrict__ ta, const 
 constexpr float BOOT_CLAMP = 60000.f;   // the scaled image stays inside fp16 (65504) whatever the rounding did to the bound
 
 // st[0]: the image's in-scale 2^su; st[1]: the out-scale 2^-su / (the weights' in-scale)
-template <class Kern>
+// PRODUCT (stein_ksd_matmul): the same j loop with the other tail -- T itself is stored, `weights` is not read
+template <class Kern, bool PRODUCT>
 __global__ __launch_bounds__(ST_THREADS) void k_ksd_boot(const u16* __restrict__ T3, const u16* __restrict__ M3, int ntk,
                                                          const u16* __restrict__ Wt3, long ntj, const float* __restrict__ r,
                                                          const float* __restrict__ rowb, const float* __restrict__ sct,
@@ -181,8 +185,32 @@ __global__ __launch_bounds__(ST_THREADS) void k_ksd_boot(const u16* __restrict__
     }
   }
 
-  // ---- tail: sum_i w_bi T_ib over this tile's rows, one float per (j range, row tile, replicate)
   if (!live) return;
+  if constexpr (PRODUCT) {
+    // ---- tail: this j range's partial of T, part[z][b][row]: one float per (j range, replicate, row < n).  A lane holds four
+    // consecutive rows: one 16-byte store (the rows are padded to the tiles and the block is 256-byte aligned) unless they
+    // straddle n, where the rows < n go out one by one; rows >= n and replicates >= reps are not written
+    const size_t rows = (size_t)row_tiles * ST_ROWS;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int b = g * 128 + wcol + j * 16 + l15;
+      if (b >= reps) continue;
+      float* __restrict__ dst = part + ((size_t)z * repsp + b) * rows;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int row = i0 + i * 16 + 4 * lq;
+        if (row + 3 < n) {
+          *reinterpret_cast<f32x4*>(dst + row) = acc[i][j];
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (row + e < n) dst[row + e] = acc[i][j][e];
+        }
+      }
+    }
+    return;
+  }
+  // ---- tail: sum_i w_bi T_ib over this tile's rows, one float per (j range, row tile, replicate)
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int b = g * 128 + wcol + j * 16 + l15;
@@ -314,6 +342,18 @@ __global__ __launch_bounds__(256) void k_boot_sum(const float* __restrict__ part
   q_out[b] = s * (double)st[1];
 }
 
+// ---- stein_ksd_matmul: the j ranges' partials of T in range order in fp64, unscaled -> out [reps][n] as float ----------------
+__global__ __launch_bounds__(256) void k_boot_product_sum(const float* __restrict__ part, const float* __restrict__ st, int jsplit,
+                                                          int repsp, long rows, int n, long total, float* __restrict__ out) {
+  const double os = (double)st[1];
+  for (long at = blockIdx.x * 256L + threadIdx.x; at < total; at += gridDim.x * 256L) {
+    const long b = at / n, i = at - b * n;
+    double s = 0.0;
+    for (int z = 0; z < jsplit; ++z) s += (double)part[((size_t)z * repsp + b) * rows + i];
+    out[at] = (float)(s * os);
+  }
+}
+
 // ================================================================================================
 // host side
 // ================================================================================================
@@ -333,11 +373,11 @@ struct BootLayout {
   size_t r, sct, t3, w, scm, m3, scw, w3, rowb, rown, rowdiag, st, part, wc, total;
 };
 
-static int boot_check_shape(int64_t n, int64_t d, int64_t reps, int dtype, int flags) {
+static int boot_check_shape(int64_t n, int64_t d, int64_t reps, int dtype, int flags, const char* who = "stein_ksd_boot") {
   if (dtype == STEIN_BF16 || dtype == STEIN_F64)
-    return fail(STEIN_E_UNSUPPORTED, "stein_ksd_boot takes fp32 inputs (STEIN_F32), not bf16 or f64");
+    return fail(STEIN_E_UNSUPPORTED, "%s takes fp32 inputs (STEIN_F32), not bf16 or f64", who);
   if (dtype != STEIN_F32) return fail(STEIN_E_UNSUPPORTED, "dtype %d", dtype);
-  if (flags != 0) return fail(STEIN_E_BADARG, "stein_ksd_boot takes no flags, got 0x%x", flags);
+  if (flags != 0) return fail(STEIN_E_BADARG, "%s takes no flags, got 0x%x", who, flags);
   if (n < 2 || d < 1) return fail(STEIN_E_SHAPE, "bad shape n=%lld d=%lld: need n >= 2 and d >= 1", (long long)n, (long long)d);
   if (reps < 1) return fail(STEIN_E_SHAPE, "bad replicate count reps=%lld: need reps >= 1", (long long)reps);
   if (int rc = stein_check_size(n, d)) return rc;
@@ -346,7 +386,8 @@ static int boot_check_shape(int64_t n, int64_t d, int64_t reps, int dtype, int f
 
 // The plan: one workgroup per (row tile, group of 256 replicates, j range); the j ranges fill the resident grid by the
 // streaming step's rule (stream_make_layout) with the replicate groups in the place of its column groups.
-static int boot_make_layout(int64_t n, int64_t d, int64_t reps, BootLayout* L) {
+// product (stein_ksd_matmul): the partial block holds T itself, [jsplit][repsp][rows], and there are no canonical weights.
+static int boot_make_layout(int64_t n, int64_t d, int64_t reps, BootLayout* L, bool product = false) {
   *L = BootLayout{};
   L->row_tiles = (n + ST_ROWS - 1) / ST_ROWS;
   L->cblocks = (reps + 127) / 128;
@@ -376,8 +417,8 @@ static int boot_make_layout(int64_t n, int64_t d, int64_t reps, BootLayout* L) {
   L->rown = put((size_t)L->rows * 4);
   L->rowdiag = put((size_t)L->rows * 8);
   L->st = put(256);
-  L->part = put((size_t)L->jsplit * L->row_tiles * L->repsp * 4);
-  L->wc = put((size_t)reps * n * 4);
+  L->part = put((size_t)L->jsplit * (product ? L->rows : L->row_tiles) * L->repsp * 4);
+  L->wc = put(product ? 0 : (size_t)reps * n * 4);
   L->total = at;
   if (L->row_tiles * L->col_groups * L->jsplit > 0x7fffffffll) return fail(STEIN_E_SHAPE, "too many tiles");
   return STEIN_OK;
@@ -426,9 +467,11 @@ static int boot_split_one(const StepViews& v, const void* X, int64_t rows_in, in
   return stein_x3_split(v, X, nullptr, STEIN_F32, rows_in, cols_in, s, &only_rows);
 }
 
-template <class Kern>
+// PRODUCT: `weights` is V, contracted as given (no canonical sign), and T goes to prod_out [reps][n]; q_out, diag_out unused
+template <class Kern, bool PRODUCT = false>
 static int boot_launch(const BootLayout& L, char* ws, const float* theta, const float* score, int64_t n, int64_t d,
-                       const float* h2_in, const float* weights, int64_t reps, double* q_out, double* diag_out, hipStream_t s) {
+                       const float* h2_in, const float* weights, int64_t reps, double* q_out, double* diag_out, hipStream_t s,
+                       float* prod_out = nullptr) {
   float* r = (float*)(ws + L.r);
   float* W = (float*)(ws + L.w);
   float* rowb = (float*)(ws + L.rowb);
@@ -436,7 +479,7 @@ static int boot_launch(const BootLayout& L, char* ws, const float* theta, const 
   double* rowdiag = (double*)(ws + L.rowdiag);
   float* st = (float*)(ws + L.st);
   float* part = (float*)(ws + L.part);
-  float* Wc = (float*)(ws + L.wc);
+  const float* Wc = weights;
   int rc;
   // 1. row norms; theta's scales and planes (the score only feeds column maxima nothing here reads)
   if ((rc = stein_rownorms(theta, n, d, STEIN_F32, r, (void*)s))) return rc;
@@ -451,8 +494,12 @@ static int boot_launch(const BootLayout& L, char* ws, const float* theta, const 
   const StepViews vm = boot_split_views(ws, L.scm, L.m3, L.rows, L.dk, L.dc);
   if ((rc = boot_split_one(vm, Kern::ID == STEIN_KERNEL_RBF ? W : score, n, d, s))) return rc;
   const StepViews vw = boot_split_views(ws, L.scw, L.w3, L.repsc, L.rows, L.rows);
-  hipLaunchKernelGGL(k_boot_canon, dim3((unsigned)((reps + 3) / 4)), dim3(256), 0, s, weights, Wc, (int)n, (int)reps);
-  LAUNCH_CHECK("k_boot_canon");
+  if (!PRODUCT) {
+    float* canon = (float*)(ws + L.wc);
+    hipLaunchKernelGGL(k_boot_canon, dim3((unsigned)((reps + 3) / 4)), dim3(256), 0, s, weights, canon, (int)n, (int)reps);
+    LAUNCH_CHECK("k_boot_canon");
+    Wc = canon;
+  }
   if ((rc = boot_split_one(vw, Wc, reps, n, s))) return rc;
   // 5. the image's scale (after the weights' scale exists), the diagonal sum
   hipLaunchKernelGGL(k_boot_scale<Kern::ID>, dim3(1), dim3(256), 0, s, rown, rowb, rowdiag, h2_in, vw.sc + 4 * L.rows, st, diag_out,
@@ -460,10 +507,17 @@ static int boot_launch(const BootLayout& L, char* ws, const float* theta, const 
   LAUNCH_CHECK("k_boot_scale");
   // 6. the streaming kernel; 7. the partials in fixed order
   const unsigned nblk = (unsigned)(L.row_tiles * L.col_groups * L.jsplit);
-  hipLaunchKernelGGL(k_ksd_boot<Kern>, dim3(nblk), dim3(ST_THREADS), 0, s, vt.T3, vm.T3, (int)(L.dk / 32), vw.T3,
+  hipLaunchKernelGGL((k_ksd_boot<Kern, PRODUCT>), dim3(nblk), dim3(ST_THREADS), 0, s, vt.T3, vm.T3, (int)(L.dk / 32), vw.T3,
                      (long)(L.rows / 32), r, rowb, vt.sc, vm.sc, (int)L.dc, st, h2_in, Wc, part, (int)n, (int)d, (int)reps,
                      (int)L.repsp, (int)L.row_tiles, (int)L.col_groups, (int)L.cblocks, (int)L.row_tiles, (int)L.jtiles_per);
   LAUNCH_CHECK("k_ksd_boot");
+  if (PRODUCT) {
+    const long total = (long)reps * (long)n;
+    hipLaunchKernelGGL(k_boot_product_sum, dim3((unsigned)grid_for(total, 1 << 20)), dim3(256), 0, s, part, st,
+                       (int)L.jsplit, (int)L.repsp, (long)L.rows, (int)n, total, prod_out);
+    LAUNCH_CHECK("k_boot_product_sum");
+    return STEIN_OK;
+  }
   hipLaunchKernelGGL(k_boot_sum, dim3((unsigned)((reps + 255) / 256)), dim3(256), 0, s, part, st,
                      (int)(L.jsplit * L.row_tiles), (int)L.repsp, (int)reps, q_out);
   LAUNCH_CHECK("k_boot_sum");
@@ -488,4 +542,35 @@ extern "C" int stein_ksd_boot(const void* theta, const void* score, int64_t n, i
                                 diag_out, s);
   return boot_launch<ImqBoot>(L, (char*)workspace, (const float*)theta, (const float*)score, n, d, h2_in, weights, reps, q_out,
                               diag_out, s);
+}
+
+// ---- stein_ksd_matmul: out = V U, the same launches with the product tail --------------------------------------------------
+extern "C" int stein_ksd_matmul_workspace_bytes(int64_t n, int64_t d, int64_t reps, int dtype, int flags, size_t* out_bytes) {
+  if (!out_bytes) return fail(STEIN_E_BADARG, "out_bytes is NULL");
+  int rc = boot_check_shape(n, d, reps, dtype, flags, "stein_ksd_matmul");
+  if (rc) return rc;
+  BootLayout L;
+  if ((rc = boot_make_layout(n, d, reps, &L, true))) return rc;
+  *out_bytes = L.total;
+  return STEIN_OK;
+}
+
+extern "C" int stein_ksd_matmul(const void* theta, const void* score, int64_t n, int64_t d, int dtype, const float* h2_in,
+                                int kernel, const float* V, int64_t reps, float* out, void* workspace, size_t ws_bytes, int flags,
+                                void* stream) {
+  if (!theta || !score || !h2_in || !V || !out || !workspace) return fail(STEIN_E_BADARG, "NULL pointer");
+  if ((uintptr_t)workspace & 15) return fail(STEIN_E_BADARG, "the workspace must be 16-byte aligned");
+  int rc = boot_check_shape(n, d, reps, dtype, flags, "stein_ksd_matmul");
+  if (rc) return rc;
+  if (kernel != STEIN_KERNEL_RBF && kernel != STEIN_KERNEL_IMQ) return fail(STEIN_E_BADARG, "unknown kernel id %d", kernel);
+  BootLayout L;
+  if ((rc = boot_make_layout(n, d, reps, &L, true))) return rc;
+  if (ws_bytes < L.total) return fail(STEIN_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L.total);
+  if ((rc = stein_take_device_error())) return rc;
+  const hipStream_t s = (hipStream_t)stream;
+  if (kernel == STEIN_KERNEL_RBF)
+    return boot_launch<RbfBoot, true>(L, (char*)workspace, (const float*)theta, (const float*)score, n, d, h2_in, V, reps, nullptr,
+                                      nullptr, s, out);
+  return boot_launch<ImqBoot, true>(L, (char*)workspace, (const float*)theta, (const float*)score, n, d, h2_in, V, reps, nullptr,
+                                    nullptr, s, out);
 }

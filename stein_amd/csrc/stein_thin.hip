@@ -26,12 +26,7 @@
 // of u_p(s, j) does not depend on which lanes computed it (duplicated rows get equal objectives: the lower index wins).
 // Every load is plain C++; every index read from memory is clamped to [0, n) before it addresses anything.
 
-#include "stein_host.h"
-
-constexpr int THIN_THREADS = 256;
-constexpr int THIN_CHUNK = 512;     // columns of x_s and of g_s in LDS at a time (4 KB)
-constexpr int THIN_RB = 4;          // rows a lane group holds at once: 2 x THIN_RB loads in flight per lane
-constexpr int THIN_MAX_PARTS = 1024;
+#include "stein_thin_dev.h"   // the constants, the (value, index) order, thin_up and the row sums: shared with stein_weights.hip
 
 struct ThinPart { double v; long long j; };
 
@@ -44,44 +39,8 @@ struct ThinArgs {
   long long* idx_out; double* ksd2_out;
 };
 
-__device__ __forceinline__ bool thin_less(double v, long long j, double bv, long long bj) {
-  return v < bv || (v == bv && j < bj);
-}
-
-// (v, j) of the workgroup's least value, lowest index on equal value, in every thread
-__device__ __forceinline__ void thin_block_argmin(double& v, long long& j, double* sv, long long* sj) {
-  for (int o = 32; o; o >>= 1) {
-    const double ov = __shfl_xor(v, o);
-    const long long oj = __shfl_xor(j, o);
-    if (thin_less(ov, oj, v, j)) { v = ov; j = oj; }
-  }
-  __syncthreads();   // (the arrays' previous readers)
-  if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = v; sj[threadIdx.x >> 6] = j; }
-  __syncthreads();
-  v = sv[0]; j = sj[0];
-  for (int w = 1; w < THIN_THREADS / 64; ++w)
-    if (thin_less(sv[w], sj[w], v, j)) { v = sv[w]; j = sj[w]; }
-}
-
-__device__ __forceinline__ float thin_group_sum(float x, int lg) {
-  for (int o = lg >> 1; o; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
-
-// u_p from the three sums of one pair
-__device__ __forceinline__ float thin_up(int kernel, float D, float cross, float gg, float h2, float fd) {
-  if (kernel == STEIN_KERNEL_IMQ) {
-    const float c2 = 2.0f * h2;
-    const float k = rsqrtf(1.0f + D / c2);
-    const float k3 = k * k * k, k5 = k3 * k * k;
-    return k * gg + k3 * cross / c2 + fd * k3 / c2 - 3.0f * k5 * D / (c2 * c2);
-  }
-  const float k = expf(-D / (2.0f * h2));
-  return k * (gg + cross / h2 + fd / h2 - D / (h2 * h2));
-}
-
 template <bool VEC>
-__global__ __launch_bounds__(THIN_THREADS) void k_thin_step(ThinArgs a) {
+__global__ __launch_bounds__(THIN_THREADS, THIN_WAVES_PER_SIMD) void k_thin_step(ThinArgs a) {
   __shared__ __attribute__((aligned(16))) float sx[THIN_CHUNK];
   __shared__ __attribute__((aligned(16))) float sg[THIN_CHUNK];
   __shared__ double sv[THIN_THREADS / 64];
@@ -143,59 +102,9 @@ __global__ __launch_bounds__(THIN_THREADS) void k_thin_step(ThinArgs a) {
     }
     for (long long batch = blockIdx.x; batch < nbatch; batch += gridDim.x) {   // (uniform per workgroup: barriers inside)
       long long row[THIN_RB];
-      const float* xr[THIN_RB];
-      const float* gr[THIN_RB];
-      float D[THIN_RB], C[THIN_RB], G[THIN_RB];
-#pragma unroll
-      for (int r = 0; r < THIN_RB; ++r) {   // for a fixed r the wave's groups read gpw consecutive rows
-        row[r] = batch * rows_per_batch + ((long long)wave * THIN_RB + r) * gpw + grp;
-        const long long rc = row[r] < n ? row[r] : n - 1;
-        xr[r] = a.theta + rc * d;
-        gr[r] = a.score + rc * d;
-        D[r] = C[r] = G[r] = 0.0f;
-      }
-      for (long long c0 = 0; c0 < d; c0 += THIN_CHUNK) {
-        const int len = (int)(d - c0 < THIN_CHUNK ? d - c0 : THIN_CHUNK);
-        if (!one_chunk) {
-          __syncthreads();   // (the previous chunk's readers)
-          for (int c = tid; c < len; c += THIN_THREADS) { sx[c] = xs[c0 + c]; sg[c] = gs[c0 + c]; }
-          __syncthreads();
-        }
-        if (VEC) {   // 3. 16-byte units: d % 4 == 0 and both bases aligned, so every row and every chunk starts aligned
-          for (int u = gl; u < len / 4; u += lg) {
-            const float4 x0 = reinterpret_cast<const float4*>(sx)[u], g0 = reinterpret_cast<const float4*>(sg)[u];
-            float4 x[THIN_RB], g[THIN_RB];
-#pragma unroll
-            for (int r = 0; r < THIN_RB; ++r) {
-              x[r] = reinterpret_cast<const float4*>(xr[r] + c0)[u];
-              g[r] = reinterpret_cast<const float4*>(gr[r] + c0)[u];
-            }
-#pragma unroll
-            for (int r = 0; r < THIN_RB; ++r) {
-              const float dx0 = x0.x - x[r].x, dx1 = x0.y - x[r].y, dx2 = x0.z - x[r].z, dx3 = x0.w - x[r].w;
-              D[r] = fmaf(dx0, dx0, D[r]); D[r] = fmaf(dx1, dx1, D[r]); D[r] = fmaf(dx2, dx2, D[r]); D[r] = fmaf(dx3, dx3, D[r]);
-              C[r] = fmaf(g0.x - g[r].x, dx0, C[r]); C[r] = fmaf(g0.y - g[r].y, dx1, C[r]);
-              C[r] = fmaf(g0.z - g[r].z, dx2, C[r]); C[r] = fmaf(g0.w - g[r].w, dx3, C[r]);
-              G[r] = fmaf(g0.x, g[r].x, G[r]); G[r] = fmaf(g0.y, g[r].y, G[r]);
-              G[r] = fmaf(g0.z, g[r].z, G[r]); G[r] = fmaf(g0.w, g[r].w, G[r]);
-            }
-          }
-        } else {     //    4-byte units: any d, any alignment
-          for (int u = gl; u < len; u += lg) {
-            const float x0 = sx[u], g0 = sg[u];
-            float x[THIN_RB], g[THIN_RB];
-#pragma unroll
-            for (int r = 0; r < THIN_RB; ++r) { x[r] = xr[r][c0 + u]; g[r] = gr[r][c0 + u]; }
-#pragma unroll
-            for (int r = 0; r < THIN_RB; ++r) {
-              const float dx = x0 - x[r];
-              D[r] = fmaf(dx, dx, D[r]);
-              C[r] = fmaf(g0 - g[r], dx, C[r]);
-              G[r] = fmaf(g0, g[r], G[r]);
-            }
-          }
-        }
-      }
+      float D[THIN_RB], C[THIN_RB], G[THIN_RB];   // 3. (thin_row_sums: 16-byte or 4-byte units)
+      thin_row_sums<VEC>(a.theta, a.score, xs, gs, sx, sg, n, d, batch, rows_per_batch, lg, gl, grp, gpw, wave, tid, one_chunk,
+                         row, D, C, G);
 #pragma unroll
       for (int r = 0; r < THIN_RB; ++r) {
         const float Dr = thin_group_sum(D[r], lg), Cr = thin_group_sum(C[r], lg), Gr = thin_group_sum(G[r], lg);
@@ -264,11 +173,9 @@ extern "C" int stein_thin(const void* theta, const void* score, int64_t n, int64
   if (ws_bytes < L.total) return fail(STEIN_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L.total);
   if ((rc = stein_take_device_error())) return rc;
 
-  const bool vec = d % 4 == 0 && (((uintptr_t)theta | (uintptr_t)score) & 15) == 0;
-  int64_t units = vec ? d / 4 : d;
-  int lg = 1;
-  while (lg < 64 && lg < units) lg <<= 1;
-  const int64_t rows_per_batch = (int64_t)(THIN_THREADS / 64) * (64 / lg) * THIN_RB;
+  bool vec;
+  const int lg = thin_lane_group(d, theta, score, &vec);
+  const int64_t rows_per_batch = thin_rows_per_batch(lg);
   int64_t blocks = (n + rows_per_batch - 1) / rows_per_batch;
   if (g_thin_grid > 0) blocks = g_thin_grid;
   if (blocks > THIN_MAX_PARTS) blocks = THIN_MAX_PARTS;

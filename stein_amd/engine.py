@@ -114,6 +114,20 @@ class HipStages:
         _lib.call_on(T.device, "stein_ksd_boot", _ptr(T), _ptr(G), n, d, _dt(T), _ptr(h2), kernel, _ptr(weights), reps,
                      _ptr(q), _ptr(diag), _ptr(ws), ws.numel(), 0, _stream(T))
 
+    def ksd_matmul(self, T, G, n, d, h2, kernel, V, reps, out, ws):
+        """Stein-kernel products (stein_ksd_matmul, include/steinhip.h): out[b, i] = sum_j u_p(x_i, x_j) V[b, j] for the
+        float32 device tensor V [reps, n] into the float32 device tensor out [reps, n].  kernel: _lib.KERNEL_RBF /
+        _lib.KERNEL_IMQ."""
+        _lib.call_on(T.device, "stein_ksd_matmul", _ptr(T), _ptr(G), n, d, _dt(T), _ptr(h2), kernel, _ptr(V), reps, _ptr(out),
+                     _ptr(ws), ws.numel(), 0, _stream(T))
+
+    def weights(self, T, G, n, d, h2, kernel, iters, w, stats, idx, gamma, ws):
+        """Stein importance weights (stein_weights, include/steinhip.h): `iters` Frank-Wolfe steps from the uniform weights
+        into the float64 device tensors w [n] and stats [3] = f(w), gap, f(uniform); idx (int64 [iters]) and gamma (float64
+        [iters]) take the steps' vertices and lengths, or None.  kernel: _lib.KERNEL_RBF / _lib.KERNEL_IMQ."""
+        _lib.call_on(T.device, "stein_weights", _ptr(T), _ptr(G), n, d, _dt(T), _ptr(h2), kernel, iters, _ptr(w), _ptr(stats),
+                     _ptr(idx), _ptr(gamma), _ptr(ws), ws.numel(), 0, _stream(T))
+
     def x3_prepare(self, T, G, n, d, planes):
         """T or G may be None: only the other matrix's scales and planes are rebuilt."""
         ref = T if T is not None else G

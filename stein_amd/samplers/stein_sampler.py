@@ -82,6 +82,18 @@ class SteinSampler(AbstractSteinSampler):
         from ..utilities.stein_test import stein_goodness_of_fit
         return stein_goodness_of_fit(self._matrix_f32().detach(), self.score_matrix(batch_feed).detach(), **kw)
 
+    def importance_weights(self, batch_feed=None, iters=None, bandwidth="median", kernel="imq", return_path=False):
+        """Stein importance weights of the sampler's own particles at their current scores (score_matrix(batch_feed)):
+        (w, info) from stein_amd.utilities.stein_importance_weights, which see -- w a float64 device tensor [n] on the
+        simplex that lowers the KSD^2 of the weighted particles, info its KSD^2, the uniform weights' and the duality gap.
+        `(w[:, None] * f(theta_matrix)).sum(0)` is the corrected estimate; the particles do not move.  One rank only."""
+        if self._group is not None:
+            raise ValueError("importance_weights works on one rank only: the weights couple all n particles; gather "
+                             "them (samples_all) and call stein_amd.utilities.stein_importance_weights")
+        from ..utilities.stein_weights import stein_importance_weights
+        return stein_importance_weights(self._matrix_f32().detach(), self.score_matrix(batch_feed).detach(), iters=iters,
+                                        bandwidth=bandwidth, kernel=kernel, return_path=return_path)
+
     @property
     def samples(self):
         """Packed [n_local, d] particle matrix as NumPy (stein_sampler.py:73-78)."""
