@@ -700,6 +700,32 @@ int stein_predict_bnn(const float* theta, int64_t n, int64_t d, int64_t n_in, in
                       int output, const float* X, const float* y, int64_t batch,
                       float* pred, float* mean, float* var, float* lpd, void* workspace, size_t ws_bytes, void* stream);
 
+/* Weighted summaries: the same producers under per-particle weights -- Stein importance weights (stein_weights), or the
+ * counts of a thinned multiset (torch.bincount of stein_thin's indices).  weights [n]: fp64 device data, w_p >= 0, their
+ * sum W > 0; they need not sum to 1.
+ *   mean_b = sum_p w_p f_pb / W      var_b = sum_p w_p (f_pb - mean_b)^2 / W      lpd_b = log(sum_p w_p exp(l_pb) / W)
+ *   ess [1] (fp64, device) = W^2 / sum_p w_p^2, the effective sample size of the weights
+ * with f_pb and l_pb those of the unweighted calls.  pred does not depend on the weights: it is bit for bit the unweighted
+ * call's and is written for every particle.  A particle of weight zero is skipped: its outputs enter no summary, even when
+ * they are not finite.  The lanes hold fl32(w_p / W), the quotient taken in fp64, so a power-of-two rescaling of the
+ * weights changes no bit of any output while the sums stay in fp64's normal range; a weight below 2^-126 W counts as zero.
+ * The host never reads the weights: if one is negative or not finite, or W is 0 or overflows, the call returns STEIN_OK
+ * and every requested summary row and ess are NaN.
+ * Refusals and their order are those of the unweighted calls, with weights == NULL among the NULL pointers
+ * (STEIN_E_BADARG) and ess counting as a requested output and as a summary: a call that asks for mean, var, lpd or ess
+ * needs stein_predict_weighted_workspace_bytes(n, batch) bytes, 8-byte aligned -- the unweighted size plus 24 bytes per
+ * particle slice and 16 more for the sums of the weights; monotone in both arguments, independent of d.  It may hold
+ * anything on entry.  Deterministic: no atomics, the weights and the slices are summed in a fixed order. */
+int stein_predict_weighted_workspace_bytes(int64_t n, int64_t batch, size_t* out_bytes);
+int stein_predict_glm_weighted(const float* theta, int64_t n, int64_t d, int kind, int output, int64_t w_col,
+                               int64_t n_feats, const float* X, const float* y, int64_t batch, double noise_precision,
+                               const double* weights, float* pred, float* mean, float* var, float* lpd, double* ess,
+                               void* workspace, size_t ws_bytes, void* stream);
+int stein_predict_bnn_weighted(const float* theta, int64_t n, int64_t d, int64_t n_in, int64_t n_hidden,
+                               const int64_t* cols, int output, const float* X, const float* y, int64_t batch,
+                               const double* weights, float* pred, float* mean, float* var, float* lpd, double* ess,
+                               void* workspace, size_t ws_bytes, void* stream);
+
 /* small helpers used by the host layer */
 int stein_cast_f64_to_f32(const double* src, float* dst, int64_t count, void* stream);
 int stein_cast_f32_to_bf16(const float* src, void* dst, int64_t count, void* stream);

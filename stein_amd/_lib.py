@@ -65,6 +65,11 @@ _SIGNATURES = {
     "stein_predict_workspace_bytes": [_i64, _i64, _c.POINTER(_sz)],
     "stein_predict_glm": [_vp, _i64, _i64, _int, _int, _i64, _i64, _vp, _vp, _i64, _dbl, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "stein_predict_bnn": [_vp, _i64, _i64, _i64, _i64, _c.POINTER(_i64), _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    "stein_predict_weighted_workspace_bytes": [_i64, _i64, _c.POINTER(_sz)],
+    "stein_predict_glm_weighted": [_vp, _i64, _i64, _int, _int, _i64, _i64, _vp, _vp, _i64, _dbl, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _sz, _vp],
+    "stein_predict_bnn_weighted": [_vp, _i64, _i64, _i64, _i64, _c.POINTER(_i64), _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _vp, _sz, _vp],
     "stein_rank_begin": [_vp, _i64, _i64, _i64, _i64, _int, _vp, _sz, _int, _vp],
     "stein_rank_pick": [_i64, _i64, _i64, _i64, _int, _vp, _sz, _int, _vp, _vp, _vp, _vp],
     "stein_rank_radix": [_int, _int, _i64, _i64, _i64, _i64, _int, _vp, _sz, _int, _vp, _vp, _vp],
@@ -341,6 +346,14 @@ def predict_workspace_bytes(n, batch):
     slice, independent of d.  Host arithmetic."""
     total = _sz(0)
     call("stein_predict_workspace_bytes", n, batch, ctypes.byref(total))
+    return int(total.value)
+
+
+def predict_weighted_workspace_bytes(n, batch):
+    """Workspace bytes of a stein_predict_*_weighted call that asks for mean, var, lpd or ess: the unweighted size plus the
+    weight pass's per-slice sums.  Host arithmetic."""
+    total = _sz(0)
+    call("stein_predict_weighted_workspace_bytes", n, batch, ctypes.byref(total))
     return int(total.value)
 
 

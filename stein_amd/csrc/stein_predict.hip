@@ -19,7 +19,18 @@
 // the slices in slice order (Chan et al.'s pairwise update and a max / rescaled-sum merge, both in fp64, as a fixed tree).  A slice's
 // particle count follows from its index, so it is not stored, and every workspace word that is read was written by the
 // same call: the workspace may hold anything on entry.
+//
+// Weighted form (stein_predict_*_weighted; the WEIGHTED instantiations below): per-particle weights w_p >= 0 in fp64, W their
+// sum, mean_b = sum_p w_p f_pb / W and so on (include/steinhip.h).  k_predict_wsum / k_predict_wtotal sum the weights per
+// slice and in total in fp64, in a fixed order, and poison W with NaN when a weight is negative or not finite or W is 0.
+// The forward kernels stage fl32(w_p / W) of a pass's particles beside the particle data (the quotient is taken in fp64, so
+// a power-of-two rescaling of w changes no bit; a quotient below 2^-126 counts as zero), every lane reads them at one
+// address, and the running state becomes West's weighted update and a running max with sum w exp(l - max); a particle of
+// weight zero is skipped.  The first particle with w > 0 sets shift, max and sum.  The state stays five floats: a slice's
+// weight W_s / W is per slice, not per row, and comes from the weight pass, which also zeroes the W_s of a slice none of
+// whose weights survives the rounding, so the finish kernel skips exactly the slices whose state was never set.
 #include "stein_common.h"
+#include <cfloat>
 
 constexpr int PR_ROWS = 256;         // rows of X per workgroup: one per lane
 constexpr int PR_PASS = 16;          // particles per pass: their outputs are 16 registers of every lane
@@ -67,6 +78,48 @@ __device__ __forceinline__ void pred_accumulate(PredState& st, int k, float f, f
   }
 }
 
+// The weighted update of one particle of normalised weight w (lane-uniform; 0: skipped) with wk the running sum of the
+// weights before it.  West (1979) on g = f - shift: wk += w, mean += (w / wk) delta, M2 += w delta (g - mean).  The first
+// particle with w > 0 meets wk = 0: it sets the shift (g = 0, delta = 0: mean and M2 stay exactly 0), max = l and sum = w.
+__device__ __forceinline__ void pred_accumulate_weighted(PredState& st, float& wk, float w, float f, float l, bool want_mv,
+                                                         bool want_lpd) {
+  if (!(w > 0.f)) return;
+  const bool first = wk == 0.f;
+  wk += w;
+  if (want_mv) {
+    if (first) st.shift = f;
+    const float g = f - st.shift;
+    const float delta = g - st.mean;
+    st.mean = fmaf(delta, w / wk, st.mean);
+    st.m2 = fmaf(w * delta, g - st.mean, st.m2);
+  }
+  if (want_lpd) {
+    if (first) {
+      st.mx = l;
+      st.se = w;
+    } else {
+      const float e = l == st.mx ? 1.f : expf(-fabsf(l - st.mx));
+      if (l > st.mx) {
+        st.se = fmaf(st.se, e, w);
+        st.mx = l;
+      } else {
+        st.se = fmaf(w, e, st.se);
+      }
+    }
+  }
+}
+
+// The header of a weighted call's workspace, in doubles: W (NaN: bad weights), sum w^2, then per slice W_s (0 after
+// k_predict_wtotal when none of the slice's weights survives the rounding to fp32), sum w^2 and max w.  The states follow.
+constexpr int PW_HEAD = 2;
+__host__ __device__ constexpr size_t pw_doubles(int64_t slices) { return (size_t)(PW_HEAD + 3 * slices); }
+
+// fl32(w / W) as the lanes hold it: below the normal range it counts as zero (whatever the denormal mode); W = NaN gives 0
+__device__ __forceinline__ float pred_norm_weight(double w, double W) {
+  const float q = (float)(w / W);
+  return q >= FLT_MIN ? q : 0.f;
+}
+
 __device__ __forceinline__ void pred_store_state(const PredState& st, float* __restrict__ part, int slice, int B, int row,
                                                  bool want_mv, bool want_lpd) {
   float* p = part + (size_t)slice * PR_STATE * B + row;   // [slice][shift, mean, m2, max, sum][B]
@@ -82,15 +135,21 @@ __device__ __forceinline__ void pred_store_state(const PredState& st, float* __r
 }
 
 // fc = features per chunk (F when the whole tile fits, else PR_FC), ld = floats per staged row of X (odd: lane t reads
-// xs[t * ld + f], 64 different banks)
+// xs[t * ld + f], 64 different banks).  WEIGHTED: wts [n] the weights, head the weight pass's header (head[0] = W); the
+// pass's PR_PASS normalised weights are staged behind ws.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_predict_glm(const float* __restrict__ theta, int n, int d, int kind, int output,
                                                      int w_col, int F, int fc, int ld, const float* __restrict__ X,
                                                      const float* __restrict__ y, int B, int per, float half_tau, float c0,
                                                      float* __restrict__ pred, float* __restrict__ part, int want_mv,
-                                                     int want_lpd) {
+                                                     int want_lpd, const double* __restrict__ wts,
+                                                     const double* __restrict__ head) {
   extern __shared__ float lds[];
   float* xs = lds;                   // [PR_ROWS][ld]
   float* ws = lds + PR_ROWS * ld;    // [fc][PR_PASS]
+  float* wl = ws + fc * PR_PASS;     // [PR_PASS], WEIGHTED only
+  float wk = 0.f;
+  const double wtot = WEIGHTED ? head[0] : 0.0;
   const int t = threadIdx.x;
   const int row0 = blockIdx.x * PR_ROWS, row = row0 + t;
   const bool live = row < B;
@@ -119,6 +178,7 @@ __global__ __launch_bounds__(256) void k_predict_glm(const float* __restrict__ t
         const int k = i / len, f = i - k * len;
         ws[f * PR_PASS + k] = k < cnt ? theta[(size_t)(p0 + k) * d + w_col + f0 + f] : 0.f;
       }
+      if (WEIGHTED && c == 0 && t < PR_PASS) wl[t] = t < cnt ? pred_norm_weight(wts[p0 + t], wtot) : 0.f;
       __syncthreads();
       const float* xr = xs + t * ld;
 #pragma unroll 2
@@ -150,7 +210,8 @@ __global__ __launch_bounds__(256) void k_predict_glm(const float* __restrict__ t
             l = fmaf(-half_tau, r * r, c0);
           }
         }
-        pred_accumulate(st, p0 - p_begin + k, f, l, want_mv, want_lpd);
+        if constexpr (WEIGHTED) pred_accumulate_weighted(st, wk, wl[k], f, l, want_mv, want_lpd);
+        else pred_accumulate(st, p0 - p_begin + k, f, l, want_mv, want_lpd);
       }
     }
   }
@@ -159,14 +220,17 @@ __global__ __launch_bounds__(256) void k_predict_glm(const float* __restrict__ t
 
 // NIN input features in registers per lane; the PR_PASS staged particles' b1, w2 and w1 rows of a chunk of PR_HC hidden
 // units in LDS (hidden units past H are staged as zeros: relu(0) * 0 adds an exact zero)
-template <int NIN>
+template <int NIN, bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_predict_bnn(const float* __restrict__ theta, int n, int d, int H, PredCols c,
                                                      const float* __restrict__ X, const float* __restrict__ y, int B, int per,
                                                      float* __restrict__ pred, float* __restrict__ part, int want_mv,
-                                                     int want_lpd) {
+                                                     int want_lpd, const double* __restrict__ wts,
+                                                     const double* __restrict__ head) {
   constexpr int PW = (NIN + 2) * PR_HC;   // staged floats per particle: b1 [PR_HC], w2 [PR_HC], w1 [NIN][PR_HC]
   __shared__ __attribute__((aligned(16))) float lw[PR_PASS * PW];
-  __shared__ float lp[PR_PASS][4];        // per particle: b2, 1/2 lg - 1/2 log 2 pi, 1/2 e^lg
+  __shared__ float lp[PR_PASS][4];        // per particle: b2, 1/2 lg - 1/2 log 2 pi, 1/2 e^lg; WEIGHTED: its normalised weight
+  float wk = 0.f;
+  const double wtot = WEIGHTED ? head[0] : 0.0;
   const int t = threadIdx.x;
   const int row = blockIdx.x * PR_ROWS + t;
   const bool live = row < B;
@@ -200,6 +264,7 @@ __global__ __launch_bounds__(256) void k_predict_bnn(const float* __restrict__ t
         lp[t][0] = th[c.b2];
         lp[t][1] = fmaf(0.5f, lg, -PR_HALF_LOG_2PI);
         lp[t][2] = 0.5f * expf(lg);
+        if (WEIGHTED) lp[t][3] = pred_norm_weight(wts[p0 + t], wtot);
       }
       __syncthreads();
 #pragma unroll
@@ -238,7 +303,8 @@ __global__ __launch_bounds__(256) void k_predict_bnn(const float* __restrict__ t
           const float r = yb - f;
           l = fmaf(-lp[k][2], r * r, lp[k][1]);
         }
-        pred_accumulate(st, p0 - p_begin + k, f, l, want_mv, want_lpd);
+        if constexpr (WEIGHTED) pred_accumulate_weighted(st, wk, lp[k][3], f, l, want_mv, want_lpd);
+        else pred_accumulate(st, p0 - p_begin + k, f, l, want_mv, want_lpd);
       }
     }
   }
@@ -251,22 +317,33 @@ __global__ __launch_bounds__(256) void k_predict_bnn(const float* __restrict__ t
 // pass at 512 slices.)
 constexpr int PF_ROWS = 16, PF_GROUPS = 16;
 
+//
+// WEIGHTED: a slice counts with W_s / W of the weight pass's header in place of its particle count, so the total is 1 and
+// nothing is divided at the end; a slice (and then a group) of weight 0 holds no state and is skipped, wherever it lies.
+// Bad weights (W = NaN) give NaN rows.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_predict_finish(const float* __restrict__ part, int slices, int per, int n, int B,
                                                         float* __restrict__ mean, float* __restrict__ var,
-                                                        float* __restrict__ lpd) {
+                                                        float* __restrict__ lpd, const double* __restrict__ head) {
   __shared__ double sh[5][PF_GROUPS][PF_ROWS];   // count, mean, M2, max, sum
   const int r = threadIdx.x % PF_ROWS, g = threadIdx.x / PF_ROWS;
   const int b = blockIdx.x * PF_ROWS + r;
   const int per_g = (slices + PF_GROUPS - 1) / PF_GROUPS;
   const int s0 = g * per_g, s1 = min(slices, s0 + per_g);
   const size_t sB = (size_t)B;
+  const double wtot = WEIGHTED ? head[0] : 0.0;
+  auto weight = [&](int s) {   // of slice s: not positive (0, or NaN under a poisoned W) = no state
+    if constexpr (WEIGHTED) return head[PW_HEAD + s] / wtot;
+    else return (double)min(per, n - s * per);
+  };
   double cnt = 0.0, m = 0.0, m2 = 0.0, top = 0.0, sum = 0.0;
   if (b < B && s0 < s1) {
     const float* p = part + b;
     if (mean || var) {   // Chan et al.: (count, mean, M2) of the union of two sets
       for (int s = s0; s < s1; ++s) {
         const float* ps = p + (size_t)s * PR_STATE * sB;
-        const double cs = (double)min(per, n - s * per);
+        const double cs = weight(s);
+        if (WEIGHTED && !(cs > 0.0)) continue;
         const double ms = (double)ps[0] + (double)ps[sB], m2s = ps[2 * sB];
         const double tot = cnt + cs, delta = ms - m;
         m += delta * (cs / tot);
@@ -274,11 +351,30 @@ __global__ __launch_bounds__(256) void k_predict_finish(const float* __restrict_
         cnt = tot;
       }
     }
-    cnt = (double)(min((long)n, (long)s1 * per) - (long)s0 * per);
-    if (lpd) {
-      top = (double)p[((size_t)s0 * PR_STATE + 3) * sB];
-      for (int s = s0 + 1; s < s1; ++s) top = fmax(top, (double)p[((size_t)s * PR_STATE + 3) * sB]);
+    if constexpr (WEIGHTED) {   // the same sum in the same order, whether or not the loop above ran
+      cnt = 0.0;
       for (int s = s0; s < s1; ++s) {
+        const double cs = weight(s);
+        if (cs > 0.0) cnt += cs;
+      }
+    } else {
+      cnt = (double)(min((long)n, (long)s1 * per) - (long)s0 * per);
+    }
+    if (lpd) {
+      if constexpr (WEIGHTED) {
+        bool any = false;
+        for (int s = s0; s < s1; ++s) {
+          if (!(weight(s) > 0.0)) continue;
+          const double mx = p[((size_t)s * PR_STATE + 3) * sB];
+          top = any ? fmax(top, mx) : mx;
+          any = true;
+        }
+      } else {
+        top = (double)p[((size_t)s0 * PR_STATE + 3) * sB];
+        for (int s = s0 + 1; s < s1; ++s) top = fmax(top, (double)p[((size_t)s * PR_STATE + 3) * sB]);
+      }
+      for (int s = s0; s < s1; ++s) {
+        if (WEIGHTED && !(weight(s) > 0.0)) continue;
         const double mx = p[((size_t)s * PR_STATE + 3) * sB], se = p[((size_t)s * PR_STATE + 4) * sB];
         sum += mx == top ? se : se * exp(mx - top);
       }
@@ -287,8 +383,22 @@ __global__ __launch_bounds__(256) void k_predict_finish(const float* __restrict_
   sh[0][g][r] = cnt; sh[1][g][r] = m; sh[2][g][r] = m2; sh[3][g][r] = top; sh[4][g][r] = sum;
   __syncthreads();
   if (g != 0 || b >= B) return;
-  for (int k = 1; k < PF_GROUPS; ++k) {   // (group 0 is never empty)
+  if (WEIGHTED && !(wtot > 0.0)) {   // a negative or non-finite weight, or W = 0
+    const float bad = __builtin_nanf("");
+    if (mean) mean[b] = bad;
+    if (var) var[b] = bad;
+    if (lpd) lpd[b] = bad;
+    return;
+  }
+  for (int k = 1; k < PF_GROUPS; ++k) {   // (unweighted: group 0 is never empty, and no group follows an empty one)
     const double cs = sh[0][k][r];
+    if (WEIGHTED) {
+      if (!(cs > 0.0)) continue;
+      if (cnt == 0.0) {   // the first group that holds anything
+        cnt = cs; m = sh[1][k][r]; m2 = sh[2][k][r]; top = sh[3][k][r]; sum = sh[4][k][r];
+        continue;
+      }
+    }
     if (cs == 0.0) break;
     const double tot = cnt + cs, delta = sh[1][k][r] - m;
     m += delta * (cs / tot);
@@ -303,8 +413,67 @@ __global__ __launch_bounds__(256) void k_predict_finish(const float* __restrict_
     }
   }
   if (mean) mean[b] = (float)m;
-  if (var) var[b] = (float)(m2 / (double)n);
-  if (lpd) lpd[b] = (float)(top + log(sum) - log((double)n));
+  if (var) var[b] = WEIGHTED ? (float)m2 : (float)(m2 / (double)n);
+  if (lpd) lpd[b] = WEIGHTED ? (float)(top + log(sum)) : (float)(top + log(sum) - log((double)n));
+}
+
+// ---- the weight pass of a weighted call ------------------------------------------------------------------
+// 256 partial results per quantity folded by halving, in a fixed order: quantities 0 and 1 are sums, 2 is a maximum
+__device__ __forceinline__ void pw_fold(double (*sh)[256], int t, int quantities) {
+  for (int half = 128; half > 0; half >>= 1) {
+    __syncthreads();
+    if (t < half)
+      for (int q = 0; q < quantities; ++q) sh[q][t] = q == 2 ? fmax(sh[q][t], sh[q][t + half]) : sh[q][t] + sh[q][t + half];
+  }
+  __syncthreads();
+}
+
+// one workgroup per slice of predict_plan: W_s, sum w^2 and max w of the slice; a weight that is negative or not finite
+// turns W_s into NaN, which every later sum keeps
+__global__ __launch_bounds__(256) void k_predict_wsum(const double* __restrict__ wts, int n, int per, int slices,
+                                                      double* __restrict__ head) {
+  __shared__ double sh[3][256];
+  const int t = threadIdx.x, s = blockIdx.x;
+  const int p_begin = s * per, p_end = min(n, p_begin + per);
+  double a = 0.0, q = 0.0, top = 0.0;
+  bool bad = false;
+  for (int p = p_begin + t; p < p_end; p += 256) {
+    const double v = wts[p];
+    bad = bad || !(v >= 0.0 && v < (double)INFINITY);
+    a += v;
+    q += v * v;
+    top = fmax(top, v);
+  }
+  sh[0][t] = bad ? (double)NAN : a; sh[1][t] = q; sh[2][t] = top;
+  pw_fold(sh, t, 3);
+  if (t == 0) {
+    head[PW_HEAD + s] = sh[0][0];
+    head[PW_HEAD + slices + s] = sh[1][0];
+    head[PW_HEAD + 2 * slices + s] = sh[2][0];
+  }
+}
+
+// one workgroup: W and sum w^2 over the slices, the poison (W is NaN unless 0 < W < inf), ess = W^2 / sum w^2, and W_s = 0
+// for a slice whose largest weight rounds to zero as the forward kernels round it (rounding is monotone: then all do)
+__global__ __launch_bounds__(256) void k_predict_wtotal(int slices, double* __restrict__ head, double* __restrict__ ess) {
+  __shared__ double sh[2][256];
+  const int t = threadIdx.x;
+  double a = 0.0, q = 0.0;
+  for (int s = t; s < slices; s += 256) {
+    a += head[PW_HEAD + s];
+    q += head[PW_HEAD + slices + s];
+  }
+  sh[0][t] = a; sh[1][t] = q;
+  pw_fold(sh, t, 2);
+  double W = sh[0][0];
+  if (!(W > 0.0 && W < (double)INFINITY)) W = (double)NAN;
+  for (int s = t; s < slices; s += 256)
+    if (!(pred_norm_weight(head[PW_HEAD + 2 * slices + s], W) > 0.f)) head[PW_HEAD + s] = 0.0;
+  if (t == 0) {
+    head[0] = W;
+    head[1] = sh[1][0];
+    if (ess) *ess = W * W / sh[1][0];
+  }
 }
 
 // ---- host side -----------------------------------------------------------------------------------------
@@ -342,12 +511,31 @@ extern "C" int stein_predict_workspace_bytes(int64_t n, int64_t batch, size_t* o
   return STEIN_OK;
 }
 
-// the checks the two entry points share, in the order the header lists them
+// the weights of a weighted call (on = false: an unweighted call, for which every check and launch is what it was)
+struct PredWeights { bool on; const double* w; double* ess; };
+
+static size_t predict_wws_bytes(int64_t n, int64_t batch) {   // the states behind the weight pass's header; monotone too
+  int64_t s = (n + PR_PASS - 1) / PR_PASS;
+  if (s > PR_SLICE_CAP) s = PR_SLICE_CAP;
+  return pw_doubles(s) * sizeof(double) + predict_ws_bytes(n, batch);
+}
+
+extern "C" int stein_predict_weighted_workspace_bytes(int64_t n, int64_t batch, size_t* out_bytes) {
+  if (!out_bytes) return stein_fail(STEIN_E_BADARG, "NULL pointer");
+  if (n < 1 || batch < 1 || n > PR_COUNT_MAX || batch > PR_COUNT_MAX)
+    return stein_fail(STEIN_E_SHAPE, "bad shape n=%lld batch=%lld", (long long)n, (long long)batch);
+  *out_bytes = predict_wws_bytes(n, batch);
+  return STEIN_OK;
+}
+
+// the checks the entry points share, in the order the header lists them
 static int predict_check(const float* theta, const float* X, const float* y, int64_t n, int64_t d, int64_t batch,
                          int64_t width, int output, const float* pred, const float* mean, const float* var,
-                         const float* lpd) {
-  if (!theta || !X) return stein_fail(STEIN_E_BADARG, "NULL pointer");
-  if (!pred && !mean && !var && !lpd) return stein_fail(STEIN_E_BADARG, "no output requested: pred, mean, var and lpd are all NULL");
+                         const float* lpd, const PredWeights& pw) {
+  if (!theta || !X || (pw.on && !pw.w)) return stein_fail(STEIN_E_BADARG, "NULL pointer");
+  if (!pred && !mean && !var && !lpd && !pw.ess)
+    return stein_fail(STEIN_E_BADARG, pw.on ? "no output requested: pred, mean, var, lpd and ess are all NULL"
+                                            : "no output requested: pred, mean, var and lpd are all NULL");
   if (lpd && !y) return stein_fail(STEIN_E_BADARG, "lpd needs y");
   if (output != STEIN_PRED_LINK && output != STEIN_PRED_MEAN) return stein_fail(STEIN_E_BADARG, "output %d", output);
   if (n < 1 || d < 1 || batch < 1 || width < 1 || n > PR_COUNT_MAX || d > 0x7fffffffl || batch > PR_COUNT_MAX)
@@ -356,27 +544,46 @@ static int predict_check(const float* theta, const float* X, const float* y, int
   return STEIN_OK;
 }
 
-static int predict_check_ws(int64_t n, int64_t batch, bool summary, const void* workspace, size_t ws_bytes) {
+static int predict_check_ws(int64_t n, int64_t batch, bool summary, const void* workspace, size_t ws_bytes,
+                            const PredWeights& pw) {
   if (!summary) return STEIN_OK;   // a call that only asks for pred needs no workspace
-  if (!workspace) return stein_fail(STEIN_E_WORKSPACE, "mean, var and lpd need a workspace (stein_predict_workspace_bytes)");
-  const size_t need = predict_ws_bytes(n, batch);
+  if (!workspace)
+    return stein_fail(STEIN_E_WORKSPACE, pw.on ? "mean, var, lpd and ess need a workspace (stein_predict_weighted_workspace_bytes)"
+                                               : "mean, var and lpd need a workspace (stein_predict_workspace_bytes)");
+  const size_t need = pw.on ? predict_wws_bytes(n, batch) : predict_ws_bytes(n, batch);
   if (ws_bytes < need) return stein_fail(STEIN_E_WORKSPACE, "workspace too small: %zu < %zu bytes", ws_bytes, need);
+  if (pw.on && (uintptr_t)workspace % sizeof(double))
+    return stein_fail(STEIN_E_WORKSPACE, "the workspace of a weighted call must be 8-byte aligned");
+  return STEIN_OK;
+}
+
+// where a call's states lie in its workspace: at its start, or behind the weight pass's header
+static float* predict_states(const PredPlan& pl, void* workspace, const PredWeights& pw) {
+  return pw.on ? (float*)((double*)workspace + pw_doubles(pl.slices)) : (float*)workspace;
+}
+
+// the weight pass, queued ahead of the forward kernel of a weighted call that asks for any summary
+static int predict_weight_pass(const PredPlan& pl, int64_t n, const PredWeights& pw, void* workspace, hipStream_t s) {
+  hipLaunchKernelGGL(k_predict_wsum, dim3((unsigned)pl.slices), dim3(256), 0, s, pw.w, (int)n, pl.per, pl.slices, (double*)workspace);
+  LAUNCH_CHECK("k_predict_wsum");
+  hipLaunchKernelGGL(k_predict_wtotal, dim3(1), dim3(256), 0, s, pl.slices, (double*)workspace, pw.ess);
+  LAUNCH_CHECK("k_predict_wtotal");
   return STEIN_OK;
 }
 
 static int predict_finish(const PredPlan& pl, int64_t n, int64_t batch, const float* part, float* mean, float* var,
-                          float* lpd, hipStream_t s) {
-  hipLaunchKernelGGL(k_predict_finish, dim3((unsigned)((batch + PF_ROWS - 1) / PF_ROWS)), dim3(256), 0, s, part, pl.slices, pl.per, (int)n,
-                     (int)batch, mean, var, lpd);
+                          float* lpd, const double* head, hipStream_t s) {
+  const dim3 grid((unsigned)((batch + PF_ROWS - 1) / PF_ROWS));
+  if (head) hipLaunchKernelGGL(k_predict_finish<true>, grid, dim3(256), 0, s, part, pl.slices, pl.per, (int)n, (int)batch, mean, var, lpd, head);
+  else hipLaunchKernelGGL(k_predict_finish<false>, grid, dim3(256), 0, s, part, pl.slices, pl.per, (int)n, (int)batch, mean, var, lpd, head);
   LAUNCH_CHECK("k_predict_finish");
   return STEIN_OK;
 }
 
-extern "C" int stein_predict_glm(const float* theta, int64_t n, int64_t d, int kind, int output, int64_t w_col,
-                                 int64_t n_feats, const float* X, const float* y, int64_t batch, double noise_precision,
-                                 float* pred, float* mean, float* var, float* lpd, void* workspace, size_t ws_bytes,
-                                 void* stream) {
-  if (int rc = predict_check(theta, X, y, n, d, batch, n_feats, output, pred, mean, var, lpd)) return rc;
+static int predict_glm(const float* theta, int64_t n, int64_t d, int kind, int output, int64_t w_col, int64_t n_feats,
+                       const float* X, const float* y, int64_t batch, double noise_precision, float* pred, float* mean,
+                       float* var, float* lpd, void* workspace, size_t ws_bytes, void* stream, const PredWeights& pw) {
+  if (int rc = predict_check(theta, X, y, n, d, batch, n_feats, output, pred, mean, var, lpd, pw)) return rc;
   if (kind != STEIN_GLM_LINEAR && kind != STEIN_GLM_LOGISTIC) return stein_fail(STEIN_E_BADARG, "kind %d", kind);
   if (w_col < 0 || w_col + n_feats > d)
     return stein_fail(STEIN_E_SHAPE, "weights [%lld, %lld) do not fit d=%lld", (long long)w_col, (long long)(w_col + n_feats),
@@ -384,28 +591,36 @@ extern "C" int stein_predict_glm(const float* theta, int64_t n, int64_t d, int k
   if (n_feats > PR_WIDTH_MAX) return stein_fail(STEIN_E_UNSUPPORTED, "more than 1024 features per particle");
   if (lpd && kind == STEIN_GLM_LINEAR && !(noise_precision > 0.0 && noise_precision < INFINITY))
     return stein_fail(STEIN_E_BADARG, "noise_precision must be positive and finite");
-  const bool summary = mean || var || lpd;
-  if (int rc = predict_check_ws(n, batch, summary, workspace, ws_bytes)) return rc;
+  const bool summary = mean || var || lpd;   // the rows the forward kernel reduces; ess comes from the weight pass alone
+  if (int rc = predict_check_ws(n, batch, summary || pw.ess, workspace, ws_bytes, pw)) return rc;
   const PredPlan pl = predict_plan(n, batch);
   const int fc = (int)(n_feats <= PR_FC ? n_feats : PR_FC);
   const int ld = fc | 1;
   const size_t lds_bytes = ((size_t)PR_ROWS * ld + (size_t)fc * PR_PASS) * sizeof(float);
   const double tau = (lpd && kind == STEIN_GLM_LINEAR) ? noise_precision : 1.0;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_predict_glm, dim3((unsigned)pl.row_tiles, (unsigned)pl.slices), dim3(256), lds_bytes, s, theta, (int)n,
-                     (int)d, kind, output, (int)w_col, (int)n_feats, fc, ld, X, y, (int)batch, pl.per, (float)(0.5 * tau),
-                     (float)(0.5 * log(tau) - (double)PR_HALF_LOG_2PI), pred, summary ? (float*)workspace : nullptr,
-                     (mean || var) ? 1 : 0, lpd ? 1 : 0);
+  if (pw.on && (summary || pw.ess))
+    if (int rc = predict_weight_pass(pl, n, pw, workspace, s)) return rc;
+  if (!pred && !summary) return STEIN_OK;   // ess alone
+  float* part = summary ? predict_states(pl, workspace, pw) : nullptr;
+  const double* head = (pw.on && summary) ? (const double*)workspace : nullptr;
+#define PR_LAUNCH_GLM(WEIGHTED, LDS)                                                                                    \
+  hipLaunchKernelGGL(k_predict_glm<WEIGHTED>, dim3((unsigned)pl.row_tiles, (unsigned)pl.slices), dim3(256), LDS, s, theta, \
+                     (int)n, (int)d, kind, output, (int)w_col, (int)n_feats, fc, ld, X, y, (int)batch, pl.per,            \
+                     (float)(0.5 * tau), (float)(0.5 * log(tau) - (double)PR_HALF_LOG_2PI), pred, part,                   \
+                     (mean || var) ? 1 : 0, lpd ? 1 : 0, pw.w, head)
+  if (head) PR_LAUNCH_GLM(true, lds_bytes + PR_PASS * sizeof(float));
+  else PR_LAUNCH_GLM(false, lds_bytes);
+#undef PR_LAUNCH_GLM
   LAUNCH_CHECK("k_predict_glm");
-  return summary ? predict_finish(pl, n, batch, (const float*)workspace, mean, var, lpd, s) : STEIN_OK;
+  return summary ? predict_finish(pl, n, batch, part, mean, var, lpd, head, s) : STEIN_OK;
 }
 
-extern "C" int stein_predict_bnn(const float* theta, int64_t n, int64_t d, int64_t n_in, int64_t n_hidden,
-                                 const int64_t* cols /*[6]: w1, b1, w2, b2, log_lambda, log_gamma*/, int output,
-                                 const float* X, const float* y, int64_t batch, float* pred, float* mean, float* var,
-                                 float* lpd, void* workspace, size_t ws_bytes, void* stream) {
+static int predict_bnn(const float* theta, int64_t n, int64_t d, int64_t n_in, int64_t n_hidden, const int64_t* cols,
+                       int output, const float* X, const float* y, int64_t batch, float* pred, float* mean, float* var,
+                       float* lpd, void* workspace, size_t ws_bytes, void* stream, const PredWeights& pw) {
   if (!cols) return stein_fail(STEIN_E_BADARG, "NULL pointer");
-  if (int rc = predict_check(theta, X, y, n, d, batch, n_hidden, output, pred, mean, var, lpd)) return rc;
+  if (int rc = predict_check(theta, X, y, n, d, batch, n_hidden, output, pred, mean, var, lpd, pw)) return rc;
   if (n_in < 1) return stein_fail(STEIN_E_SHAPE, "bad shape n_in=%lld", (long long)n_in);
   if (n_in > PR_NIN_MAX) return stein_fail(STEIN_E_UNSUPPORTED, "more than %d input features", PR_NIN_MAX);
   if (n_hidden > PR_WIDTH_MAX) return stein_fail(STEIN_E_UNSUPPORTED, "more than 1024 hidden units");
@@ -416,19 +631,62 @@ extern "C" int stein_predict_bnn(const float* theta, int64_t n, int64_t d, int64
       if (cols[i] < cols[j] + len[j] && cols[j] < cols[i] + len[i]) return stein_fail(STEIN_E_SHAPE, "blocks %d and %d overlap", j, i);
   }
   const bool summary = mean || var || lpd;
-  if (int rc = predict_check_ws(n, batch, summary, workspace, ws_bytes)) return rc;
+  if (int rc = predict_check_ws(n, batch, summary || pw.ess, workspace, ws_bytes, pw)) return rc;
   const PredPlan pl = predict_plan(n, batch);
   const PredCols c = {(int)cols[0], (int)cols[1], (int)cols[2], (int)cols[3], (int)cols[5]};
   hipStream_t s = (hipStream_t)stream;
+  if (pw.on && (summary || pw.ess))
+    if (int rc = predict_weight_pass(pl, n, pw, workspace, s)) return rc;
+  if (!pred && !summary) return STEIN_OK;   // ess alone
+  float* part = summary ? predict_states(pl, workspace, pw) : nullptr;
+  const double* head = (pw.on && summary) ? (const double*)workspace : nullptr;
+#define PR_LAUNCH_BNN_AS(NIN, WEIGHTED)                                                                                 \
+  hipLaunchKernelGGL((k_predict_bnn<NIN, WEIGHTED>), dim3((unsigned)pl.row_tiles, (unsigned)pl.slices), dim3(256), 0, s, \
+                     theta, (int)n, (int)d, (int)n_hidden, c, X, y, (int)batch, pl.per, pred, part,                      \
+                     (mean || var) ? 1 : 0, lpd ? 1 : 0, pw.w, head)
 #define PR_LAUNCH_BNN(NIN)                                                                                              \
-  hipLaunchKernelGGL((k_predict_bnn<NIN>), dim3((unsigned)pl.row_tiles, (unsigned)pl.slices), dim3(256), 0, s, theta,    \
-                     (int)n, (int)d, (int)n_hidden, c, X, y, (int)batch, pl.per, pred,                                   \
-                     summary ? (float*)workspace : nullptr, (mean || var) ? 1 : 0, lpd ? 1 : 0)
+  do {                                                                                                                  \
+    if (head) PR_LAUNCH_BNN_AS(NIN, true);                                                                              \
+    else PR_LAUNCH_BNN_AS(NIN, false);                                                                                  \
+  } while (0)
   if (n_in == 1) PR_LAUNCH_BNN(1);
   else if (n_in == 2) PR_LAUNCH_BNN(2);
   else if (n_in == 3) PR_LAUNCH_BNN(3);
   else PR_LAUNCH_BNN(4);
 #undef PR_LAUNCH_BNN
+#undef PR_LAUNCH_BNN_AS
   LAUNCH_CHECK("k_predict_bnn");
-  return summary ? predict_finish(pl, n, batch, (const float*)workspace, mean, var, lpd, s) : STEIN_OK;
+  return summary ? predict_finish(pl, n, batch, part, mean, var, lpd, head, s) : STEIN_OK;
+}
+
+extern "C" int stein_predict_glm(const float* theta, int64_t n, int64_t d, int kind, int output, int64_t w_col,
+                                 int64_t n_feats, const float* X, const float* y, int64_t batch, double noise_precision,
+                                 float* pred, float* mean, float* var, float* lpd, void* workspace, size_t ws_bytes,
+                                 void* stream) {
+  return predict_glm(theta, n, d, kind, output, w_col, n_feats, X, y, batch, noise_precision, pred, mean, var, lpd, workspace,
+                     ws_bytes, stream, PredWeights{false, nullptr, nullptr});
+}
+
+extern "C" int stein_predict_glm_weighted(const float* theta, int64_t n, int64_t d, int kind, int output, int64_t w_col,
+                                          int64_t n_feats, const float* X, const float* y, int64_t batch,
+                                          double noise_precision, const double* weights, float* pred, float* mean, float* var,
+                                          float* lpd, double* ess, void* workspace, size_t ws_bytes, void* stream) {
+  return predict_glm(theta, n, d, kind, output, w_col, n_feats, X, y, batch, noise_precision, pred, mean, var, lpd, workspace,
+                     ws_bytes, stream, PredWeights{true, weights, ess});
+}
+
+extern "C" int stein_predict_bnn(const float* theta, int64_t n, int64_t d, int64_t n_in, int64_t n_hidden,
+                                 const int64_t* cols /*[6]: w1, b1, w2, b2, log_lambda, log_gamma*/, int output,
+                                 const float* X, const float* y, int64_t batch, float* pred, float* mean, float* var,
+                                 float* lpd, void* workspace, size_t ws_bytes, void* stream) {
+  return predict_bnn(theta, n, d, n_in, n_hidden, cols, output, X, y, batch, pred, mean, var, lpd, workspace, ws_bytes, stream,
+                     PredWeights{false, nullptr, nullptr});
+}
+
+extern "C" int stein_predict_bnn_weighted(const float* theta, int64_t n, int64_t d, int64_t n_in, int64_t n_hidden,
+                                          const int64_t* cols, int output, const float* X, const float* y, int64_t batch,
+                                          const double* weights, float* pred, float* mean, float* var, float* lpd,
+                                          double* ess, void* workspace, size_t ws_bytes, void* stream) {
+  return predict_bnn(theta, n, d, n_in, n_hidden, cols, output, X, y, batch, pred, mean, var, lpd, workspace, ws_bytes, stream,
+                     PredWeights{true, weights, ess});
 }

@@ -8,7 +8,10 @@ hand-written HIP kernels (csrc/stein_predict.hip) in two forms:
 * ``producer(theta_matrix, feed)`` -> the [n, batch] outputs, a device tensor: a valid ``function_posterior`` callable;
 * ``producer.summary(theta_matrix, feed)`` -> (mean, var, lpd) per test point, device tensors of [batch]: the ensemble
   mean and variance of the outputs and the log predictive density log(1/n sum_p p(y_b | theta_p)), without ever
-  materialising [n, batch].  ``SteinSampler.posterior_predictive`` hands these back as NumPy.
+  materialising [n, batch].  ``SteinSampler.posterior_predictive`` hands these back as NumPy;
+* ``producer.weighted_summary(theta_matrix, feed, weights)`` -> (mean, var, lpd, ess): the same summaries under per-particle
+  weights -- ``sampler.importance_weights(...)`` or the counts of ``sampler.thin(...)`` -- and the weights' effective sample
+  size (``posterior_predictive(..., weights=w)``).
 """
 import ctypes
 
@@ -34,6 +37,7 @@ class _Predict:
         self.output = _OUTPUTS[output]
         self._width = int(width)      # columns of feed["X"]
         self._ws = None
+        self._wws = None              # the workspace of weighted_summary: the weight pass's sums ahead of the states
 
     def _workspace(self, n, batch, device):
         need = _lib.predict_workspace_bytes(n, batch)
@@ -83,6 +87,32 @@ class _Predict:
         self._launch(theta, X, y, batch, None, mean, var, out_lpd, self._workspace(theta.shape[0], batch, theta.device))
         return mean, var, out_lpd
 
+    def weighted_summary(self, theta, feed, weights, lpd=None):
+        """-> (mean, var, lpd or None, ess) under per-particle weights w_p >= 0 (Stein importance weights, or the counts
+        ``torch.bincount(idx, minlength=n)`` of a thinned sample; they need not sum to 1): mean_b = sum_p w_p f_pb / W and
+        so on, ess = W^2 / sum_p w_p^2 as a 1-element float64 device tensor.  `weights`: any real-valued [n] tensor or
+        NumPy array; it is moved to the particles' device as contiguous float64 and never read on the host, so a negative
+        or non-finite weight (or W = 0) shows as NaN in every result."""
+        if lpd is None:
+            lpd = feed.get("y") is not None
+        X, y, batch = self._inputs(theta, feed, bool(lpd))
+        n = theta.shape[0]
+        w = torch.as_tensor(weights)
+        if w.dtype == torch.bool or w.is_complex():
+            raise ValueError("weights must be real-valued, not %s" % w.dtype)
+        if w.dim() != 1 or w.shape[0] != n:
+            raise ValueError("weights must be [%d], one per particle" % n)
+        w = w.to(device=theta.device, dtype=torch.float64).contiguous()
+        mean = torch.empty(batch, dtype=torch.float32, device=theta.device)
+        var = torch.empty_like(mean)
+        out_lpd = torch.empty_like(mean) if lpd else None
+        ess = torch.empty(1, dtype=torch.float64, device=theta.device)
+        need = _lib.predict_weighted_workspace_bytes(n, batch)
+        if self._wws is None or self._wws.device != theta.device or self._wws.numel() < need:
+            self._wws = torch.empty(need, dtype=torch.uint8, device=theta.device)
+        self._launch(theta, X, y, batch, None, mean, var, out_lpd, self._wws, weights=w, ess=ess)
+        return mean, var, out_lpd, ess
+
     @staticmethod
     def _ptr(t):
         return None if t is None else t.data_ptr()
@@ -106,11 +136,13 @@ class GlmPredict(_Predict):
         self.n_feats, self.w_col = int(n_feats), int(w_col)
         self.noise_precision = float(noise_precision)
 
-    def _launch(self, theta, X, y, batch, pred, mean, var, lpd, ws):
+    def _launch(self, theta, X, y, batch, pred, mean, var, lpd, ws, weights=None, ess=None):
         n, d = theta.shape
-        _lib.call_on(theta.device, "stein_predict_glm", theta.data_ptr(), n, d, self.kind, self.output, self.w_col, self.n_feats,
-                     X.data_ptr(), self._ptr(y), batch, self.noise_precision, self._ptr(pred), self._ptr(mean), self._ptr(var),
-                     self._ptr(lpd), self._ptr(ws), 0 if ws is None else ws.numel(),
+        name, w, e = ("stein_predict_glm", (), ()) if weights is None else \
+            ("stein_predict_glm_weighted", (weights.data_ptr(),), (ess.data_ptr(),))
+        _lib.call_on(theta.device, name, theta.data_ptr(), n, d, self.kind, self.output, self.w_col, self.n_feats,
+                     X.data_ptr(), self._ptr(y), batch, self.noise_precision, *w, self._ptr(pred), self._ptr(mean),
+                     self._ptr(var), self._ptr(lpd), *e, self._ptr(ws), 0 if ws is None else ws.numel(),
                      torch.cuda.current_stream(theta.device).cuda_stream)
 
 
@@ -125,8 +157,10 @@ class BnnPredict(_Predict):
         self.n_in, self.n_hidden = int(n_in), int(n_hidden)
         self._cols = (ctypes.c_int64 * 6)(*[int(c) for c in cols])
 
-    def _launch(self, theta, X, y, batch, pred, mean, var, lpd, ws):
+    def _launch(self, theta, X, y, batch, pred, mean, var, lpd, ws, weights=None, ess=None):
         n, d = theta.shape
-        _lib.call_on(theta.device, "stein_predict_bnn", theta.data_ptr(), n, d, self.n_in, self.n_hidden, self._cols, self.output,
-                     X.data_ptr(), self._ptr(y), batch, self._ptr(pred), self._ptr(mean), self._ptr(var), self._ptr(lpd),
-                     self._ptr(ws), 0 if ws is None else ws.numel(), torch.cuda.current_stream(theta.device).cuda_stream)
+        name, w, e = ("stein_predict_bnn", (), ()) if weights is None else \
+            ("stein_predict_bnn_weighted", (weights.data_ptr(),), (ess.data_ptr(),))
+        _lib.call_on(theta.device, name, theta.data_ptr(), n, d, self.n_in, self.n_hidden, self._cols, self.output,
+                     X.data_ptr(), self._ptr(y), batch, *w, self._ptr(pred), self._ptr(mean), self._ptr(var), self._ptr(lpd),
+                     *e, self._ptr(ws), 0 if ws is None else ws.numel(), torch.cuda.current_stream(theta.device).cuda_stream)

@@ -304,21 +304,31 @@ class AbstractSteinSampler:
             return self.theta_matrix
         return self._theta_f32() if self.kernel_dtype == torch.float32 else self.theta_matrix.float()
 
-    def posterior_predictive(self, producer, feed):
+    def posterior_predictive(self, producer, feed, weights=None):
         """Per-test-point ensemble summaries of a predictive producer (stein_amd.predict.GlmPredict / BnnPredict) under
         the current particles: {"mean", "var"} of its outputs over the particles and, when `feed` has a "y", "lpd", the log
         predictive density log(1/n sum_p p(y_b | theta_p)) -- NumPy arrays of [batch].  The [n, batch] matrix that
-        function_posterior returns is never formed; only the three vectors cross to the host.  One rank only."""
+        function_posterior returns is never formed; only the three vectors cross to the host.  One rank only.
+
+        weights ([n], w_p >= 0: ``importance_weights(...)``, or ``torch.bincount(thin(m), minlength=n)``): the summaries
+        under these weights, sum_p w_p (.) / sum_p w_p in place of 1/n sum_p (.), and "ess", the weights' effective
+        sample size (sum w)^2 / sum w^2, a float.  A bad weight vector (a negative or non-finite entry, all zero) gives NaN."""
         if self._group is not None:
             raise ValueError("posterior_predictive works on one rank only: a sharded sampler would have to merge the "
                              "ranks' states; use function_posterior, which gathers the outputs")
         if not hasattr(producer, "summary"):
             raise ValueError("posterior_predictive needs a predictive producer (GlmPredict / BnnPredict)")
+        ess = None
         with torch.no_grad():
-            mean, var, lpd = producer.summary(self._matrix_f32(), feed)
+            if weights is None:
+                mean, var, lpd = producer.summary(self._matrix_f32(), feed)
+            else:
+                mean, var, lpd, ess = producer.weighted_summary(self._matrix_f32(), feed, weights)
         out = {"mean": mean.cpu().numpy(), "var": var.cpu().numpy()}
         if lpd is not None:
             out["lpd"] = lpd.cpu().numpy()
+        if ess is not None:
+            out["ess"] = float(ess.item())
         return out
 
     def samples_all(self):
