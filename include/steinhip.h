@@ -726,6 +726,36 @@ int stein_predict_bnn_weighted(const float* theta, int64_t n, int64_t d, int64_t
                                const double* weights, float* pred, float* mean, float* var, float* lpd, double* ess,
                                void* workspace, size_t ws_bytes, void* stream);
 
+/* Order statistics of the outputs: credible bands and the ensemble median per test point, without pred.
+ *   out [n_ranks][batch]   out[i][b] = the ranks[i]-th smallest (0-based) of the n values f_pb, p = 0 .. n-1
+ * with f_pb bit for bit what stein_predict_glm / stein_predict_bnn write to pred for the same arguments (one body of device
+ * code computes both).  The result is exact -- an element of the column pred would have held -- not a sketch.  The order is
+ * numeric with -0 before +0; every NaN, of either sign, sorts last (as in torch.sort) and comes back as a quiet NaN.
+ * ranks: a HOST array of n_ranks integers in [0, n), in any order, repeats allowed; read before the call returns.  A rank's
+ * row does not depend on which other ranks share the call.  At most STEIN_PRED_RANKS_MAX ranks per call.
+ * Method: a radix select over the 32-bit order-preserving keys of the outputs, 4 bits per level: the forward pass runs 8
+ * times and counts digits; nothing of size n is stored.  The only values summed across workgroups are integer counts
+ * (integer atomics), so a repeated call is bit-identical and the result depends neither on the grid nor on the particle
+ * slices.  The host never reads device memory and never synchronises; every launch goes on `stream`.
+ * Workspace: stein_predict_ranks_workspace_bytes = 76 bytes per (row, rank) -- the key prefix, the remaining rank, the rank
+ * whose counts it shares, 16 counts -- so 76 * batch * n_ranks: independent of n and d, 4-byte aligned.  It may hold
+ * anything on entry and carries nothing from call to call.
+ * Refused before any launch, in this order: a NULL pointer (theta, X, ranks, out, cols, out_bytes) or n_ranks < 1
+ * (STEIN_E_BADARG); then the output, shape, kind, column and width checks of stein_predict_* with their codes and messages;
+ * n_ranks > STEIN_PRED_RANKS_MAX (STEIN_E_UNSUPPORTED); a rank outside [0, n) (STEIN_E_BADARG); no workspace, too small a
+ * one or a misaligned one (STEIN_E_WORKSPACE). */
+enum { STEIN_PRED_RANKS_MAX = 8 };
+int stein_predict_ranks_workspace_bytes(int64_t n, int64_t batch, int64_t n_ranks, size_t* out_bytes);
+int stein_predict_glm_ranks(const float* theta, int64_t n, int64_t d, int kind, int output, int64_t w_col, int64_t n_feats,
+                            const float* X, int64_t batch, const int64_t* ranks /* host */, int64_t n_ranks,
+                            float* out /* [n_ranks][batch] */, void* workspace, size_t ws_bytes, void* stream);
+int stein_predict_bnn_ranks(const float* theta, int64_t n, int64_t d, int64_t n_in, int64_t n_hidden, const int64_t* cols,
+                            int output, const float* X, int64_t batch, const int64_t* ranks, int64_t n_ranks,
+                            float* out, void* workspace, size_t ws_bytes, void* stream);
+/* test hook, per calling thread: the ranks calls cut the particles into `slices` slices (1 .. 1024; never less than one pass
+ * of 16 particles per slice) instead of the summary calls' plan; 0 = default.  No bit of the result depends on it. */
+int stein_debug_predict_ranks_slices(int slices);
+
 /* small helpers used by the host layer */
 int stein_cast_f64_to_f32(const double* src, float* dst, int64_t count, void* stream);
 int stein_cast_f32_to_bf16(const float* src, void* dst, int64_t count, void* stream);

@@ -134,30 +134,19 @@ __device__ __forceinline__ void pred_store_state(const PredState& st, float* __r
   }
 }
 
-// fc = features per chunk (F when the whole tile fits, else PR_FC), ld = floats per staged row of X (odd: lane t reads
-// xs[t * ld + f], 64 different banks).  WEIGHTED: wts [n] the weights, head the weight pass's header (head[0] = W); the
-// pass's PR_PASS normalised weights are staged behind ws.
-template <bool WEIGHTED>
-__global__ __launch_bounds__(256) void k_predict_glm(const float* __restrict__ theta, int n, int d, int kind, int output,
-                                                     int w_col, int F, int fc, int ld, const float* __restrict__ X,
-                                                     const float* __restrict__ y, int B, int per, float half_tau, float c0,
-                                                     float* __restrict__ pred, float* __restrict__ part, int want_mv,
-                                                     int want_lpd, const double* __restrict__ wts,
-                                                     const double* __restrict__ head) {
-  extern __shared__ float lds[];
-  float* xs = lds;                   // [PR_ROWS][ld]
-  float* ws = lds + PR_ROWS * ld;    // [fc][PR_PASS]
-  float* wl = ws + fc * PR_PASS;     // [PR_PASS], WEIGHTED only
-  float wk = 0.f;
-  const double wtot = WEIGHTED ? head[0] : 0.0;
-  const int t = threadIdx.x;
-  const int row0 = blockIdx.x * PR_ROWS, row = row0 + t;
-  const bool live = row < B;
-  const int p_begin = blockIdx.y * per, p_end = min(n, p_begin + per);
+// ---- the forward passes, shared by the summary kernels and the rank-counting kernels of stein_predict_ranks.hip: one body
+// of device code, so a counted value is bit for bit the value pred holds.
+// GLM: the walk of one workgroup over its slice [p_begin, p_end) of the particles, PR_PASS at a time.  fc = features per
+// chunk (F when the whole X tile fits, else PR_FC), ld = floats per staged row of X (odd: lane t reads xs[t * ld + f], 64
+// different banks); xs [PR_ROWS][ld] and ws [fc][PR_PASS] in LDS.  z[k] = x_row . w_(p0 + k) is summed over the features in
+// order whatever the chunking.  between(p0, cnt): what the caller stages beside the first chunk's weights of a pass, between
+// the two barriers; consume(p0, k, z): the lane's linear output of particle p0 + k, in particle order.  (z stays a local of
+// this function: handed to a helper by reference, the inner loop came out with its LDS reads serialised, 7 % slower.)
+template <class Between, class Consume>
+__device__ __forceinline__ void pred_glm_slice(const float* theta, int d, int w_col, int F, int fc, int ld, const float* X, int B,
+                                               int row0, int p_begin, int p_end, float* xs, float* ws, int t, Between&& between,
+                                               Consume&& consume) {
   const int nfc = (F + fc - 1) / fc;
-  const bool logistic = kind == STEIN_GLM_LOGISTIC, sigmoid = logistic && output == STEIN_PRED_MEAN;
-  const float yb = (want_lpd && live) ? y[row] : 0.f;
-  PredState st = {0.f, 0.f, 0.f, 0.f, 0.f};
   auto stage_x = [&](int f0, int len) {   // rows past the batch are staged as zeros
     for (int i = t; i < PR_ROWS * len; i += 256) {
       const int r = i / len, f = i - r * len;
@@ -178,7 +167,7 @@ __global__ __launch_bounds__(256) void k_predict_glm(const float* __restrict__ t
         const int k = i / len, f = i - k * len;
         ws[f * PR_PASS + k] = k < cnt ? theta[(size_t)(p0 + k) * d + w_col + f0 + f] : 0.f;
       }
-      if (WEIGHTED && c == 0 && t < PR_PASS) wl[t] = t < cnt ? pred_norm_weight(wts[p0 + t], wtot) : 0.f;
+      if (c == 0) between(p0, cnt);
       __syncthreads();
       const float* xr = xs + t * ld;
 #pragma unroll 2
@@ -196,10 +185,43 @@ __global__ __launch_bounds__(256) void k_predict_glm(const float* __restrict__ t
       }
     }
 #pragma unroll
-    for (int k = 0; k < PR_PASS; ++k) {
-      if (k < cnt) {   // a particle past the slice's end is no particle: it is not counted as f = 0
-        const float zz = z[k];
-        const float f = sigmoid ? 1.f / (1.f + expf(-zz)) : zz;
+    for (int k = 0; k < PR_PASS; ++k)
+      if (k < cnt) consume(p0, k, z[k]);   // a particle past the slice's end is no particle: it is not counted as f = 0
+  }
+}
+
+// the reported output of a GLM particle from its linear output
+__device__ __forceinline__ float pred_glm_output(float zz, bool sigmoid) { return sigmoid ? 1.f / (1.f + expf(-zz)) : zz; }
+
+// WEIGHTED: wts [n] the weights, head the weight pass's header (head[0] = W); the pass's PR_PASS normalised weights are
+// staged behind ws.
+template <bool WEIGHTED>
+__global__ __launch_bounds__(256) void k_predict_glm(const float* __restrict__ theta, int n, int d, int kind, int output,
+                                                     int w_col, int F, int fc, int ld, const float* __restrict__ X,
+                                                     const float* __restrict__ y, int B, int per, float half_tau, float c0,
+                                                     float* __restrict__ pred, float* __restrict__ part, int want_mv,
+                                                     int want_lpd, const double* __restrict__ wts,
+                                                     const double* __restrict__ head) {
+  extern __shared__ float lds[];
+  float* xs = lds;                   // [PR_ROWS][ld]
+  float* ws = lds + PR_ROWS * ld;    // [fc][PR_PASS]
+  float* wl = ws + fc * PR_PASS;     // [PR_PASS], WEIGHTED only
+  float wk = 0.f;
+  const double wtot = WEIGHTED ? head[0] : 0.0;
+  const int t = threadIdx.x;
+  const int row0 = blockIdx.x * PR_ROWS, row = row0 + t;
+  const bool live = row < B;
+  const int p_begin = blockIdx.y * per, p_end = min(n, p_begin + per);
+  const bool logistic = kind == STEIN_GLM_LOGISTIC, sigmoid = logistic && output == STEIN_PRED_MEAN;
+  const float yb = (want_lpd && live) ? y[row] : 0.f;
+  PredState st = {0.f, 0.f, 0.f, 0.f, 0.f};
+  pred_glm_slice(
+      theta, d, w_col, F, fc, ld, X, B, row0, p_begin, p_end, xs, ws, t,
+      [&](int p0, int cnt) {
+        if (WEIGHTED && t < PR_PASS) wl[t] = t < cnt ? pred_norm_weight(wts[p0 + t], wtot) : 0.f;
+      },
+      [&](int p0, int k, float zz) {
+        const float f = pred_glm_output(zz, sigmoid);
         if (pred && live) pred[(size_t)(p0 + k) * B + row] = f;
         float l = 0.f;
         if (want_lpd) {
@@ -212,22 +234,79 @@ __global__ __launch_bounds__(256) void k_predict_glm(const float* __restrict__ t
         }
         if constexpr (WEIGHTED) pred_accumulate_weighted(st, wk, wl[k], f, l, want_mv, want_lpd);
         else pred_accumulate(st, p0 - p_begin + k, f, l, want_mv, want_lpd);
-      }
-    }
-  }
+      });
   if (live && part) pred_store_state(st, part, blockIdx.y, B, row, want_mv, want_lpd);
 }
 
-// NIN input features in registers per lane; the PR_PASS staged particles' b1, w2 and w1 rows of a chunk of PR_HC hidden
-// units in LDS (hidden units past H are staged as zeros: relu(0) * 0 adds an exact zero)
+// Network: z[k] of the cnt particles from p0 WITHOUT b2 (z comes in as zeros; f = z[k] + lp[k][0]).  x: the lane's NIN input
+// features in registers; lw: the PR_PASS staged particles' b1, w2 and w1 rows of a chunk of PR_HC hidden units (hidden units
+// past H are staged as zeros: relu(0) * 0 adds an exact zero); lp per particle: b2, 1/2 lg - 1/2 log 2 pi, 1/2 e^lg, and
+// what extra(t) puts into lp[t][3] beside them (called by the thread that stages particle p0 + t).
+template <int NIN>
+constexpr int PR_BNN_PW = (NIN + 2) * PR_HC;   // staged floats per particle: b1 [PR_HC], w2 [PR_HC], w1 [NIN][PR_HC]
+
+template <int NIN, class Extra>
+__device__ __forceinline__ void pred_bnn_pass(float (&z)[PR_PASS], const float* theta, int d, int H,
+                                              const PredCols& c, const float (&x)[NIN], int p0, int cnt,
+                                              float* lw, float (*lp)[4], int t, Extra&& extra) {
+  constexpr int PW = PR_BNN_PW<NIN>;
+  for (int h0 = 0; h0 < H; h0 += PR_HC) {
+    const int len = min(PR_HC, H - h0), len4 = (len + 3) & ~3;
+    __syncthreads();   // every lane is past its last read of lw and lp
+    for (int i = t; i < PR_PASS * len4; i += 256) {
+      const int k = i / len4, h = i - k * len4;
+      const bool ok = k < cnt && h < len;
+      const float* th = theta + (size_t)(p0 + (ok ? k : 0)) * d + h0 + h;
+      float* dst = lw + k * PW + h;
+      dst[0] = ok ? th[c.b1] : 0.f;
+      dst[PR_HC] = ok ? th[c.w2] : 0.f;
+#pragma unroll
+      for (int f = 0; f < NIN; ++f) dst[(2 + f) * PR_HC] = ok ? th[c.w1 + f * H] : 0.f;
+    }
+    if (h0 == 0 && t < cnt) {
+      const float* th = theta + (size_t)(p0 + t) * d;
+      const float lg = th[c.loggam];
+      lp[t][0] = th[c.b2];
+      lp[t][1] = fmaf(0.5f, lg, -PR_HALF_LOG_2PI);
+      lp[t][2] = 0.5f * expf(lg);
+      extra(t);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < PR_PASS; ++k) {
+      if (k < cnt) {
+        const float* wk = lw + k * PW;
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+#pragma unroll 2
+        for (int h = 0; h < len4; h += 4) {
+          float4 v = *reinterpret_cast<const float4*>(wk + h);
+          const float4 w2 = *reinterpret_cast<const float4*>(wk + PR_HC + h);
+#pragma unroll
+          for (int f = 0; f < NIN; ++f) {
+            const float4 w1 = *reinterpret_cast<const float4*>(wk + (2 + f) * PR_HC + h);
+            v.x = fmaf(x[f], w1.x, v.x);
+            v.y = fmaf(x[f], w1.y, v.y);
+            v.z = fmaf(x[f], w1.z, v.z);
+            v.w = fmaf(x[f], w1.w, v.w);
+          }
+          a0 = fmaf(fmaxf(v.x, 0.f), w2.x, a0);
+          a1 = fmaf(fmaxf(v.y, 0.f), w2.y, a1);
+          a2 = fmaf(fmaxf(v.z, 0.f), w2.z, a2);
+          a3 = fmaf(fmaxf(v.w, 0.f), w2.w, a3);
+        }
+        z[k] += (a0 + a1) + (a2 + a3);
+      }
+    }
+  }
+}
+
 template <int NIN, bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_predict_bnn(const float* __restrict__ theta, int n, int d, int H, PredCols c,
                                                      const float* __restrict__ X, const float* __restrict__ y, int B, int per,
                                                      float* __restrict__ pred, float* __restrict__ part, int want_mv,
                                                      int want_lpd, const double* __restrict__ wts,
                                                      const double* __restrict__ head) {
-  constexpr int PW = (NIN + 2) * PR_HC;   // staged floats per particle: b1 [PR_HC], w2 [PR_HC], w1 [NIN][PR_HC]
-  __shared__ __attribute__((aligned(16))) float lw[PR_PASS * PW];
+  __shared__ __attribute__((aligned(16))) float lw[PR_PASS * PR_BNN_PW<NIN>];
   __shared__ float lp[PR_PASS][4];        // per particle: b2, 1/2 lg - 1/2 log 2 pi, 1/2 e^lg; WEIGHTED: its normalised weight
   float wk = 0.f;
   const double wtot = WEIGHTED ? head[0] : 0.0;
@@ -245,54 +324,9 @@ __global__ __launch_bounds__(256) void k_predict_bnn(const float* __restrict__ t
     float z[PR_PASS];
 #pragma unroll
     for (int k = 0; k < PR_PASS; ++k) z[k] = 0.f;
-    for (int h0 = 0; h0 < H; h0 += PR_HC) {
-      const int len = min(PR_HC, H - h0), len4 = (len + 3) & ~3;
-      __syncthreads();   // every lane is past its last read of lw and lp
-      for (int i = t; i < PR_PASS * len4; i += 256) {
-        const int k = i / len4, h = i - k * len4;
-        const bool ok = k < cnt && h < len;
-        const float* th = theta + (size_t)(p0 + (ok ? k : 0)) * d + h0 + h;
-        float* dst = lw + k * PW + h;
-        dst[0] = ok ? th[c.b1] : 0.f;
-        dst[PR_HC] = ok ? th[c.w2] : 0.f;
-#pragma unroll
-        for (int f = 0; f < NIN; ++f) dst[(2 + f) * PR_HC] = ok ? th[c.w1 + f * H] : 0.f;
-      }
-      if (h0 == 0 && t < cnt) {
-        const float* th = theta + (size_t)(p0 + t) * d;
-        const float lg = th[c.loggam];
-        lp[t][0] = th[c.b2];
-        lp[t][1] = fmaf(0.5f, lg, -PR_HALF_LOG_2PI);
-        lp[t][2] = 0.5f * expf(lg);
-        if (WEIGHTED) lp[t][3] = pred_norm_weight(wts[p0 + t], wtot);
-      }
-      __syncthreads();
-#pragma unroll
-      for (int k = 0; k < PR_PASS; ++k) {
-        if (k < cnt) {
-          const float* wk = lw + k * PW;
-          float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-#pragma unroll 2
-          for (int h = 0; h < len4; h += 4) {
-            float4 v = *reinterpret_cast<const float4*>(wk + h);
-            const float4 w2 = *reinterpret_cast<const float4*>(wk + PR_HC + h);
-#pragma unroll
-            for (int f = 0; f < NIN; ++f) {
-              const float4 w1 = *reinterpret_cast<const float4*>(wk + (2 + f) * PR_HC + h);
-              v.x = fmaf(x[f], w1.x, v.x);
-              v.y = fmaf(x[f], w1.y, v.y);
-              v.z = fmaf(x[f], w1.z, v.z);
-              v.w = fmaf(x[f], w1.w, v.w);
-            }
-            a0 = fmaf(fmaxf(v.x, 0.f), w2.x, a0);
-            a1 = fmaf(fmaxf(v.y, 0.f), w2.y, a1);
-            a2 = fmaf(fmaxf(v.z, 0.f), w2.z, a2);
-            a3 = fmaf(fmaxf(v.w, 0.f), w2.w, a3);
-          }
-          z[k] += (a0 + a1) + (a2 + a3);
-        }
-      }
-    }
+    pred_bnn_pass<NIN>(z, theta, d, H, c, x, p0, cnt, lw, lp, t, [&](int k) {
+      if (WEIGHTED) lp[k][3] = pred_norm_weight(wts[p0 + k], wtot);
+    });
 #pragma unroll
     for (int k = 0; k < PR_PASS; ++k) {
       if (k < cnt) {
@@ -417,6 +451,53 @@ __global__ __launch_bounds__(256) void k_predict_finish(const float* __restrict_
   if (lpd) lpd[b] = WEIGHTED ? (float)(top + log(sum)) : (float)(top + log(sum) - log((double)n));
 }
 
+// ---- host-side pieces that stein_predict_ranks.hip shares (it includes this file with STEIN_PREDICT_SHARED_ONLY: every
+// line above this one and these, nothing below) ---------------------------------------------------------
+struct PredPlan { int row_tiles, slices, per; };
+
+static PredPlan predict_plan(int64_t n, int64_t batch) {
+  PredPlan p;
+  p.row_tiles = (int)((batch + PR_ROWS - 1) / PR_ROWS);
+  int64_t s = (PR_TARGET_WGS + p.row_tiles - 1) / p.row_tiles;   // slices that fill the card at this batch
+  if (s > PR_SLICE_CAP) s = PR_SLICE_CAP;
+  const int64_t passes = (n + PR_PASS - 1) / PR_PASS;            // no slice of less than one pass
+  if (s > passes) s = passes;
+  p.per = (int)((n + s - 1) / s);
+  p.slices = (int)((n + p.per - 1) / p.per);
+  return p;
+}
+
+// the weights of a weighted call (on = false: an unweighted call, for which every check and launch is what it was)
+struct PredWeights { bool on; const double* w; double* ess; };
+
+// the checks the entry points share, in the order the header lists them
+static int predict_check(const float* theta, const float* X, const float* y, int64_t n, int64_t d, int64_t batch,
+                         int64_t width, int output, const float* pred, const float* mean, const float* var,
+                         const float* lpd, const PredWeights& pw) {
+  if (!theta || !X || (pw.on && !pw.w)) return stein_fail(STEIN_E_BADARG, "NULL pointer");
+  if (!pred && !mean && !var && !lpd && !pw.ess)
+    return stein_fail(STEIN_E_BADARG, pw.on ? "no output requested: pred, mean, var, lpd and ess are all NULL"
+                                            : "no output requested: pred, mean, var and lpd are all NULL");
+  if (lpd && !y) return stein_fail(STEIN_E_BADARG, "lpd needs y");
+  if (output != STEIN_PRED_LINK && output != STEIN_PRED_MEAN) return stein_fail(STEIN_E_BADARG, "output %d", output);
+  if (n < 1 || d < 1 || batch < 1 || width < 1 || n > PR_COUNT_MAX || d > 0x7fffffffl || batch > PR_COUNT_MAX)
+    return stein_fail(STEIN_E_SHAPE, "bad shape n=%lld d=%lld batch=%lld width=%lld", (long long)n, (long long)d,
+                      (long long)batch, (long long)width);
+  return STEIN_OK;
+}
+
+// the network's six column blocks fit d and do not overlap
+static int predict_check_cols(const int64_t* cols, int64_t n_in, int64_t n_hidden, int64_t d) {
+  const int64_t len[6] = {n_in * n_hidden, n_hidden, n_hidden, 1, 1, 1};
+  for (int i = 0; i < 6; ++i) {
+    if (cols[i] < 0 || cols[i] + len[i] > d) return stein_fail(STEIN_E_SHAPE, "block %d does not fit d=%lld", i, (long long)d);
+    for (int j = 0; j < i; ++j)
+      if (cols[i] < cols[j] + len[j] && cols[j] < cols[i] + len[i]) return stein_fail(STEIN_E_SHAPE, "blocks %d and %d overlap", j, i);
+  }
+  return STEIN_OK;
+}
+
+#ifndef STEIN_PREDICT_SHARED_ONLY
 // ---- the weight pass of a weighted call ------------------------------------------------------------------
 // 256 partial results per quantity folded by halving, in a fixed order: quantities 0 and 1 are sums, 2 is a maximum
 __device__ __forceinline__ void pw_fold(double (*sh)[256], int t, int quantities) {
@@ -477,20 +558,6 @@ __global__ __launch_bounds__(256) void k_predict_wtotal(int slices, double* __re
 }
 
 // ---- host side -----------------------------------------------------------------------------------------
-struct PredPlan { int row_tiles, slices, per; };
-
-static PredPlan predict_plan(int64_t n, int64_t batch) {
-  PredPlan p;
-  p.row_tiles = (int)((batch + PR_ROWS - 1) / PR_ROWS);
-  int64_t s = (PR_TARGET_WGS + p.row_tiles - 1) / p.row_tiles;   // slices that fill the card at this batch
-  if (s > PR_SLICE_CAP) s = PR_SLICE_CAP;
-  const int64_t passes = (n + PR_PASS - 1) / PR_PASS;            // no slice of less than one pass
-  if (s > passes) s = passes;
-  p.per = (int)((n + s - 1) / s);
-  p.slices = (int)((n + p.per - 1) / p.per);
-  return p;
-}
-
 // An upper bound of the plan's slices * batch states, monotone in both arguments (the plan's own product is not: a row tile
 // more can cost slices).  slices <= passes, <= PR_SLICE_CAP, and <= PR_TARGET_WGS / row_tiles + 1 with row_tiles >= batch /
 // PR_ROWS, so slices * batch <= PR_TARGET_WGS * PR_ROWS + batch.
@@ -511,9 +578,6 @@ extern "C" int stein_predict_workspace_bytes(int64_t n, int64_t batch, size_t* o
   return STEIN_OK;
 }
 
-// the weights of a weighted call (on = false: an unweighted call, for which every check and launch is what it was)
-struct PredWeights { bool on; const double* w; double* ess; };
-
 static size_t predict_wws_bytes(int64_t n, int64_t batch) {   // the states behind the weight pass's header; monotone too
   int64_t s = (n + PR_PASS - 1) / PR_PASS;
   if (s > PR_SLICE_CAP) s = PR_SLICE_CAP;
@@ -525,22 +589,6 @@ extern "C" int stein_predict_weighted_workspace_bytes(int64_t n, int64_t batch, 
   if (n < 1 || batch < 1 || n > PR_COUNT_MAX || batch > PR_COUNT_MAX)
     return stein_fail(STEIN_E_SHAPE, "bad shape n=%lld batch=%lld", (long long)n, (long long)batch);
   *out_bytes = predict_wws_bytes(n, batch);
-  return STEIN_OK;
-}
-
-// the checks the entry points share, in the order the header lists them
-static int predict_check(const float* theta, const float* X, const float* y, int64_t n, int64_t d, int64_t batch,
-                         int64_t width, int output, const float* pred, const float* mean, const float* var,
-                         const float* lpd, const PredWeights& pw) {
-  if (!theta || !X || (pw.on && !pw.w)) return stein_fail(STEIN_E_BADARG, "NULL pointer");
-  if (!pred && !mean && !var && !lpd && !pw.ess)
-    return stein_fail(STEIN_E_BADARG, pw.on ? "no output requested: pred, mean, var, lpd and ess are all NULL"
-                                            : "no output requested: pred, mean, var and lpd are all NULL");
-  if (lpd && !y) return stein_fail(STEIN_E_BADARG, "lpd needs y");
-  if (output != STEIN_PRED_LINK && output != STEIN_PRED_MEAN) return stein_fail(STEIN_E_BADARG, "output %d", output);
-  if (n < 1 || d < 1 || batch < 1 || width < 1 || n > PR_COUNT_MAX || d > 0x7fffffffl || batch > PR_COUNT_MAX)
-    return stein_fail(STEIN_E_SHAPE, "bad shape n=%lld d=%lld batch=%lld width=%lld", (long long)n, (long long)d,
-                      (long long)batch, (long long)width);
   return STEIN_OK;
 }
 
@@ -624,12 +672,7 @@ static int predict_bnn(const float* theta, int64_t n, int64_t d, int64_t n_in, i
   if (n_in < 1) return stein_fail(STEIN_E_SHAPE, "bad shape n_in=%lld", (long long)n_in);
   if (n_in > PR_NIN_MAX) return stein_fail(STEIN_E_UNSUPPORTED, "more than %d input features", PR_NIN_MAX);
   if (n_hidden > PR_WIDTH_MAX) return stein_fail(STEIN_E_UNSUPPORTED, "more than 1024 hidden units");
-  const int64_t len[6] = {n_in * n_hidden, n_hidden, n_hidden, 1, 1, 1};
-  for (int i = 0; i < 6; ++i) {
-    if (cols[i] < 0 || cols[i] + len[i] > d) return stein_fail(STEIN_E_SHAPE, "block %d does not fit d=%lld", i, (long long)d);
-    for (int j = 0; j < i; ++j)
-      if (cols[i] < cols[j] + len[j] && cols[j] < cols[i] + len[i]) return stein_fail(STEIN_E_SHAPE, "blocks %d and %d overlap", j, i);
-  }
+  if (int rc = predict_check_cols(cols, n_in, n_hidden, d)) return rc;
   const bool summary = mean || var || lpd;
   if (int rc = predict_check_ws(n, batch, summary || pw.ess, workspace, ws_bytes, pw)) return rc;
   const PredPlan pl = predict_plan(n, batch);
@@ -690,3 +733,4 @@ extern "C" int stein_predict_bnn_weighted(const float* theta, int64_t n, int64_t
   return predict_bnn(theta, n, d, n_in, n_hidden, cols, output, X, y, batch, pred, mean, var, lpd, workspace, ws_bytes, stream,
                      PredWeights{true, weights, ess});
 }
+#endif  // STEIN_PREDICT_SHARED_ONLY

@@ -11,9 +11,13 @@ hand-written HIP kernels (csrc/stein_predict.hip) in two forms:
   materialising [n, batch].  ``SteinSampler.posterior_predictive`` hands these back as NumPy;
 * ``producer.weighted_summary(theta_matrix, feed, weights)`` -> (mean, var, lpd, ess): the same summaries under per-particle
   weights -- ``sampler.importance_weights(...)`` or the counts of ``sampler.thin(...)`` -- and the weights' effective sample
-  size (``posterior_predictive(..., weights=w)``).
+  size (``posterior_predictive(..., weights=w)``);
+* ``producer.order_statistics(theta_matrix, feed, ranks)`` / ``producer.quantiles(theta_matrix, feed, q)`` -> [len, batch]:
+  exact order statistics of the outputs over the particles per test point -- the ensemble median, credible bands -- again
+  without [n, batch] (``posterior_predictive(..., quantiles=(0.05, 0.5, 0.95))``).
 """
 import ctypes
+import math
 
 import torch
 
@@ -38,6 +42,7 @@ class _Predict:
         self._width = int(width)      # columns of feed["X"]
         self._ws = None
         self._wws = None              # the workspace of weighted_summary: the weight pass's sums ahead of the states
+        self._rws = None              # the workspace of order_statistics: 76 bytes per (row, rank of one call)
 
     def _workspace(self, n, batch, device):
         need = _lib.predict_workspace_bytes(n, batch)
@@ -113,6 +118,65 @@ class _Predict:
         self._launch(theta, X, y, batch, None, mean, var, out_lpd, self._wws, weights=w, ess=ess)
         return mean, var, out_lpd, ess
 
+    def order_statistics(self, theta, feed, ranks):
+        """-> [len(ranks), batch] float32 device tensor: row i holds, per test point, the ranks[i]-th smallest (0-based) of
+        the n outputs f_pb -- exactly the entry ``torch.sort(self(theta, feed), dim=0)`` has there (NaNs last), found by a
+        radix select that recomputes the forward pass and never forms [n, batch].  `ranks`: integers in [0, n), in any
+        order, repeats allowed; eight go into one call of the library, more are split over several calls."""
+        X, _, batch = self._inputs(theta, feed, False)
+        n = theta.shape[0]
+        ranks = [int(r) for r in ranks]
+        if not ranks:
+            raise ValueError("ranks must not be empty")
+        for r in ranks:
+            if not 0 <= r < n:
+                raise ValueError("rank %d is outside [0, %d)" % (r, n))
+        out = torch.empty(len(ranks), batch, dtype=torch.float32, device=theta.device)
+        need = _lib.predict_ranks_workspace_bytes(n, batch, min(len(ranks), _lib.PRED_RANKS_MAX))
+        if self._rws is None or self._rws.device != theta.device or self._rws.numel() < need:
+            self._rws = torch.empty(need, dtype=torch.uint8, device=theta.device)
+        for at in range(0, len(ranks), _lib.PRED_RANKS_MAX):
+            part = ranks[at:at + _lib.PRED_RANKS_MAX]
+            self._launch_ranks(theta, X, batch, (ctypes.c_int64 * len(part))(*part), len(part), out[at:at + len(part)],
+                               self._rws)
+        return out
+
+    def quantiles(self, theta, feed, q, interpolation="linear"):
+        """-> [len(q), batch] float32 device tensor: the q-quantiles of the n outputs per test point by NumPy's definition,
+        position q (n - 1) among the sorted outputs.  "linear": lo + (hi - lo) frac of the two neighbouring order statistics,
+        in fp32 on the device (a position that is an integer gives that order statistic itself); "lower" / "higher": the
+        neighbour below / above, exact.  Built on ``order_statistics``: no [n, batch] matrix."""
+        if interpolation not in ("linear", "lower", "higher"):
+            raise ValueError("interpolation must be 'linear', 'lower' or 'higher'")
+        q = [float(v) for v in q]
+        if not q:
+            raise ValueError("q must not be empty")
+        n = theta.shape[0]
+        ranks, plan = [], []
+        for v in q:
+            if not 0.0 <= v <= 1.0:       # NaN too
+                raise ValueError("quantiles must lie in [0, 1], not %r" % v)
+            pos = v * (n - 1)
+            lo = min(int(math.floor(pos)), n - 1)
+            frac = pos - lo
+            hi = lo + 1 if frac > 0.0 else lo
+            if interpolation == "lower":
+                hi, frac = lo, 0.0
+            elif interpolation == "higher":
+                lo, frac = hi, 0.0
+            for r in (lo, hi):
+                if r not in ranks:
+                    ranks.append(r)
+            plan.append((ranks.index(lo), ranks.index(hi), frac))
+        stats = self.order_statistics(theta, feed, ranks)
+        out = torch.empty(len(q), stats.shape[1], dtype=torch.float32, device=stats.device)
+        for i, (lo, hi, frac) in enumerate(plan):
+            if frac == 0.0:
+                out[i] = stats[lo]
+            else:
+                out[i] = stats[lo] + (stats[hi] - stats[lo]) * frac
+        return out
+
     @staticmethod
     def _ptr(t):
         return None if t is None else t.data_ptr()
@@ -145,6 +209,12 @@ class GlmPredict(_Predict):
                      self._ptr(var), self._ptr(lpd), *e, self._ptr(ws), 0 if ws is None else ws.numel(),
                      torch.cuda.current_stream(theta.device).cuda_stream)
 
+    def _launch_ranks(self, theta, X, batch, ranks, n_ranks, out, ws):
+        n, d = theta.shape
+        _lib.call_on(theta.device, "stein_predict_glm_ranks", theta.data_ptr(), n, d, self.kind, self.output, self.w_col,
+                     self.n_feats, X.data_ptr(), batch, ranks, n_ranks, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                     torch.cuda.current_stream(theta.device).cuda_stream)
+
 
 class BnnPredict(_Predict):
     """Outputs of the one-hidden-layer network of BnnScore: relu(X w1 + b1) w2 + b2 per particle.
@@ -164,3 +234,9 @@ class BnnPredict(_Predict):
         _lib.call_on(theta.device, name, theta.data_ptr(), n, d, self.n_in, self.n_hidden, self._cols, self.output,
                      X.data_ptr(), self._ptr(y), batch, *w, self._ptr(pred), self._ptr(mean), self._ptr(var), self._ptr(lpd),
                      *e, self._ptr(ws), 0 if ws is None else ws.numel(), torch.cuda.current_stream(theta.device).cuda_stream)
+
+    def _launch_ranks(self, theta, X, batch, ranks, n_ranks, out, ws):
+        n, d = theta.shape
+        _lib.call_on(theta.device, "stein_predict_bnn_ranks", theta.data_ptr(), n, d, self.n_in, self.n_hidden, self._cols,
+                     self.output, X.data_ptr(), batch, ranks, n_ranks, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                     torch.cuda.current_stream(theta.device).cuda_stream)

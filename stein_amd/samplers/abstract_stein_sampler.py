@@ -304,7 +304,7 @@ class AbstractSteinSampler:
             return self.theta_matrix
         return self._theta_f32() if self.kernel_dtype == torch.float32 else self.theta_matrix.float()
 
-    def posterior_predictive(self, producer, feed, weights=None):
+    def posterior_predictive(self, producer, feed, weights=None, quantiles=None):
         """Per-test-point ensemble summaries of a predictive producer (stein_amd.predict.GlmPredict / BnnPredict) under
         the current particles: {"mean", "var"} of its outputs over the particles and, when `feed` has a "y", "lpd", the log
         predictive density log(1/n sum_p p(y_b | theta_p)) -- NumPy arrays of [batch].  The [n, batch] matrix that
@@ -312,7 +312,14 @@ class AbstractSteinSampler:
 
         weights ([n], w_p >= 0: ``importance_weights(...)``, or ``torch.bincount(thin(m), minlength=n)``): the summaries
         under these weights, sum_p w_p (.) / sum_p w_p in place of 1/n sum_p (.), and "ess", the weights' effective
-        sample size (sum w)^2 / sum w^2, a float.  A bad weight vector (a negative or non-finite entry, all zero) gives NaN."""
+        sample size (sum w)^2 / sum w^2, a float.  A bad weight vector (a negative or non-finite entry, all zero) gives NaN.
+
+        quantiles (e.g. (0.05, 0.5, 0.95)): also "quantiles", a NumPy [len(quantiles), batch] array of these quantiles of
+        the outputs over the particles per test point (``producer.quantiles``: exact order statistics, NumPy's linear
+        interpolation) -- the ensemble median and credible bands, where mean +- k sqrt(var) assumes a Gaussian ensemble.
+        Weighted quantiles are not built: `quantiles` together with `weights` is a ValueError."""
+        if quantiles is not None and weights is not None:
+            raise ValueError("weighted quantiles are not built: pass `quantiles` or `weights`, not both")
         if self._group is not None:
             raise ValueError("posterior_predictive works on one rank only: a sharded sampler would have to merge the "
                              "ranks' states; use function_posterior, which gathers the outputs")
@@ -324,7 +331,10 @@ class AbstractSteinSampler:
                 mean, var, lpd = producer.summary(self._matrix_f32(), feed)
             else:
                 mean, var, lpd, ess = producer.weighted_summary(self._matrix_f32(), feed, weights)
+            band = None if quantiles is None else producer.quantiles(self._matrix_f32(), feed, quantiles)
         out = {"mean": mean.cpu().numpy(), "var": var.cpu().numpy()}
+        if band is not None:
+            out["quantiles"] = band.cpu().numpy()
         if lpd is not None:
             out["lpd"] = lpd.cpu().numpy()
         if ess is not None:
