@@ -756,6 +756,62 @@ int stein_predict_bnn_ranks(const float* theta, int64_t n, int64_t d, int64_t n_
  * of 16 particles per slice) instead of the summary calls' plan; 0 = default.  No bit of the result depends on it. */
 int stein_debug_predict_ranks_slices(int slices);
 
+/* Weighted order statistics: credible bands under per-particle weights (stein_weights) or of a thinned multiset (the counts
+ * of stein_thin's indices), again without pred.  Every particle carries a mass m_p, an unsigned 32-bit integer (device
+ * array masses [n]; stein_predict_rank_masses below makes them from weights).  M = sum_p m_p with 0 < M < 2^32.
+ *   out [n_levels][batch]  out[i][b] = the smallest f_pb among the particles with m_p > 0 such that the mass of the
+ *                          particles with m_p > 0 and key(f) <= key(f_pb) exceeds t_i = max(0, ceil(levels[i] * M) - 1)
+ * t_i is computed on the device, one fp64 multiply and a ceil; the host never learns M.  This is NumPy's
+ * np.quantile(f, q, weights=m, method="inverted_cdf"): with counts c it is np.sort(np.repeat(f, c))[t] exactly, with m = 1
+ * the unweighted t-th order statistic bit for bit, and the level (t + 0.5) / M selects target t for every M < 2^32.  It is
+ * NOT the linear interpolation that Python's quantiles() puts on top of the unweighted order statistics: no two elements
+ * are ever mixed.  f_pb, the key order (-0 before +0, every NaN last, returned as a quiet NaN) and the exactness are those
+ * of stein_predict_*_ranks.  A particle of mass 0 is skipped: its output may be NaN and is never returned or counted.
+ * levels: a HOST array of n_levels doubles in [0, 1], in any order, repeats allowed, read before the call returns; a level's
+ * row does not depend on its company.  At most STEIN_PRED_RANKS_MAX levels per call.
+ * Method: the select of stein_predict_*_ranks with every output adding m_p in place of 1 to a 32-bit counter per bin; all
+ * sums across workgroups are 32-bit integer atomics, so a repeated call is bit-identical and the result depends on neither
+ * the grid, the particle slices nor the digit width.  A word per bin costs four times the LDS of the unweighted call's
+ * bytes.  The digit width, 1 .. 4 bits a level, is the one of the least ceil(32 / bits) / min(2, workgroups whose LDS fit a
+ * CU), the wider on a tie (measured: two resident workgroups run a forward pass 1.9 times faster than one, more no faster);
+ * a grid of at most 256 workgroups takes the widest width that fits.  A first small launch sums the masses in 64 bits; the
+ * masses are not trusted: M = 0 or M >= 2^32 gives NaN rows and STEIN_OK.
+ * Workspace: stein_predict_ranks_weighted_workspace_bytes = 512 bytes + 76 per (row, level); independent of n and d,
+ * 8-byte aligned; it may hold anything on entry.
+ * Refused before any launch, in the order of stein_predict_*_ranks: masses == NULL and levels == NULL among the NULL
+ * pointers and n_levels < 1 (STEIN_E_BADARG); the output, shape, kind, column and width checks; n_levels >
+ * STEIN_PRED_RANKS_MAX (STEIN_E_UNSUPPORTED); a level outside [0, 1], NaN included (STEIN_E_BADARG); the workspace
+ * (STEIN_E_WORKSPACE); a digit width forced by the hook below whose counters do not fit a CU's LDS (STEIN_E_UNSUPPORTED). */
+int stein_predict_ranks_weighted_workspace_bytes(int64_t n, int64_t batch, int64_t n_levels, size_t* out_bytes);
+int stein_predict_glm_ranks_weighted(const float* theta, int64_t n, int64_t d, int kind, int output, int64_t w_col,
+                                     int64_t n_feats, const float* X, int64_t batch, const uint32_t* masses,
+                                     const double* levels /* host */, int64_t n_levels, float* out /* [n_levels][batch] */,
+                                     void* workspace, size_t ws_bytes, void* stream);
+int stein_predict_bnn_ranks_weighted(const float* theta, int64_t n, int64_t d, int64_t n_in, int64_t n_hidden,
+                                     const int64_t* cols, int output, const float* X, int64_t batch, const uint32_t* masses,
+                                     const double* levels, int64_t n_levels, float* out, void* workspace, size_t ws_bytes,
+                                     void* stream);
+/* test hook, per calling thread: the digit width of the weighted ranks calls, 1 .. 4 bits a level; 0 = the rule above.  No bit
+ * of the result depends on it.  The stein_debug_predict_ranks_slices hook applies to the weighted calls too. */
+int stein_debug_predict_ranks_weighted_bits(int bits);
+
+/* Masses from weights, on the device: weights [n] fp64 (device) -> masses [n] and info [2] fp64 (device).
+ *   STEIN_MASS_NORMALISED  m_p = rint(w_p / W * 2^31), the quotient taken in fp64, W the fp64 sum of the weights in a fixed
+ *                          order that depends on n alone.  n <= 2^30, so M <= 2^31 + n / 2 < 2^32; a weight below 2^-32 W
+ *                          gets mass 0; a power-of-two rescaling of the weights changes no bit.
+ *   STEIN_MASS_COUNTS      m_p = w_p exactly: every weight an integer in [0, 2^32), their sum below 2^32.
+ *   info[0] = M as a double, info[1] = the number of particles with m_p > 0.
+ * The host never reads the weights.  A negative or non-finite weight, W = 0, an overflow of W, or (COUNTS) a weight that is no
+ * integer or a sum of 2^32 or more: the call returns STEIN_OK, every mass is 0 and info[0] is NaN, and a weighted ranks
+ * call on these masses returns NaN rows.  Deterministic: no atomics; a repeated call is bit-identical.
+ * Workspace: stein_predict_rank_masses_workspace_bytes(n) = 24 bytes per workgroup of 256 lanes, at most 256 of them; 8-byte
+ * aligned; it may hold anything on entry.  Refused: a NULL pointer or an unknown mode (STEIN_E_BADARG), n outside
+ * [1, 2^30] (STEIN_E_SHAPE), the workspace (STEIN_E_WORKSPACE). */
+enum { STEIN_MASS_NORMALISED = 0, STEIN_MASS_COUNTS = 1 };
+int stein_predict_rank_masses_workspace_bytes(int64_t n, size_t* out_bytes);
+int stein_predict_rank_masses(const double* weights, int64_t n, int mode, uint32_t* masses, double* info /* [2] */,
+                              void* workspace, size_t ws_bytes, void* stream);
+
 /* small helpers used by the host layer */
 int stein_cast_f64_to_f32(const double* src, float* dst, int64_t count, void* stream);
 int stein_cast_f32_to_bf16(const float* src, void* dst, int64_t count, void* stream);

@@ -35,6 +35,7 @@ FLAG_KSD = 256      # also the kernelized Stein discrepancy sums: sqnorm is doub
 GLM_LINEAR, GLM_LOGISTIC = 0, 1
 PRED_LINK, PRED_MEAN = 0, 1
 PRED_RANKS_MAX = 8                # STEIN_PRED_RANKS_MAX: order statistics per stein_predict_*_ranks call
+MASS_NORMALISED, MASS_COUNTS = 0, 1   # STEIN_MASS_* (stein_predict_rank_masses)
 KERNEL_RBF, KERNEL_IMQ = 0, 1     # STEIN_KERNEL_* (stein_thin, stein_ksd_boot, stein_ksd_matmul, stein_weights)
 SPEC_TABLE_WORDS = 65544          # uint64 words of the rank-summed window table ...
 SPEC_TABLE_OFFSET_WORDS = 1 << 21  # ... which starts 2^21 words into the SPEC section (slots + entry buffer)
@@ -76,6 +77,14 @@ _SIGNATURES = {
     "stein_predict_bnn_ranks": [_vp, _i64, _i64, _i64, _i64, _c.POINTER(_i64), _int, _vp, _i64, _c.POINTER(_i64), _i64, _vp, _vp,
                                 _sz, _vp],
     "stein_debug_predict_ranks_slices": [_int],
+    "stein_predict_ranks_weighted_workspace_bytes": [_i64, _i64, _i64, _c.POINTER(_sz)],
+    "stein_predict_glm_ranks_weighted": [_vp, _i64, _i64, _int, _int, _i64, _i64, _vp, _i64, _vp, _c.POINTER(_dbl), _i64, _vp,
+                                         _vp, _sz, _vp],
+    "stein_predict_bnn_ranks_weighted": [_vp, _i64, _i64, _i64, _i64, _c.POINTER(_i64), _int, _vp, _i64, _vp, _c.POINTER(_dbl),
+                                         _i64, _vp, _vp, _sz, _vp],
+    "stein_debug_predict_ranks_weighted_bits": [_int],
+    "stein_predict_rank_masses_workspace_bytes": [_i64, _c.POINTER(_sz)],
+    "stein_predict_rank_masses": [_vp, _i64, _int, _vp, _vp, _vp, _sz, _vp],
     "stein_rank_begin": [_vp, _i64, _i64, _i64, _i64, _int, _vp, _sz, _int, _vp],
     "stein_rank_pick": [_i64, _i64, _i64, _i64, _int, _vp, _sz, _int, _vp, _vp, _vp, _vp],
     "stein_rank_radix": [_int, _int, _i64, _i64, _i64, _i64, _int, _vp, _sz, _int, _vp, _vp, _vp],
@@ -374,6 +383,27 @@ def debug_predict_ranks_slices(slices):
     """Test hook (per calling thread): particle slices of the stein_predict_*_ranks calls (at most 1024); 0 restores the
     plan's own rule.  No bit of the result depends on it."""
     call("stein_debug_predict_ranks_slices", int(slices))
+
+
+def predict_ranks_weighted_workspace_bytes(n, batch, n_levels):
+    """Workspace bytes of a stein_predict_*_ranks_weighted call: 512 bytes and 76 per (row, level), independent of n and d.
+    Host arithmetic."""
+    total = _sz(0)
+    call("stein_predict_ranks_weighted_workspace_bytes", n, batch, n_levels, ctypes.byref(total))
+    return int(total.value)
+
+
+def predict_rank_masses_workspace_bytes(n):
+    """Workspace bytes of stein_predict_rank_masses: 24 per workgroup of its grid, at most 6144.  Host arithmetic."""
+    total = _sz(0)
+    call("stein_predict_rank_masses_workspace_bytes", n, ctypes.byref(total))
+    return int(total.value)
+
+
+def debug_predict_ranks_weighted_bits(bits):
+    """Test hook (per calling thread): digit bits per level of the stein_predict_*_ranks_weighted calls (1 .. 4); 0 restores
+    the rule.  No bit of the result depends on it."""
+    call("stein_debug_predict_ranks_weighted_bits", int(bits))
 
 
 def version():

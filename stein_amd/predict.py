@@ -14,7 +14,10 @@ hand-written HIP kernels (csrc/stein_predict.hip) in two forms:
   size (``posterior_predictive(..., weights=w)``);
 * ``producer.order_statistics(theta_matrix, feed, ranks)`` / ``producer.quantiles(theta_matrix, feed, q)`` -> [len, batch]:
   exact order statistics of the outputs over the particles per test point -- the ensemble median, credible bands -- again
-  without [n, batch] (``posterior_predictive(..., quantiles=(0.05, 0.5, 0.95))``).
+  without [n, batch] (``posterior_predictive(..., quantiles=(0.05, 0.5, 0.95))``);
+* ``producer.weighted_quantiles(theta_matrix, feed, weights, q)`` -> [len(q), batch]: the band under importance weights or
+  of a thinned multiset (counts), by the inverted weighted distribution function -- an element of the ensemble, not
+  interpolated (``sampler.predictive_quantiles(producer, feed, q, weights=w)``).
 """
 import ctypes
 import math
@@ -43,6 +46,8 @@ class _Predict:
         self._ws = None
         self._wws = None              # the workspace of weighted_summary: the weight pass's sums ahead of the states
         self._rws = None              # the workspace of order_statistics: 76 bytes per (row, rank of one call)
+        self._masses = self._mass_info = None   # weighted_quantiles: the particles' integer masses and their total
+        self._mws = self._wrws = None           # ... the workspaces of the masses pass and of the weighted select
 
     def _workspace(self, n, batch, device):
         need = _lib.predict_workspace_bytes(n, batch)
@@ -177,6 +182,53 @@ class _Predict:
                 out[i] = stats[lo] + (stats[hi] - stats[lo]) * frac
         return out
 
+    def weighted_quantiles(self, theta, feed, weights, q):
+        """-> [len(q), batch] float32 device tensor: the q-quantiles of the outputs per test point under per-particle
+        weights, by the inverted weighted distribution function (NumPy's ``method="inverted_cdf"`` with weights): the
+        smallest output at which the cumulative weight reaches q of the total.  Always an element of the ensemble, never
+        an interpolation -- a different definition from ``quantiles``' "linear".  `weights` [n], validated as for
+        ``weighted_summary`` and never read on the host.  An integer dtype -- ``torch.bincount(sampler.thin(m),
+        minlength=n)`` -- is taken as counts: the result is exactly the order statistic ceil(q M) - 1 (0 for q = 0) of the
+        multiset with M = sum of the counts elements.  Any float dtype is normalised on the device to integer masses
+        rint(w_p / W 2^31), so the cumulative probabilities are exact to (n / 2 + 1) / 2^31.  A particle of weight zero
+        is skipped; bad weights (negative, non-finite, all zero, a count sum of 2^32 or more) give NaN rows.  No
+        [n, batch] matrix: a weighted radix select that recomputes the forward pass; eight levels go into one call of the
+        library, more are split."""
+        X, _, batch = self._inputs(theta, feed, False)
+        n = theta.shape[0]
+        w = torch.as_tensor(weights)
+        if w.dtype == torch.bool or w.is_complex():
+            raise ValueError("weights must be real-valued, not %s" % w.dtype)
+        if w.dim() != 1 or w.shape[0] != n:
+            raise ValueError("weights must be [%d], one per particle" % n)
+        mode = _lib.MASS_NORMALISED if w.dtype.is_floating_point else _lib.MASS_COUNTS
+        w = w.to(device=theta.device, dtype=torch.float64).contiguous()
+        q = [float(v) for v in q]
+        if not q:
+            raise ValueError("q must not be empty")
+        for v in q:
+            if not 0.0 <= v <= 1.0:       # NaN too
+                raise ValueError("quantiles must lie in [0, 1], not %r" % v)
+        dev = theta.device
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if self._masses is None or self._masses.device != dev or self._masses.numel() < n:
+            self._masses = torch.empty(n, dtype=torch.int32, device=dev)      # the uint32 masses, as bytes
+            self._mass_info = torch.empty(2, dtype=torch.float64, device=dev)
+        need = _lib.predict_rank_masses_workspace_bytes(n)
+        if self._mws is None or self._mws.device != dev or self._mws.numel() < need:
+            self._mws = torch.empty(need, dtype=torch.uint8, device=dev)
+        _lib.call_on(dev, "stein_predict_rank_masses", w.data_ptr(), n, mode, self._masses.data_ptr(),
+                     self._mass_info.data_ptr(), self._mws.data_ptr(), self._mws.numel(), stream)
+        need = _lib.predict_ranks_weighted_workspace_bytes(n, batch, min(len(q), _lib.PRED_RANKS_MAX))
+        if self._wrws is None or self._wrws.device != dev or self._wrws.numel() < need:
+            self._wrws = torch.empty(need, dtype=torch.uint8, device=dev)
+        out = torch.empty(len(q), batch, dtype=torch.float32, device=dev)
+        for at in range(0, len(q), _lib.PRED_RANKS_MAX):
+            part = q[at:at + _lib.PRED_RANKS_MAX]
+            self._launch_wranks(theta, X, batch, self._masses, (ctypes.c_double * len(part))(*part), len(part),
+                                out[at:at + len(part)], self._wrws)
+        return out
+
     @staticmethod
     def _ptr(t):
         return None if t is None else t.data_ptr()
@@ -215,6 +267,12 @@ class GlmPredict(_Predict):
                      self.n_feats, X.data_ptr(), batch, ranks, n_ranks, out.data_ptr(), ws.data_ptr(), ws.numel(),
                      torch.cuda.current_stream(theta.device).cuda_stream)
 
+    def _launch_wranks(self, theta, X, batch, masses, levels, n_levels, out, ws):
+        n, d = theta.shape
+        _lib.call_on(theta.device, "stein_predict_glm_ranks_weighted", theta.data_ptr(), n, d, self.kind, self.output,
+                     self.w_col, self.n_feats, X.data_ptr(), batch, masses.data_ptr(), levels, n_levels, out.data_ptr(),
+                     ws.data_ptr(), ws.numel(), torch.cuda.current_stream(theta.device).cuda_stream)
+
 
 class BnnPredict(_Predict):
     """Outputs of the one-hidden-layer network of BnnScore: relu(X w1 + b1) w2 + b2 per particle.
@@ -240,3 +298,9 @@ class BnnPredict(_Predict):
         _lib.call_on(theta.device, "stein_predict_bnn_ranks", theta.data_ptr(), n, d, self.n_in, self.n_hidden, self._cols,
                      self.output, X.data_ptr(), batch, ranks, n_ranks, out.data_ptr(), ws.data_ptr(), ws.numel(),
                      torch.cuda.current_stream(theta.device).cuda_stream)
+
+    def _launch_wranks(self, theta, X, batch, masses, levels, n_levels, out, ws):
+        n, d = theta.shape
+        _lib.call_on(theta.device, "stein_predict_bnn_ranks_weighted", theta.data_ptr(), n, d, self.n_in, self.n_hidden,
+                     self._cols, self.output, X.data_ptr(), batch, masses.data_ptr(), levels, n_levels, out.data_ptr(),
+                     ws.data_ptr(), ws.numel(), torch.cuda.current_stream(theta.device).cuda_stream)

@@ -317,9 +317,11 @@ class AbstractSteinSampler:
         quantiles (e.g. (0.05, 0.5, 0.95)): also "quantiles", a NumPy [len(quantiles), batch] array of these quantiles of
         the outputs over the particles per test point (``producer.quantiles``: exact order statistics, NumPy's linear
         interpolation) -- the ensemble median and credible bands, where mean +- k sqrt(var) assumes a Gaussian ensemble.
-        Weighted quantiles are not built: `quantiles` together with `weights` is a ValueError."""
+        `quantiles` together with `weights` is a ValueError: weighted quantiles follow another definition (no
+        interpolation) and come from ``predictive_quantiles(producer, feed, q, weights=w)``."""
         if quantiles is not None and weights is not None:
-            raise ValueError("weighted quantiles are not built: pass `quantiles` or `weights`, not both")
+            raise ValueError("weighted quantiles are not interpolated and are not part of posterior_predictive: pass "
+                             "`quantiles` or `weights`, not both, and use predictive_quantiles(producer, feed, q, weights=w)")
         if self._group is not None:
             raise ValueError("posterior_predictive works on one rank only: a sharded sampler would have to merge the "
                              "ranks' states; use function_posterior, which gathers the outputs")
@@ -340,6 +342,28 @@ class AbstractSteinSampler:
         if ess is not None:
             out["ess"] = float(ess.item())
         return out
+
+    def predictive_quantiles(self, producer, feed, q, weights=None):
+        """-> NumPy [len(q), batch]: the q-quantiles (e.g. (0.05, 0.5, 0.95)) of a predictive producer's outputs over the
+        current particles per test point, without the [n, batch] matrix.  One rank only.
+
+        weights=None: ``producer.quantiles`` -- exact order statistics under NumPy's linear interpolation, what
+        ``posterior_predictive(..., quantiles=q)`` returns.
+        weights ([n]: ``importance_weights(...)``, or the integer counts ``torch.bincount(thin(m), minlength=n)``):
+        ``producer.weighted_quantiles`` -- the inverted weighted distribution function, the smallest output at which the
+        cumulative weight reaches q of the total.  It is an element of the ensemble and is NOT interpolated, so with
+        uniform weights it is the "inverted_cdf" quantile, not the linear one.  Bad weights give NaN."""
+        if self._group is not None:
+            raise ValueError("predictive_quantiles works on one rank only: a sharded sampler would have to merge the "
+                             "ranks' counts; use function_posterior, which gathers the outputs")
+        if not hasattr(producer, "weighted_quantiles"):
+            raise ValueError("predictive_quantiles needs a predictive producer (GlmPredict / BnnPredict)")
+        with torch.no_grad():
+            if weights is None:
+                band = producer.quantiles(self._matrix_f32(), feed, q)
+            else:
+                band = producer.weighted_quantiles(self._matrix_f32(), feed, weights, q)
+        return band.cpu().numpy()
 
     def samples_all(self):
         """All n particles as one float64 [n, d] NumPy array on every rank (the reference's `samples`, stein_sampler.py:73-78,
