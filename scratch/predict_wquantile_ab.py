@@ -1,7 +1,7 @@
 """A/B of the weighted predictive quantiles (stein_amd/predict.py, weighted_quantiles) by the protocol of
 profiles/predict_quantile_ab.txt: one process, variants alternated block by block, 5 warm-up calls, 5 blocks, device events.
 
-    python scratch/predict_wquantile_ab.py --parent PATH_OF_THE_PARENT_COMMITS_libsteinhip.so [--out FILE]
+    python scratch/predict_wquantile_ab.py --parent PATH_OF_THE_PARENT_COMMITS_libsteinhip.so [--out FILE] [--sections 3]
 
 Per shape (the four example shapes and the GLM kernel's chunked arm):
   1. the weighted C call at three and at six levels (masses made once, outside the timing) against the parent commit's
@@ -9,8 +9,9 @@ Per shape (the four example shapes and the GLM kernel's chunked arm):
      [n, batch], torch.sort(dim=0), a gather of the weights, cumsum, searchsorted -- and the masses pass alone; peak of
      torch.cuda.max_memory_allocated over one call of each route;
   2. the same weighted calls under every digit width the hook can force (the rule's own width is marked);
-  3. the existing calls, this commit against the parent commit's library loaded beside it: pred + mean + var + lpd and the
-     six-rank call, timed alternately and compared bit for bit.
+  3. the existing calls, this commit against the parent commit's library loaded beside it: pred + mean + var + lpd, the
+     six-rank call and the weighted call at three and at six levels, timed alternately and compared bit for bit.
+--sections 3 runs section 3 alone (a change that must leave every call as it is needs nothing else).
 """
 import ctypes
 import os
@@ -31,6 +32,10 @@ from stein_amd import _lib  # noqa: E402
 from stein_amd.predict import BnnPredict, GlmPredict  # noqa: E402
 
 OUT_FILE = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
+SECTIONS = sys.argv[sys.argv.index("--sections") + 1] if "--sections" in sys.argv else "all"
+if SECTIONS not in ("all", "3"):
+    sys.exit("--sections takes 'all' or '3', not %r" % SECTIONS)
+ONLY_3 = SECTIONS == "3"
 dev = base.dev
 say = base.say
 Q3 = (0.05, 0.5, 0.95)
@@ -58,9 +63,10 @@ def raw_ranks(lib, prod, theta, feed, n, B, ranks):
     return call, out
 
 
-def raw_wranks(prod, theta, feed, n, B, masses, levels):
+def raw_wranks(lib, prod, theta, feed, n, B, masses, levels):
     which, head = model_head(prod, theta, feed, n, B)
-    fn = getattr(_lib.load(), "stein_predict_%s_ranks_weighted" % which)
+    fn = getattr(lib, "stein_predict_%s_ranks_weighted" % which)
+    fn.argtypes, fn.restype = _lib._SIGNATURES["stein_predict_%s_ranks_weighted" % which], ctypes.c_int
     out = torch.empty(len(levels), B, device=dev)
     ws = torch.empty(_lib.predict_ranks_weighted_workspace_bytes(n, B, len(levels)), dtype=torch.uint8, device=dev)
     arr = (ctypes.c_double * len(levels))(*levels)
@@ -90,6 +96,15 @@ def case(tag, n, B, prod, theta, feed, outputs, parent, blocks=5, steps=20):
         _lib.call("stein_predict_rank_masses", w.data_ptr(), n, _lib.MASS_NORMALISED, masses.data_ptr(), info.data_ptr(),
                   mws.data_ptr(), mws.numel(), stream)
     masses_pass()
+    if not ONLY_3:
+        sections_1_2(tag, n, B, prod, theta, feed, outputs, parent, blocks, steps, w, masses, masses_pass)
+    else:
+        say("%s, %d x %d calls" % (tag, blocks, steps))
+    if parent is not None:
+        section_3(n, B, prod, theta, feed, parent, blocks, steps, masses)
+
+
+def sections_1_2(tag, n, B, prod, theta, feed, outputs, parent, blocks, steps, w, masses, masses_pass):
     keep = {}
 
     def torch_route(qs):
@@ -102,7 +117,7 @@ def case(tag, n, B, prod, theta, feed, outputs, parent, blocks=5, steps=20):
     outs = {}
     for qs in (Q3, Q6):
         k = len(qs)
-        call, outs["w%d" % k] = raw_wranks(prod, theta, feed, n, B, masses, qs)
+        call, outs["w%d" % k] = raw_wranks(_lib.load(), prod, theta, feed, n, B, masses, qs)
         variants["this: weighted, %d levels (%d bits)" % (k, default_bits(prod, k, n, B))] = call
         if parent is not None:
             call, outs["p%d" % k] = raw_ranks(parent, prod, theta, feed, n, B, [int(q * (n - 1)) for q in qs])
@@ -128,7 +143,7 @@ def case(tag, n, B, prod, theta, feed, outputs, parent, blocks=5, steps=20):
     widths = {}
     calls = {}
     for k, qs in ((3, Q3), (6, Q6)):
-        calls[k], _ = raw_wranks(prod, theta, feed, n, B, masses, qs)
+        calls[k], _ = raw_wranks(_lib.load(), prod, theta, feed, n, B, masses, qs)
 
     def forced(k, bits):
         def run():
@@ -146,23 +161,34 @@ def case(tag, n, B, prod, theta, feed, outputs, parent, blocks=5, steps=20):
                 continue
             widths["%d levels, %d bits%s" % (k, bits, " (the rule)" if bits == default_bits(prod, k, n, B) else "")] = forced(k, bits)
     base.report("  2. forced digit widths", base.ab(widths, 3, 3, max(steps // 2, 5)))
-    if parent is not None:
-        this_call, this_bufs = wab.raw_unweighted(_lib.load(), prod, theta, feed, n, B)
-        par_call, par_bufs = wab.raw_unweighted(parent, prod, theta, feed, n, B)
-        six = [int(q * (n - 1)) for q in Q6]
-        this_r, this_out = raw_ranks(_lib.load(), prod, theta, feed, n, B, six)
-        par_r, par_out = raw_ranks(parent, prod, theta, feed, n, B, six)
-        r3 = base.ab({"this commit: pred + mean + var + lpd (C call)": this_call, "parent commit: the same call": par_call,
-                      "this commit: 6 ranks (C call)": this_r, "parent commit: 6 ranks": par_r}, 5, blocks, steps)
-        torch.cuda.synchronize()
-        same = all(torch.equal(this_bufs[k].view(torch.int32), par_bufs[k].view(torch.int32)) for k in this_bufs)
-        same_r = torch.equal(this_out.view(torch.int32), par_out.view(torch.int32))
-        base.report("  3. existing calls, this commit against the parent commit's library", r3)
-        v = list(r3.values())
-        for what, a, b, ok in (("summary", v[0], v[1], same), ("6 ranks", v[2], v[3], same_r)):
-            diff, allowed = statistics.median(a) - statistics.median(b), max(wab.spread(a), wab.spread(b))
-            say("     %s: this - parent %+.4f ms; larger block-to-block spread %.4f ms: %s; bit-identical: %s"
-                % (what, diff, allowed, "not slower" if diff <= allowed else "SLOWER", ok))
+
+
+def section_3(n, B, prod, theta, feed, parent, blocks, steps, masses):
+    this_call, this_bufs = wab.raw_unweighted(_lib.load(), prod, theta, feed, n, B)
+    par_call, par_bufs = wab.raw_unweighted(parent, prod, theta, feed, n, B)
+    six = [int(q * (n - 1)) for q in Q6]
+    this_r, this_out = raw_ranks(_lib.load(), prod, theta, feed, n, B, six)
+    par_r, par_out = raw_ranks(parent, prod, theta, feed, n, B, six)
+    variants = {"this commit: pred + mean + var + lpd (C call)": this_call, "parent commit: the same call": par_call,
+                "this commit: 6 ranks (C call)": this_r, "parent commit: 6 ranks": par_r}
+    pairs = [("summary", lambda: all(torch.equal(this_bufs[k].view(torch.int32), par_bufs[k].view(torch.int32)) for k in this_bufs)),
+             ("6 ranks", lambda: torch.equal(this_out.view(torch.int32), par_out.view(torch.int32)))]
+    for qs in (Q3, Q6):
+        this_w, this_wout = raw_wranks(_lib.load(), prod, theta, feed, n, B, masses, qs)
+        par_w, par_wout = raw_wranks(parent, prod, theta, feed, n, B, masses, qs)
+        variants["this commit: weighted, %d levels (C call)" % len(qs)] = this_w
+        variants["parent commit: weighted, %d levels" % len(qs)] = par_w
+        pairs.append(("weighted, %d levels" % len(qs),
+                      lambda a=this_wout, b=par_wout: torch.equal(a.view(torch.int32), b.view(torch.int32))))
+    r3 = base.ab(variants, 5, blocks, steps)
+    torch.cuda.synchronize()
+    base.report("  3. existing calls, this commit against the parent commit's library", r3)
+    v = list(r3.values())
+    for i, (what, same) in enumerate(pairs):
+        a, b = v[2 * i], v[2 * i + 1]
+        diff, allowed = statistics.median(a) - statistics.median(b), max(wab.spread(a), wab.spread(b))
+        say("     %s: this - parent %+.4f ms; larger block-to-block spread %.4f ms: %s; bit-identical: %s"
+            % (what, diff, allowed, "not slower" if diff <= allowed else "SLOWER", same()))
 
 
 def logistic(n, feats, B, parent, note="", steps=20):

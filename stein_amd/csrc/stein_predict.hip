@@ -29,25 +29,12 @@
 // weight zero is skipped.  The first particle with w > 0 sets shift, max and sum.  The state stays five floats: a slice's
 // weight W_s / W is per slice, not per row, and comes from the weight pass, which also zeroes the W_s of a slice none of
 // whose weights survives the rounding, so the finish kernel skips exactly the slices whose state was never set.
-#include "stein_common.h"
+//
+// The forward passes themselves (pred_glm_slice, pred_bnn_pass), the plan and the argument checks are stein_predict_fwd.h's:
+// the rank-counting kernels of stein_predict_ranks.hip run the same ones.
+#include "stein_predict_fwd.h"
 #include <cfloat>
 
-constexpr int PR_ROWS = 256;         // rows of X per workgroup: one per lane
-constexpr int PR_PASS = 16;          // particles per pass: their outputs are 16 registers of every lane
-constexpr int PR_SLICE_CAP = 1024;   // particle slices at most: the workspace is 20 bytes per (slice, row)
-constexpr int PR_TARGET_WGS = 2048;  // workgroups wanted: eight per CU (the loops wait on LDS, so more resident workgroups
-                                     // hide it; DESIGN.md 6e on what was and was not recorded); a small batch is filled
-                                     // up with slices
-constexpr int PR_FC = 58;            // GLM: features of the X tile per LDS chunk ([256][59] floats = 59 KB)
-constexpr int PR_HC = 64;            // network: hidden units of the PR_PASS staged particles per LDS chunk
-constexpr int PR_NIN_MAX = 4;        // the score producers' own limits
-constexpr int PR_WIDTH_MAX = 1024;
-// n and batch at most: the kernels index particles and rows in int and step past the end by less than a slice (p_begin + per
-// < 2 n) or a row tile (row < batch + PR_ROWS) before they clamp, so both stay below 2^31
-constexpr int64_t PR_COUNT_MAX = (int64_t)1 << 30;
-constexpr float PR_HALF_LOG_2PI = 0.91893853320467274178f;
-
-struct PredCols { int w1, b1, w2, b2, loggam; };
 // of the particles seen so far (their count is the caller's loop index): the slice's first output as a shift, mean and M2 of
 // the outputs minus that shift (a common offset of the outputs then costs no digits), running max and sum exp(l - max)
 struct PredState { float shift, mean, m2, mx, se; };
@@ -134,65 +121,6 @@ __device__ __forceinline__ void pred_store_state(const PredState& st, float* __r
   }
 }
 
-// ---- the forward passes, shared by the summary kernels and the rank-counting kernels of stein_predict_ranks.hip: one body
-// of device code, so a counted value is bit for bit the value pred holds.
-// GLM: the walk of one workgroup over its slice [p_begin, p_end) of the particles, PR_PASS at a time.  fc = features per
-// chunk (F when the whole X tile fits, else PR_FC), ld = floats per staged row of X (odd: lane t reads xs[t * ld + f], 64
-// different banks); xs [PR_ROWS][ld] and ws [fc][PR_PASS] in LDS.  z[k] = x_row . w_(p0 + k) is summed over the features in
-// order whatever the chunking.  between(p0, cnt): what the caller stages beside the first chunk's weights of a pass, between
-// the two barriers; consume(p0, k, z): the lane's linear output of particle p0 + k, in particle order.  (z stays a local of
-// this function: handed to a helper by reference, the inner loop came out with its LDS reads serialised, 7 % slower.)
-template <class Between, class Consume>
-__device__ __forceinline__ void pred_glm_slice(const float* theta, int d, int w_col, int F, int fc, int ld, const float* X, int B,
-                                               int row0, int p_begin, int p_end, float* xs, float* ws, int t, Between&& between,
-                                               Consume&& consume) {
-  const int nfc = (F + fc - 1) / fc;
-  auto stage_x = [&](int f0, int len) {   // rows past the batch are staged as zeros
-    for (int i = t; i < PR_ROWS * len; i += 256) {
-      const int r = i / len, f = i - r * len;
-      xs[r * ld + f] = row0 + r < B ? X[(size_t)(row0 + r) * F + f0 + f] : 0.f;
-    }
-  };
-  if (nfc == 1) stage_x(0, F);   // the whole tile fits: staged once for every particle of the slice
-  for (int p0 = p_begin; p0 < p_end; p0 += PR_PASS) {
-    const int cnt = min(PR_PASS, p_end - p0);
-    float z[PR_PASS];
-#pragma unroll
-    for (int k = 0; k < PR_PASS; ++k) z[k] = 0.f;
-    for (int c = 0; c < nfc; ++c) {
-      const int f0 = c * fc, len = min(fc, F - f0);
-      __syncthreads();   // every lane is past its last read of ws (and of xs)
-      if (nfc > 1) stage_x(f0, len);
-      for (int i = t; i < PR_PASS * len; i += 256) {
-        const int k = i / len, f = i - k * len;
-        ws[f * PR_PASS + k] = k < cnt ? theta[(size_t)(p0 + k) * d + w_col + f0 + f] : 0.f;
-      }
-      if (c == 0) between(p0, cnt);
-      __syncthreads();
-      const float* xr = xs + t * ld;
-#pragma unroll 2
-      for (int f = 0; f < len; ++f) {
-        const float x = xr[f];
-        const float4* w4 = reinterpret_cast<const float4*>(ws + f * PR_PASS);
-#pragma unroll
-        for (int q = 0; q < PR_PASS / 4; ++q) {
-          const float4 w = w4[q];
-          z[4 * q + 0] = fmaf(x, w.x, z[4 * q + 0]);
-          z[4 * q + 1] = fmaf(x, w.y, z[4 * q + 1]);
-          z[4 * q + 2] = fmaf(x, w.z, z[4 * q + 2]);
-          z[4 * q + 3] = fmaf(x, w.w, z[4 * q + 3]);
-        }
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < PR_PASS; ++k)
-      if (k < cnt) consume(p0, k, z[k]);   // a particle past the slice's end is no particle: it is not counted as f = 0
-  }
-}
-
-// the reported output of a GLM particle from its linear output
-__device__ __forceinline__ float pred_glm_output(float zz, bool sigmoid) { return sigmoid ? 1.f / (1.f + expf(-zz)) : zz; }
-
 // WEIGHTED: wts [n] the weights, head the weight pass's header (head[0] = W); the pass's PR_PASS normalised weights are
 // staged behind ws.
 template <bool WEIGHTED>
@@ -236,68 +164,6 @@ __global__ __launch_bounds__(256) void k_predict_glm(const float* __restrict__ t
         else pred_accumulate(st, p0 - p_begin + k, f, l, want_mv, want_lpd);
       });
   if (live && part) pred_store_state(st, part, blockIdx.y, B, row, want_mv, want_lpd);
-}
-
-// Network: z[k] of the cnt particles from p0 WITHOUT b2 (z comes in as zeros; f = z[k] + lp[k][0]).  x: the lane's NIN input
-// features in registers; lw: the PR_PASS staged particles' b1, w2 and w1 rows of a chunk of PR_HC hidden units (hidden units
-// past H are staged as zeros: relu(0) * 0 adds an exact zero); lp per particle: b2, 1/2 lg - 1/2 log 2 pi, 1/2 e^lg, and
-// what extra(t) puts into lp[t][3] beside them (called by the thread that stages particle p0 + t).
-template <int NIN>
-constexpr int PR_BNN_PW = (NIN + 2) * PR_HC;   // staged floats per particle: b1 [PR_HC], w2 [PR_HC], w1 [NIN][PR_HC]
-
-template <int NIN, class Extra>
-__device__ __forceinline__ void pred_bnn_pass(float (&z)[PR_PASS], const float* theta, int d, int H,
-                                              const PredCols& c, const float (&x)[NIN], int p0, int cnt,
-                                              float* lw, float (*lp)[4], int t, Extra&& extra) {
-  constexpr int PW = PR_BNN_PW<NIN>;
-  for (int h0 = 0; h0 < H; h0 += PR_HC) {
-    const int len = min(PR_HC, H - h0), len4 = (len + 3) & ~3;
-    __syncthreads();   // every lane is past its last read of lw and lp
-    for (int i = t; i < PR_PASS * len4; i += 256) {
-      const int k = i / len4, h = i - k * len4;
-      const bool ok = k < cnt && h < len;
-      const float* th = theta + (size_t)(p0 + (ok ? k : 0)) * d + h0 + h;
-      float* dst = lw + k * PW + h;
-      dst[0] = ok ? th[c.b1] : 0.f;
-      dst[PR_HC] = ok ? th[c.w2] : 0.f;
-#pragma unroll
-      for (int f = 0; f < NIN; ++f) dst[(2 + f) * PR_HC] = ok ? th[c.w1 + f * H] : 0.f;
-    }
-    if (h0 == 0 && t < cnt) {
-      const float* th = theta + (size_t)(p0 + t) * d;
-      const float lg = th[c.loggam];
-      lp[t][0] = th[c.b2];
-      lp[t][1] = fmaf(0.5f, lg, -PR_HALF_LOG_2PI);
-      lp[t][2] = 0.5f * expf(lg);
-      extra(t);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < PR_PASS; ++k) {
-      if (k < cnt) {
-        const float* wk = lw + k * PW;
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-#pragma unroll 2
-        for (int h = 0; h < len4; h += 4) {
-          float4 v = *reinterpret_cast<const float4*>(wk + h);
-          const float4 w2 = *reinterpret_cast<const float4*>(wk + PR_HC + h);
-#pragma unroll
-          for (int f = 0; f < NIN; ++f) {
-            const float4 w1 = *reinterpret_cast<const float4*>(wk + (2 + f) * PR_HC + h);
-            v.x = fmaf(x[f], w1.x, v.x);
-            v.y = fmaf(x[f], w1.y, v.y);
-            v.z = fmaf(x[f], w1.z, v.z);
-            v.w = fmaf(x[f], w1.w, v.w);
-          }
-          a0 = fmaf(fmaxf(v.x, 0.f), w2.x, a0);
-          a1 = fmaf(fmaxf(v.y, 0.f), w2.y, a1);
-          a2 = fmaf(fmaxf(v.z, 0.f), w2.z, a2);
-          a3 = fmaf(fmaxf(v.w, 0.f), w2.w, a3);
-        }
-        z[k] += (a0 + a1) + (a2 + a3);
-      }
-    }
-  }
 }
 
 template <int NIN, bool WEIGHTED>
@@ -451,53 +317,6 @@ __global__ __launch_bounds__(256) void k_predict_finish(const float* __restrict_
   if (lpd) lpd[b] = WEIGHTED ? (float)(top + log(sum)) : (float)(top + log(sum) - log((double)n));
 }
 
-// ---- host-side pieces that stein_predict_ranks.hip shares (it includes this file with STEIN_PREDICT_SHARED_ONLY: every
-// line above this one and these, nothing below) ---------------------------------------------------------
-struct PredPlan { int row_tiles, slices, per; };
-
-static PredPlan predict_plan(int64_t n, int64_t batch) {
-  PredPlan p;
-  p.row_tiles = (int)((batch + PR_ROWS - 1) / PR_ROWS);
-  int64_t s = (PR_TARGET_WGS + p.row_tiles - 1) / p.row_tiles;   // slices that fill the card at this batch
-  if (s > PR_SLICE_CAP) s = PR_SLICE_CAP;
-  const int64_t passes = (n + PR_PASS - 1) / PR_PASS;            // no slice of less than one pass
-  if (s > passes) s = passes;
-  p.per = (int)((n + s - 1) / s);
-  p.slices = (int)((n + p.per - 1) / p.per);
-  return p;
-}
-
-// the weights of a weighted call (on = false: an unweighted call, for which every check and launch is what it was)
-struct PredWeights { bool on; const double* w; double* ess; };
-
-// the checks the entry points share, in the order the header lists them
-static int predict_check(const float* theta, const float* X, const float* y, int64_t n, int64_t d, int64_t batch,
-                         int64_t width, int output, const float* pred, const float* mean, const float* var,
-                         const float* lpd, const PredWeights& pw) {
-  if (!theta || !X || (pw.on && !pw.w)) return stein_fail(STEIN_E_BADARG, "NULL pointer");
-  if (!pred && !mean && !var && !lpd && !pw.ess)
-    return stein_fail(STEIN_E_BADARG, pw.on ? "no output requested: pred, mean, var, lpd and ess are all NULL"
-                                            : "no output requested: pred, mean, var and lpd are all NULL");
-  if (lpd && !y) return stein_fail(STEIN_E_BADARG, "lpd needs y");
-  if (output != STEIN_PRED_LINK && output != STEIN_PRED_MEAN) return stein_fail(STEIN_E_BADARG, "output %d", output);
-  if (n < 1 || d < 1 || batch < 1 || width < 1 || n > PR_COUNT_MAX || d > 0x7fffffffl || batch > PR_COUNT_MAX)
-    return stein_fail(STEIN_E_SHAPE, "bad shape n=%lld d=%lld batch=%lld width=%lld", (long long)n, (long long)d,
-                      (long long)batch, (long long)width);
-  return STEIN_OK;
-}
-
-// the network's six column blocks fit d and do not overlap
-static int predict_check_cols(const int64_t* cols, int64_t n_in, int64_t n_hidden, int64_t d) {
-  const int64_t len[6] = {n_in * n_hidden, n_hidden, n_hidden, 1, 1, 1};
-  for (int i = 0; i < 6; ++i) {
-    if (cols[i] < 0 || cols[i] + len[i] > d) return stein_fail(STEIN_E_SHAPE, "block %d does not fit d=%lld", i, (long long)d);
-    for (int j = 0; j < i; ++j)
-      if (cols[i] < cols[j] + len[j] && cols[j] < cols[i] + len[i]) return stein_fail(STEIN_E_SHAPE, "blocks %d and %d overlap", j, i);
-  }
-  return STEIN_OK;
-}
-
-#ifndef STEIN_PREDICT_SHARED_ONLY
 // ---- the weight pass of a weighted call ------------------------------------------------------------------
 // 256 partial results per quantity folded by halving, in a fixed order: quantities 0 and 1 are sums, 2 is a maximum
 __device__ __forceinline__ void pw_fold(double (*sh)[256], int t, int quantities) {
@@ -632,19 +451,12 @@ static int predict_glm(const float* theta, int64_t n, int64_t d, int kind, int o
                        const float* X, const float* y, int64_t batch, double noise_precision, float* pred, float* mean,
                        float* var, float* lpd, void* workspace, size_t ws_bytes, void* stream, const PredWeights& pw) {
   if (int rc = predict_check(theta, X, y, n, d, batch, n_feats, output, pred, mean, var, lpd, pw)) return rc;
-  if (kind != STEIN_GLM_LINEAR && kind != STEIN_GLM_LOGISTIC) return stein_fail(STEIN_E_BADARG, "kind %d", kind);
-  if (w_col < 0 || w_col + n_feats > d)
-    return stein_fail(STEIN_E_SHAPE, "weights [%lld, %lld) do not fit d=%lld", (long long)w_col, (long long)(w_col + n_feats),
-                      (long long)d);
-  if (n_feats > PR_WIDTH_MAX) return stein_fail(STEIN_E_UNSUPPORTED, "more than 1024 features per particle");
+  if (int rc = predict_check_glm(kind, w_col, n_feats, d)) return rc;
   if (lpd && kind == STEIN_GLM_LINEAR && !(noise_precision > 0.0 && noise_precision < INFINITY))
     return stein_fail(STEIN_E_BADARG, "noise_precision must be positive and finite");
   const bool summary = mean || var || lpd;   // the rows the forward kernel reduces; ess comes from the weight pass alone
   if (int rc = predict_check_ws(n, batch, summary || pw.ess, workspace, ws_bytes, pw)) return rc;
   const PredPlan pl = predict_plan(n, batch);
-  const int fc = (int)(n_feats <= PR_FC ? n_feats : PR_FC);
-  const int ld = fc | 1;
-  const size_t lds_bytes = ((size_t)PR_ROWS * ld + (size_t)fc * PR_PASS) * sizeof(float);
   const double tau = (lpd && kind == STEIN_GLM_LINEAR) ? noise_precision : 1.0;
   hipStream_t s = (hipStream_t)stream;
   if (pw.on && (summary || pw.ess))
@@ -652,13 +464,14 @@ static int predict_glm(const float* theta, int64_t n, int64_t d, int kind, int o
   if (!pred && !summary) return STEIN_OK;   // ess alone
   float* part = summary ? predict_states(pl, workspace, pw) : nullptr;
   const double* head = (pw.on && summary) ? (const double*)workspace : nullptr;
+  const PredGlmTile tile = predict_glm_tile(n_feats, head != nullptr);   // weighted: the pass's weights behind the tile
 #define PR_LAUNCH_GLM(WEIGHTED, LDS)                                                                                    \
   hipLaunchKernelGGL(k_predict_glm<WEIGHTED>, dim3((unsigned)pl.row_tiles, (unsigned)pl.slices), dim3(256), LDS, s, theta, \
-                     (int)n, (int)d, kind, output, (int)w_col, (int)n_feats, fc, ld, X, y, (int)batch, pl.per,            \
+                     (int)n, (int)d, kind, output, (int)w_col, (int)n_feats, tile.fc, tile.ld, X, y, (int)batch, pl.per,  \
                      (float)(0.5 * tau), (float)(0.5 * log(tau) - (double)PR_HALF_LOG_2PI), pred, part,                   \
                      (mean || var) ? 1 : 0, lpd ? 1 : 0, pw.w, head)
-  if (head) PR_LAUNCH_GLM(true, lds_bytes + PR_PASS * sizeof(float));
-  else PR_LAUNCH_GLM(false, lds_bytes);
+  if (head) PR_LAUNCH_GLM(true, tile.bytes);
+  else PR_LAUNCH_GLM(false, tile.bytes);
 #undef PR_LAUNCH_GLM
   LAUNCH_CHECK("k_predict_glm");
   return summary ? predict_finish(pl, n, batch, part, mean, var, lpd, head, s) : STEIN_OK;
@@ -669,14 +482,11 @@ static int predict_bnn(const float* theta, int64_t n, int64_t d, int64_t n_in, i
                        float* lpd, void* workspace, size_t ws_bytes, void* stream, const PredWeights& pw) {
   if (!cols) return stein_fail(STEIN_E_BADARG, "NULL pointer");
   if (int rc = predict_check(theta, X, y, n, d, batch, n_hidden, output, pred, mean, var, lpd, pw)) return rc;
-  if (n_in < 1) return stein_fail(STEIN_E_SHAPE, "bad shape n_in=%lld", (long long)n_in);
-  if (n_in > PR_NIN_MAX) return stein_fail(STEIN_E_UNSUPPORTED, "more than %d input features", PR_NIN_MAX);
-  if (n_hidden > PR_WIDTH_MAX) return stein_fail(STEIN_E_UNSUPPORTED, "more than 1024 hidden units");
-  if (int rc = predict_check_cols(cols, n_in, n_hidden, d)) return rc;
+  if (int rc = predict_check_bnn(n_in, n_hidden, cols, d)) return rc;
   const bool summary = mean || var || lpd;
   if (int rc = predict_check_ws(n, batch, summary || pw.ess, workspace, ws_bytes, pw)) return rc;
   const PredPlan pl = predict_plan(n, batch);
-  const PredCols c = {(int)cols[0], (int)cols[1], (int)cols[2], (int)cols[3], (int)cols[5]};
+  const PredCols c = predict_cols(cols);
   hipStream_t s = (hipStream_t)stream;
   if (pw.on && (summary || pw.ess))
     if (int rc = predict_weight_pass(pl, n, pw, workspace, s)) return rc;
@@ -733,4 +543,3 @@ extern "C" int stein_predict_bnn_weighted(const float* theta, int64_t n, int64_t
   return predict_bnn(theta, n, d, n_in, n_hidden, cols, output, X, y, batch, pred, mean, var, lpd, workspace, ws_bytes, stream,
                      PredWeights{true, weights, ess});
 }
-#endif  // STEIN_PREDICT_SHARED_ONLY

@@ -1,10 +1,11 @@
 // stein_predict_ranks.hip -- order statistics of the posterior predictive outputs: credible bands and the ensemble median per
 // test point without the [n][batch] matrix (stein_predict_glm_ranks / stein_predict_bnn_ranks of include/steinhip.h).
-// The forward passes, the plan and the argument checks are stein_predict.hip's own: this file includes that source up to its
-// weight pass (STEIN_PREDICT_SHARED_ONLY), so a counted value is bit for bit the value pred holds, and it is built with the
+// The forward passes, the plan and the argument checks are the summary kernels' own (stein_predict_fwd.h, which
+// stein_predict.hip includes too), so a counted value is bit for bit the value pred holds, and this file is built with the
 // same flags.  A source of its own because it sums integer counts with atomics, which the summary kernels must not use.
-#define STEIN_PREDICT_SHARED_ONLY
-#include "stein_predict.hip"
+// One counting kernel per model, k_predict_glm_ranks<MASS, ..> and k_predict_bnn_ranks<NIN, MASS, ..>: MASS = false counts
+// every output as 1 (stein_predict_*_ranks), MASS = true adds its particle's integer mass (stein_predict_*_ranks_weighted).
+#include "stein_predict_fwd.h"
 
 // ---- order statistics of the outputs (stein_predict_*_ranks) ------------------------------------------------
 // out[i][b] = the ranks[i]-th smallest of f_pb over the particles, by a radix select over the 32-bit keys f32_key(f) (every
@@ -61,42 +62,87 @@ __device__ __forceinline__ void pq_begin(PredCount& pc, u32* hist_lds, const u32
   }
 }
 
-__device__ __forceinline__ void pq_count(const PredCount& pc, float f) {
+// ---- weighted order statistics (stein_predict_*_ranks_weighted) --------------------------------------------------------
+// The same select with every output adding its particle's mass m_p (a u32) in place of 1: out[i][b] is the smallest f_pb of
+// a particle with m_p > 0 at which the running mass passes the target max(0, ceil(q_i M) - 1), M = sum m_p < 2^32.  All sums
+// are integer sums, so everything the unweighted select promises carries over.  The masses of a pass's PR_PASS particles are
+// staged beside the particle data and read at one address by every lane; a particle of mass 0 is skipped.  A lane's counters
+// are whole words, [R][2^bits] of them and a word of padding (an odd stride): M < 2^32, so none can overflow and they are
+// flushed once, at the slice's end.  The narrow step and the leaders are the unweighted call's own kernel, launched with
+// ranks of zero; k_predict_wranks_targets then puts each level's target where that kernel put the rank.  The workspace is
+// the unweighted call's behind a header of PQW_MPARTS 64-bit words: the partial sums of the masses that
+// k_predict_wranks_msum leaves, and in the last word the poison flag -- M = 0 or M >= 2^32 (the masses are not trusted):
+// the counting kernels then count nothing, every level takes its top digit, and the call ends on the NaN key.
+constexpr int PQW_MPARTS = 64;   // the header's words: at most PQW_MPARTS - 1 workgroups of k_predict_wranks_msum, then the flag
+
+struct PredLevels { double q[STEIN_PRED_RANKS_MAX]; };
+
+// ---- the counters of a lane and the counting kernels, both selects ----------------------------------------------------------
+// MASS = false: four byte counters to an LDS word (pc.wpr = a quarter of the level's bins), the output counts 1.
+// MASS = true: a word per bin (pc.wpr = the level's bins), the output adds its particle's mass m; mass 0 is skipped.
+template <bool MASS>
+__device__ __forceinline__ void pq_count(const PredCount& pc, float f, u32 m) {
+  if (MASS && m == 0u) return;
   const u32 key = pq_key(f);
   const u32 dg = (key >> pc.shift) & pc.top;
-  const u32 inc = 1u << (8u * (dg & 3u));
-  u32* h = pc.hist + (dg >> 2);
+  const u32 inc = MASS ? m : 1u << (8u * (dg & 3u));
+  u32* h = pc.hist + (MASS ? dg : dg >> 2);
 #pragma unroll
   for (int i = 0; i < STEIN_PRED_RANKS_MAX; ++i)
     if ((pc.lead >> i & 1u) && ((key ^ pc.prefix[i]) & pc.mask) == 0u) atomicAdd(h + i * pc.wpr, inc);
 }
 
-// the lane's non-zero counters added to the totals [R][PQ_BINS][B] and cleared
+// the lane's non-zero counters added to the totals [R][PQ_BINS][B]; the byte counters are flushed more than once and cleared
+template <bool MASS>
 __device__ __forceinline__ void pq_flush(const PredCount& pc, int R, u32* __restrict__ tot, int B, int row) {
   for (int i = 0; i < R; ++i) {
     if (!(pc.lead >> i & 1u)) continue;
     for (int w = 0; w < pc.wpr; ++w) {
       const u32 v = pc.hist[i * pc.wpr + w];
       if (v == 0u) continue;
-      pc.hist[i * pc.wpr + w] = 0u;
+      if constexpr (MASS) {
+        atomicAdd(tot + (size_t)(i * PQ_BINS + w) * B + row, v);
+      } else {
+        pc.hist[i * pc.wpr + w] = 0u;
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const u32 c = (v >> (8 * q)) & 255u;
-        if (c) atomicAdd(tot + (size_t)(i * PQ_BINS + 4 * w + q) * B + row, c);
+        for (int q = 0; q < 4; ++q) {
+          const u32 c = (v >> (8 * q)) & 255u;
+          if (c) atomicAdd(tot + (size_t)(i * PQ_BINS + 4 * w + q) * B + row, c);
+        }
       }
     }
   }
 }
 
-// st: the call's workspace, [prefix | remaining | leader][R][B] then the totals [R][PQ_BINS][B].  The dynamic LDS continues
-// k_predict_glm's: the X tile, the staged weights, then the counters [PR_ROWS][4 R + 1].
+// the two arguments a counting kernel takes with MASS only (restrict, as kernel arguments are throughout), and their
+// accessors out of the kernel's pack (nothing in it: the unweighted kernel)
+using PredMasses = const u32* __restrict__;
+using PredPoison = const u64* __restrict__;
+__device__ __forceinline__ const u32* pq_masses(const u32* masses, const u64*) { return masses; }
+__device__ __forceinline__ const u32* pq_masses() { return nullptr; }
+__device__ __forceinline__ const u64* pq_poison(const u32*, const u64* poison) { return poison; }
+
+// st: the call's select state, [prefix | remaining | leader][R][B] then the totals [R][PQ_BINS][B].  The dynamic LDS continues
+// k_predict_glm's: the X tile, the staged weights, with MASS the pass's PR_PASS masses, then the counters [PR_ROWS][R wpr + 1].
+// Mass...: with MASS (PredMasses masses [n], PredPoison poison -- the flag of the workspace's header: the whole grid counts
+// nothing), without it no argument at all.  A pack and not two pointers that the unweighted kernels would carry unused, and
+// `if constexpr` wherever MASS decides, so that an instantiation names nothing of the other's: with either the generated
+// prologue changes, and a prologue two to eight instructions longer cost the GLM kernel 0.5 to 2.7 % of its time
+// (profiles/predict_ranks_unify_ab.txt, C).  For the same reason the unweighted counters' address is formed where it is used.
+template <bool MASS, class... Mass>
 __global__ __launch_bounds__(256) void k_predict_glm_ranks(const float* __restrict__ theta, int n, int d, int kind, int output,
                                                            int w_col, int F, int fc, int ld, const float* __restrict__ X,
-                                                           int B, int per, u32* __restrict__ st, int R, int shift, int width,
-                                                           int wpr) {
+                                                           int B, int per, Mass... mass, u32* __restrict__ st, int R,
+                                                           int shift, int width, int wpr) {
+  static_assert(sizeof...(Mass) == (MASS ? 2 : 0), "masses and poison with MASS, nothing without");
+  const u32* __restrict__ masses = pq_masses(mass...);
+  if constexpr (MASS) {
+    if (*pq_poison(mass...)) return;
+  }
   extern __shared__ float lds[];
   float* xs = lds;                   // [PR_ROWS][ld]
   float* ws = lds + PR_ROWS * ld;    // [fc][PR_PASS]
+  u32* ml = MASS ? reinterpret_cast<u32*>(ws + fc * PR_PASS) : nullptr;   // [PR_PASS], MASS only
   const int t = threadIdx.x;
   const int row0 = blockIdx.x * PR_ROWS, row = row0 + t;
   const bool live = row < B;
@@ -104,23 +150,38 @@ __global__ __launch_bounds__(256) void k_predict_glm_ranks(const float* __restri
   const bool sigmoid = kind == STEIN_GLM_LOGISTIC && output == STEIN_PRED_MEAN;
   u32* tot = st + (size_t)3 * R * B;
   PredCount pc;
-  pq_begin(pc, reinterpret_cast<u32*>(ws + fc * PR_PASS), st, R, B, row, live, shift, width, wpr, t);
+  pq_begin(pc, MASS ? ml + PR_PASS : reinterpret_cast<u32*>(ws + fc * PR_PASS), st, R, B, row, live, shift, width, wpr, t);
   pred_glm_slice(
-      theta, d, w_col, F, fc, ld, X, B, row0, p_begin, p_end, xs, ws, t, [](int, int) {},
+      theta, d, w_col, F, fc, ld, X, B, row0, p_begin, p_end, xs, ws, t,
+      [&](int p0, int cnt) {
+        if constexpr (MASS) {
+          if (t < PR_PASS) ml[t] = t < cnt ? masses[p0 + t] : 0u;
+        }
+      },
       [&](int p0, int k, float zz) {
-        if (k == 0 && p0 > p_begin && ((p0 - p_begin) / PR_PASS) % PQ_FLUSH == 0) pq_flush(pc, R, tot, B, row);
-        pq_count(pc, pred_glm_output(zz, sigmoid));
+        if constexpr (!MASS) {   // the byte counters, every PQ_FLUSH passes
+          if (k == 0 && p0 > p_begin && ((p0 - p_begin) / PR_PASS) % PQ_FLUSH == 0) pq_flush<MASS>(pc, R, tot, B, row);
+        }
+        const float f = pred_glm_output(zz, sigmoid);
+        if constexpr (MASS) pq_count<MASS>(pc, f, ml[k]);
+        else pq_count<MASS>(pc, f, 0u);
       });
-  pq_flush(pc, R, tot, B, row);
+  pq_flush<MASS>(pc, R, tot, B, row);
 }
 
-template <int NIN>
+// The counters [PR_ROWS][R wpr + 1] are the dynamic LDS; with MASS a particle's mass travels as the bits of lp[k][3].
+template <int NIN, bool MASS, class... Mass>
 __global__ __launch_bounds__(256) void k_predict_bnn_ranks(const float* __restrict__ theta, int n, int d, int H, PredCols c,
-                                                           const float* __restrict__ X, int B, int per, u32* __restrict__ st,
-                                                           int R, int shift, int width, int wpr) {
+                                                           const float* __restrict__ X, int B, int per, Mass... mass,
+                                                           u32* __restrict__ st, int R, int shift, int width, int wpr) {
+  static_assert(sizeof...(Mass) == (MASS ? 2 : 0), "masses and poison with MASS, nothing without");
+  const u32* __restrict__ masses = pq_masses(mass...);
+  if constexpr (MASS) {
+    if (*pq_poison(mass...)) return;
+  }
   __shared__ __attribute__((aligned(16))) float lw[PR_PASS * PR_BNN_PW<NIN>];
-  __shared__ float lp[PR_PASS][4];
-  extern __shared__ u32 hist_lds[];   // [PR_ROWS][4 R + 1]
+  __shared__ float lp[PR_PASS][4];    // per particle: b2, two words of the likelihood (unused here), MASS: its mass
+  extern __shared__ u32 hist_lds[];
   const int t = threadIdx.x;
   const int row = blockIdx.x * PR_ROWS + t;
   const bool live = row < B;
@@ -131,22 +192,29 @@ __global__ __launch_bounds__(256) void k_predict_bnn_ranks(const float* __restri
   u32* tot = st + (size_t)3 * R * B;
   PredCount pc;
   pq_begin(pc, hist_lds, st, R, B, row, live, shift, width, wpr, t);
-  int since = 0;
+  int since = 0;   // passes since the byte counters' last flush
   for (int p0 = p_begin; p0 < p_end; p0 += PR_PASS) {
     const int cnt = min(PR_PASS, p_end - p0);
     float z[PR_PASS];
 #pragma unroll
     for (int k = 0; k < PR_PASS; ++k) z[k] = 0.f;
-    pred_bnn_pass<NIN>(z, theta, d, H, c, x, p0, cnt, lw, lp, t, [](int) {});
+    pred_bnn_pass<NIN>(z, theta, d, H, c, x, p0, cnt, lw, lp, t, [&](int k) {
+      if constexpr (MASS) lp[k][3] = __uint_as_float(masses[p0 + k]);
+    });
 #pragma unroll
     for (int k = 0; k < PR_PASS; ++k)
-      if (k < cnt) pq_count(pc, z[k] + lp[k][0]);
-    if (++since == PQ_FLUSH) {
-      pq_flush(pc, R, tot, B, row);
-      since = 0;
+      if (k < cnt) {
+        if constexpr (MASS) pq_count<MASS>(pc, z[k] + lp[k][0], __float_as_uint(lp[k][3]));
+        else pq_count<MASS>(pc, z[k] + lp[k][0], 0u);
+      }
+    if constexpr (!MASS) {
+      if (++since == PQ_FLUSH) {
+        pq_flush<MASS>(pc, R, tot, B, row);
+        since = 0;
+      }
     }
   }
-  pq_flush(pc, R, tot, B, row);
+  pq_flush<MASS>(pc, R, tot, B, row);
 }
 
 // One thread per row, all of its ranks.  width 0 (the call's first launch): prefix 0, the ranks asked for, every rank led by rank 0, totals zero.
@@ -207,21 +275,7 @@ __global__ __launch_bounds__(256) void k_predict_ranks_narrow(u32* __restrict__ 
   }
 }
 
-// ---- weighted order statistics (stein_predict_*_ranks_weighted) --------------------------------------------------------
-// The same select with every output adding its particle's mass m_p (a u32) in place of 1: out[i][b] is the smallest f_pb of
-// a particle with m_p > 0 at which the running mass passes the target max(0, ceil(q_i M) - 1), M = sum m_p < 2^32.  All sums
-// are integer sums, so everything the unweighted select promises carries over.  The masses of a pass's PR_PASS particles are
-// staged beside the particle data and read at one address by every lane; a particle of mass 0 is skipped.  A lane's counters
-// are whole words, [R][2^bits] of them and a word of padding (an odd stride): M < 2^32, so none can overflow and they are
-// flushed once, at the slice's end.  The narrow step and the leaders are the unweighted call's own kernel, launched with
-// ranks of zero; k_predict_wranks_targets then puts each level's target where that kernel put the rank.  The workspace is
-// the unweighted call's behind a header of PQW_MPARTS 64-bit words: the partial sums of the masses that
-// k_predict_wranks_msum leaves, and in the last word the poison flag -- M = 0 or M >= 2^32 (the masses are not trusted):
-// the counting kernels then count nothing, every level takes its top digit, and the call ends on the NaN key.
-constexpr int PQW_MPARTS = 64;   // the header's words: at most PQW_MPARTS - 1 workgroups of k_predict_wranks_msum, then the flag
-
-struct PredLevels { double q[STEIN_PRED_RANKS_MAX]; };
-
+// the weighted select's header: up to PQW_MPARTS - 1 workgroups leave the partial sums of the masses, folded by halving
 __global__ __launch_bounds__(256) void k_predict_wranks_msum(const u32* __restrict__ masses, int n, u64* __restrict__ mpart) {
   __shared__ u64 sh[256];
   const int t = threadIdx.x;
@@ -250,86 +304,6 @@ __global__ __launch_bounds__(256) void k_predict_wranks_targets(u32* __restrict_
     const double c = ceil(levels.q[i] * (double)M);   // <= M < 2^32 unless the call is poisoned
     rem[(size_t)i * B] = (poisoned || c < 1.0) ? 0u : (u32)(c - 1.0);
   }
-}
-
-__device__ __forceinline__ void pqw_count(const PredCount& pc, float f, u32 m) {
-  if (m == 0u) return;
-  const u32 key = pq_key(f);
-  u32* h = pc.hist + ((key >> pc.shift) & pc.top);
-#pragma unroll
-  for (int i = 0; i < STEIN_PRED_RANKS_MAX; ++i)
-    if ((pc.lead >> i & 1u) && ((key ^ pc.prefix[i]) & pc.mask) == 0u) atomicAdd(h + i * pc.wpr, m);
-}
-
-// the lane's non-zero counters (pc.wpr = the level's bins: a word each) added to the totals [R][PQ_BINS][B]
-__device__ __forceinline__ void pqw_flush(const PredCount& pc, int R, u32* __restrict__ tot, int B, int row) {
-  for (int i = 0; i < R; ++i) {
-    if (!(pc.lead >> i & 1u)) continue;
-    for (int b = 0; b < pc.wpr; ++b) {
-      const u32 v = pc.hist[i * pc.wpr + b];
-      if (v) atomicAdd(tot + (size_t)(i * PQ_BINS + b) * B + row, v);
-    }
-  }
-}
-
-// The dynamic LDS: the X tile, the staged weights, the pass's PR_PASS masses, then the counters [PR_ROWS][R 2^bits + 1].
-__global__ __launch_bounds__(256) void k_predict_glm_wranks(const float* __restrict__ theta, int n, int d, int kind, int output,
-                                                            int w_col, int F, int fc, int ld, const float* __restrict__ X,
-                                                            int B, int per, const u32* __restrict__ masses,
-                                                            const u64* __restrict__ poison, u32* __restrict__ st, int R,
-                                                            int shift, int width, int bins) {
-  if (*poison) return;               // the whole grid: nothing is counted
-  extern __shared__ float lds[];
-  float* xs = lds;                   // [PR_ROWS][ld]
-  float* ws = lds + PR_ROWS * ld;    // [fc][PR_PASS]
-  u32* ml = reinterpret_cast<u32*>(ws + fc * PR_PASS);   // [PR_PASS]
-  const int t = threadIdx.x;
-  const int row0 = blockIdx.x * PR_ROWS, row = row0 + t;
-  const bool live = row < B;
-  const int p_begin = blockIdx.y * per, p_end = min(n, p_begin + per);
-  const bool sigmoid = kind == STEIN_GLM_LOGISTIC && output == STEIN_PRED_MEAN;
-  u32* tot = st + (size_t)3 * R * B;
-  PredCount pc;
-  pq_begin(pc, ml + PR_PASS, st, R, B, row, live, shift, width, bins, t);
-  pred_glm_slice(
-      theta, d, w_col, F, fc, ld, X, B, row0, p_begin, p_end, xs, ws, t,
-      [&](int p0, int cnt) {
-        if (t < PR_PASS) ml[t] = t < cnt ? masses[p0 + t] : 0u;
-      },
-      [&](int, int k, float zz) { pqw_count(pc, pred_glm_output(zz, sigmoid), ml[k]); });
-  pqw_flush(pc, R, tot, B, row);
-}
-
-template <int NIN>
-__global__ __launch_bounds__(256) void k_predict_bnn_wranks(const float* __restrict__ theta, int n, int d, int H, PredCols c,
-                                                            const float* __restrict__ X, int B, int per,
-                                                            const u32* __restrict__ masses, const u64* __restrict__ poison,
-                                                            u32* __restrict__ st, int R, int shift, int width, int bins) {
-  if (*poison) return;                // the whole grid: nothing is counted
-  __shared__ __attribute__((aligned(16))) float lw[PR_PASS * PR_BNN_PW<NIN>];
-  __shared__ float lp[PR_PASS][4];    // per particle: b2, two words of the likelihood (unused here), its mass (as bits)
-  extern __shared__ u32 hist_lds[];   // [PR_ROWS][R 2^bits + 1]
-  const int t = threadIdx.x;
-  const int row = blockIdx.x * PR_ROWS + t;
-  const bool live = row < B;
-  const int p_begin = blockIdx.y * per, p_end = min(n, p_begin + per);
-  float x[NIN];
-#pragma unroll
-  for (int f = 0; f < NIN; ++f) x[f] = live ? X[(size_t)row * NIN + f] : 0.f;
-  u32* tot = st + (size_t)3 * R * B;
-  PredCount pc;
-  pq_begin(pc, hist_lds, st, R, B, row, live, shift, width, bins, t);
-  for (int p0 = p_begin; p0 < p_end; p0 += PR_PASS) {
-    const int cnt = min(PR_PASS, p_end - p0);
-    float z[PR_PASS];
-#pragma unroll
-    for (int k = 0; k < PR_PASS; ++k) z[k] = 0.f;
-    pred_bnn_pass<NIN>(z, theta, d, H, c, x, p0, cnt, lw, lp, t, [&](int k) { lp[k][3] = __uint_as_float(masses[p0 + k]); });
-#pragma unroll
-    for (int k = 0; k < PR_PASS; ++k)
-      if (k < cnt) pqw_count(pc, z[k] + lp[k][0], __float_as_uint(lp[k][3]));
-  }
-  pqw_flush(pc, R, tot, B, row);
 }
 
 // ---- host side -----------------------------------------------------------------------------------------
@@ -374,11 +348,18 @@ static int predict_ranks_check_tail(const int64_t* ranks, int64_t n_ranks, int64
   return STEIN_OK;
 }
 
-static int predict_ranks_narrow(u32* st, int R, int64_t batch, int shift, int width, const PredRanks& pr, float* out,
-                                hipStream_t s) {
-  hipLaunchKernelGGL(k_predict_ranks_narrow, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, st, R, (int)batch, shift,
-                     width, pr, out);
-  LAUNCH_CHECK("k_predict_ranks_narrow");
+static size_t predict_wranks_ws_bytes(int64_t batch, int64_t n_levels) {
+  return (size_t)PQW_MPARTS * sizeof(u64) + predict_ranks_ws_bytes(batch, n_levels);
+}
+
+extern "C" int stein_predict_ranks_weighted_workspace_bytes(int64_t n, int64_t batch, int64_t n_levels, size_t* out_bytes) {
+  if (!out_bytes) return stein_fail(STEIN_E_BADARG, "NULL pointer");
+  if (n_levels < 1) return stein_fail(STEIN_E_BADARG, "n_levels %lld", (long long)n_levels);
+  if (n < 1 || batch < 1 || n > PR_COUNT_MAX || batch > PR_COUNT_MAX)
+    return stein_fail(STEIN_E_SHAPE, "bad shape n=%lld batch=%lld", (long long)n, (long long)batch);
+  if (n_levels > STEIN_PRED_RANKS_MAX)
+    return stein_fail(STEIN_E_UNSUPPORTED, "more than %d levels per call", (int)STEIN_PRED_RANKS_MAX);
+  *out_bytes = predict_wranks_ws_bytes(batch, n_levels);
   return STEIN_OK;
 }
 
@@ -402,105 +383,17 @@ static PredPlan predict_ranks_plan(int64_t n, int64_t batch) {
   return p;
 }
 
-// the counters of a counting workgroup: per lane 2^bits bytes per rank and a word of padding (an odd stride)
-static size_t predict_ranks_lds(int R, int bits) { return (size_t)PR_ROWS * (R * ((1 << bits) / 4) + 1) * sizeof(u32); }
+// the counters of a counting workgroup: per lane and rank 2^bits bytes, or with masses 2^bits words, and per lane a word of
+// padding (an odd stride)
+static int predict_ranks_wpr(int bits, bool mass) { return mass ? 1 << bits : (1 << bits) / 4; }
+static size_t predict_ranks_lds(int R, int bits, bool mass) {
+  return (size_t)PR_ROWS * (R * predict_ranks_wpr(bits, mass) + 1) * sizeof(u32);
+}
 constexpr size_t PQ_LDS_HALF_CU = 80 * 1024;   // two workgroups per CU fit below this
-
-extern "C" int stein_predict_glm_ranks(const float* theta, int64_t n, int64_t d, int kind, int output, int64_t w_col,
-                                       int64_t n_feats, const float* X, int64_t batch, const int64_t* ranks, int64_t n_ranks,
-                                       float* out, void* workspace, size_t ws_bytes, void* stream) {
-  if (int rc = predict_ranks_check(theta, X, ranks, n_ranks, out, n, d, batch, n_feats, output)) return rc;
-  if (kind != STEIN_GLM_LINEAR && kind != STEIN_GLM_LOGISTIC) return stein_fail(STEIN_E_BADARG, "kind %d", kind);
-  if (w_col < 0 || w_col + n_feats > d)
-    return stein_fail(STEIN_E_SHAPE, "weights [%lld, %lld) do not fit d=%lld", (long long)w_col, (long long)(w_col + n_feats),
-                      (long long)d);
-  if (n_feats > PR_WIDTH_MAX) return stein_fail(STEIN_E_UNSUPPORTED, "more than 1024 features per particle");
-  PredRanks pr = {};
-  if (int rc = predict_ranks_check_tail(ranks, n_ranks, n, batch, workspace, ws_bytes, pr)) return rc;
-  const PredPlan pl = predict_ranks_plan(n, batch);
-  const int R = (int)n_ranks;
-  const int fc = (int)(n_feats <= PR_FC ? n_feats : PR_FC);
-  const int ld = fc | 1;
-  // The X tile and the counters share the CU's 160 KiB.  With 4 bits a level, five or more ranks beside a wide tile leave
-  // room for one workgroup per CU only, which doubled the call's time; 3 bits a level (11 levels instead of 8) halve the
-  // counters and keep two.  Both give the same bits of the same order statistic.
-  const size_t tile_bytes = ((size_t)PR_ROWS * ld + (size_t)fc * PR_PASS) * sizeof(float);
-  const int bits = (tile_bytes + predict_ranks_lds(R, PQ_BITS) > PQ_LDS_HALF_CU &&
-                    tile_bytes + predict_ranks_lds(R, PQ_BITS - 1) <= PQ_LDS_HALF_CU) ? PQ_BITS - 1 : PQ_BITS;
-  const size_t lds_bytes = tile_bytes + predict_ranks_lds(R, bits);
-  // up to 96.5 KB of dynamic LDS, past the default 64 KB: the attribute belongs to the function on one device (as in
-  // stein_small_phi: a flag per device id; racing threads at worst set it twice)
-  static bool attr_set[64] = {false};
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_predict_glm_ranks), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                100 * 1024));
-    if (dev >= 0 && dev < 64) attr_set[dev] = true;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  u32* st = (u32*)workspace;
-  if (int rc = predict_ranks_narrow(st, R, batch, 32, 0, pr, out, s)) return rc;
-  for (int hi = 32; hi > 0;) {   // the key's bits from the top, `bits` at a time (the last level takes what is left)
-    const int width = bits < hi ? bits : hi, shift = hi - width;
-    hipLaunchKernelGGL(k_predict_glm_ranks, dim3((unsigned)pl.row_tiles, (unsigned)pl.slices), dim3(256), lds_bytes, s, theta,
-                       (int)n, (int)d, kind, output, (int)w_col, (int)n_feats, fc, ld, X, (int)batch, pl.per, st, R, shift, width,
-                       (1 << bits) / 4);
-    LAUNCH_CHECK("k_predict_glm_ranks");
-    if (int rc = predict_ranks_narrow(st, R, batch, shift, width, pr, out, s)) return rc;
-    hi = shift;
-  }
-  return STEIN_OK;
-}
-
-extern "C" int stein_predict_bnn_ranks(const float* theta, int64_t n, int64_t d, int64_t n_in, int64_t n_hidden,
-                                       const int64_t* cols, int output, const float* X, int64_t batch, const int64_t* ranks,
-                                       int64_t n_ranks, float* out, void* workspace, size_t ws_bytes, void* stream) {
-  if (!cols) return stein_fail(STEIN_E_BADARG, "NULL pointer");
-  if (int rc = predict_ranks_check(theta, X, ranks, n_ranks, out, n, d, batch, n_hidden, output)) return rc;
-  if (n_in < 1) return stein_fail(STEIN_E_SHAPE, "bad shape n_in=%lld", (long long)n_in);
-  if (n_in > PR_NIN_MAX) return stein_fail(STEIN_E_UNSUPPORTED, "more than %d input features", PR_NIN_MAX);
-  if (n_hidden > PR_WIDTH_MAX) return stein_fail(STEIN_E_UNSUPPORTED, "more than 1024 hidden units");
-  if (int rc = predict_check_cols(cols, n_in, n_hidden, d)) return rc;
-  PredRanks pr = {};
-  if (int rc = predict_ranks_check_tail(ranks, n_ranks, n, batch, workspace, ws_bytes, pr)) return rc;
-  const PredPlan pl = predict_ranks_plan(n, batch);
-  const int R = (int)n_ranks;
-  const PredCols c = {(int)cols[0], (int)cols[1], (int)cols[2], (int)cols[3], (int)cols[5]};
-  const size_t lds_bytes = predict_ranks_lds(R, PQ_BITS);   // beside at most 24.8 KB of static LDS: below 64 KB, two per CU
-  hipStream_t s = (hipStream_t)stream;
-  u32* st = (u32*)workspace;
-  if (int rc = predict_ranks_narrow(st, R, batch, 32, 0, pr, out, s)) return rc;
-  for (int shift = 32 - PQ_BITS; shift >= 0; shift -= PQ_BITS) {
-#define PQ_LAUNCH_BNN(NIN)                                                                                              \
-  hipLaunchKernelGGL(k_predict_bnn_ranks<NIN>, dim3((unsigned)pl.row_tiles, (unsigned)pl.slices), dim3(256), lds_bytes, s, \
-                     theta, (int)n, (int)d, (int)n_hidden, c, X, (int)batch, pl.per, st, R, shift, PQ_BITS, PQ_BINS / 4)
-    if (n_in == 1) PQ_LAUNCH_BNN(1);
-    else if (n_in == 2) PQ_LAUNCH_BNN(2);
-    else if (n_in == 3) PQ_LAUNCH_BNN(3);
-    else PQ_LAUNCH_BNN(4);
-#undef PQ_LAUNCH_BNN
-    LAUNCH_CHECK("k_predict_bnn_ranks");
-    if (int rc = predict_ranks_narrow(st, R, batch, shift, PQ_BITS, pr, out, s)) return rc;
-  }
-  return STEIN_OK;
-}
-
-// ---- weighted order statistics: host side ---------------------------------------------------------------------
-static size_t predict_wranks_ws_bytes(int64_t batch, int64_t n_levels) {
-  return (size_t)PQW_MPARTS * sizeof(u64) + predict_ranks_ws_bytes(batch, n_levels);
-}
-
-extern "C" int stein_predict_ranks_weighted_workspace_bytes(int64_t n, int64_t batch, int64_t n_levels, size_t* out_bytes) {
-  if (!out_bytes) return stein_fail(STEIN_E_BADARG, "NULL pointer");
-  if (n_levels < 1) return stein_fail(STEIN_E_BADARG, "n_levels %lld", (long long)n_levels);
-  if (n < 1 || batch < 1 || n > PR_COUNT_MAX || batch > PR_COUNT_MAX)
-    return stein_fail(STEIN_E_SHAPE, "bad shape n=%lld batch=%lld", (long long)n, (long long)batch);
-  if (n_levels > STEIN_PRED_RANKS_MAX)
-    return stein_fail(STEIN_E_UNSUPPORTED, "more than %d levels per call", (int)STEIN_PRED_RANKS_MAX);
-  *out_bytes = predict_wranks_ws_bytes(batch, n_levels);
-  return STEIN_OK;
-}
+constexpr size_t PQW_LDS_CU = 160 * 1024;   // what one workgroup can have: the CU's whole LDS
+constexpr int PQW_CUS = 256;                // compute units of the card the rule below was measured on
+// the network kernels' static LDS, lw and lp: at most 24.8 KB
+static size_t predict_bnn_lds_static(int64_t n_in) { return ((size_t)PR_PASS * (n_in + 2) * PR_HC + PR_PASS * 4) * sizeof(float); }
 
 static thread_local int g_wranks_bits = 0;   // stein_debug_predict_ranks_weighted_bits: 0 = the rule of predict_wranks_bits
 
@@ -509,11 +402,6 @@ extern "C" int stein_debug_predict_ranks_weighted_bits(int bits) {
   g_wranks_bits = bits;
   return STEIN_OK;
 }
-
-// the word counters of a weighted counting workgroup: per lane 2^bits words per level and a word of padding
-static size_t predict_wranks_lds(int R, int bits) { return (size_t)PR_ROWS * (R * (1 << bits) + 1) * sizeof(u32); }
-constexpr size_t PQW_LDS_CU = 160 * 1024;   // what one workgroup can have: the CU's whole LDS
-constexpr int PQW_CUS = 256;                // compute units of the card the rule below was measured on
 
 // The digit width of a weighted call, or the hook's.  Measured (profiles/predict_wquantile_ab.txt): a call's time is its
 // forward passes, ceil(32 / bits), times a pass's time, and a pass runs 1.9 times faster with two workgroups resident on a
@@ -524,7 +412,7 @@ static int predict_wranks_bits(int R, size_t other_bytes, int64_t workgroups) {
   if (g_wranks_bits > 0) return g_wranks_bits;
   int best = 1, best_cost = 1 << 30;
   for (int bits = PQ_BITS; bits >= 1; --bits) {
-    const size_t lds = other_bytes + predict_wranks_lds(R, bits);
+    const size_t lds = other_bytes + predict_ranks_lds(R, bits, true);
     if (lds > PQW_LDS_CU) continue;
     const int passes = (32 + bits - 1) / bits;
     const int cost = (workgroups > PQW_CUS && 2 * lds <= PQW_LDS_CU) ? passes : 2 * passes;
@@ -536,7 +424,17 @@ static int predict_wranks_bits(int R, size_t other_bytes, int64_t workgroups) {
   return best;
 }
 
-// the checks of a weighted ranks call behind the model's own: the level count, every level, the workspace, the hook's width
+// the checks of a weighted ranks call that do not depend on the model: up to and including the shapes ...
+static int predict_wranks_check(const float* theta, const float* X, const uint32_t* masses, const double* levels,
+                                int64_t n_levels, const float* out, int64_t n, int64_t d, int64_t batch, int64_t width,
+                                int output) {
+  if (!theta || !X || !masses || !levels || !out) return stein_fail(STEIN_E_BADARG, "NULL pointer");
+  if (n_levels < 1) return stein_fail(STEIN_E_BADARG, "n_levels %lld", (long long)n_levels);
+  return predict_check(theta, X, nullptr, n, d, batch, width, output, out, nullptr, nullptr, nullptr,
+                       PredWeights{false, nullptr, nullptr});
+}
+
+// ... and behind the model's own: the level count, every level, the workspace, the hook's width
 static int predict_wranks_check_tail(const double* levels, int64_t n_levels, int64_t batch, const void* workspace,
                                      size_t ws_bytes, size_t lds_total, PredLevels& lv) {
   if (n_levels > STEIN_PRED_RANKS_MAX)
@@ -556,10 +454,26 @@ static int predict_wranks_check_tail(const double* levels, int64_t n_levels, int
   return STEIN_OK;
 }
 
-// past the default 64 KB of LDS a kernel needs the attribute, which belongs to the function on one device (as above);
-// lds_dynamic: the most the kernel can be given beside its static LDS
-static int predict_wranks_attr(const void* fn, int slot, size_t lds_dynamic) {
-  static bool attr_set[5][64] = {{false}};
+// ---- the launches of a call past its checks, both selects -------------------------------------------------------------------
+// masses = nullptr: the unweighted call -- its ranks in pr, the workspace is the select's state st.  Otherwise the weighted
+// call: pr is zero, lv holds its levels, and st lies behind the workspace's header mpart.
+struct PredSelect {
+  const u32* masses;
+  u64* mpart;
+  u32* st;
+  int R, bits;
+  size_t lds_bytes;   // the counting kernel's dynamic LDS
+  PredRanks pr;
+  PredLevels lv;
+  float* out;
+  int wpr() const { return predict_ranks_wpr(bits, masses != nullptr); }
+};
+
+// Past the default 64 KB of LDS a kernel needs the attribute, which belongs to the function on one device (as in
+// stein_small_phi: a flag per device id; racing threads at worst set it twice).  slot: 0 and 1 the GLM kernel without and
+// with masses, 1 + n_in the network kernels with masses; lds_dynamic: the most the kernel can be given beside its static LDS.
+static int predict_ranks_attr(const void* fn, int slot, size_t lds_dynamic) {
+  static bool attr_set[2 + PR_NIN_MAX][64] = {{false}};
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
   if (dev < 0 || dev >= 64 || !attr_set[slot][dev]) {
@@ -569,58 +483,128 @@ static int predict_wranks_attr(const void* fn, int slot, size_t lds_dynamic) {
   return STEIN_OK;
 }
 
-// the partial sums of the masses, the first narrow launch (every level led by level 0), then the targets from the levels
-static int predict_wranks_setup(const u32* masses, int64_t n, u64* mpart, u32* st, int R, int64_t batch, const PredLevels& lv,
-                                float* out, hipStream_t s) {
+static int predict_ranks_narrow(const PredSelect& q, int64_t batch, int shift, int width, hipStream_t s) {
+  hipLaunchKernelGGL(k_predict_ranks_narrow, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, q.st, q.R, (int)batch,
+                     shift, width, q.pr, q.out);
+  LAUNCH_CHECK("k_predict_ranks_narrow");
+  return STEIN_OK;
+}
+
+// The first narrow launch (every rank led by rank 0) -- in a weighted call behind the partial sums of the masses and ahead of
+// the targets from the levels -- then the key's bits from the top, `bits` at a time (the last level takes what is left):
+// count(shift, width) launches the model's counting kernel for one level, and the narrow step is queued behind it.
+template <class Count>
+static int predict_ranks_run(const PredSelect& q, int64_t n, int64_t batch, hipStream_t s, Count&& count) {
   const int64_t blocks = (n + 255) / 256;
   const int mparts = (int)(blocks < PQW_MPARTS - 1 ? blocks : PQW_MPARTS - 1);
-  hipLaunchKernelGGL(k_predict_wranks_msum, dim3((unsigned)mparts), dim3(256), 0, s, masses, (int)n, mpart);
-  LAUNCH_CHECK("k_predict_wranks_msum");
-  if (int rc = predict_ranks_narrow(st, R, batch, 32, 0, PredRanks{}, out, s)) return rc;
-  hipLaunchKernelGGL(k_predict_wranks_targets, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, st, R, (int)batch, lv,
-                     mpart, mparts);
-  LAUNCH_CHECK("k_predict_wranks_targets");
+  if (q.masses) {
+    hipLaunchKernelGGL(k_predict_wranks_msum, dim3((unsigned)mparts), dim3(256), 0, s, q.masses, (int)n, q.mpart);
+    LAUNCH_CHECK("k_predict_wranks_msum");
+  }
+  if (int rc = predict_ranks_narrow(q, batch, 32, 0, s)) return rc;
+  if (q.masses) {
+    hipLaunchKernelGGL(k_predict_wranks_targets, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, q.st, q.R, (int)batch,
+                       q.lv, q.mpart, mparts);
+    LAUNCH_CHECK("k_predict_wranks_targets");
+  }
+  for (int hi = 32; hi > 0;) {
+    const int width = q.bits < hi ? q.bits : hi, shift = hi - width;
+    if (int rc = count(shift, width)) return rc;
+    if (int rc = predict_ranks_narrow(q, batch, shift, width, s)) return rc;
+    hi = shift;
+  }
   return STEIN_OK;
+}
+
+// mass...: what the counting kernel takes in its pack -- nothing (the unweighted call), or the masses and the poison flag
+template <class... Mass>
+static int predict_glm_select(const float* theta, int64_t n, int64_t d, int kind, int output, int64_t w_col, int64_t n_feats,
+                              const float* X, int64_t batch, const PredPlan& pl, const PredGlmTile& tile, const PredSelect& q,
+                              hipStream_t s, Mass... mass) {
+  constexpr bool MASS = sizeof...(Mass) != 0;
+  const auto kernel = k_predict_glm_ranks<MASS, Mass...>;
+  // the byte counters beside the tile: up to 96.5 KB of dynamic LDS; the word counters: whatever the CU has
+  if (int rc = predict_ranks_attr(reinterpret_cast<const void*>(kernel), MASS ? 1 : 0, MASS ? PQW_LDS_CU : 100 * 1024)) return rc;
+  return predict_ranks_run(q, n, batch, s, [&](int shift, int width) -> int {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)pl.row_tiles, (unsigned)pl.slices), dim3(256), q.lds_bytes, s, theta, (int)n,
+                       (int)d, kind, output, (int)w_col, (int)n_feats, tile.fc, tile.ld, X, (int)batch, pl.per, mass..., q.st,
+                       q.R, shift, width, q.wpr());
+    LAUNCH_CHECK("k_predict_glm_ranks");
+    return STEIN_OK;
+  });
+}
+
+template <class... Mass>
+static int predict_bnn_select(const float* theta, int64_t n, int64_t d, int64_t n_in, int64_t n_hidden, const int64_t* cols,
+                              const float* X, int64_t batch, const PredPlan& pl, const PredSelect& q, hipStream_t s,
+                              Mass... mass) {
+  constexpr bool MASS = sizeof...(Mass) != 0;
+  using Kernel = decltype(&k_predict_bnn_ranks<1, MASS, Mass...>);
+  static const Kernel kernels[PR_NIN_MAX] = {k_predict_bnn_ranks<1, MASS, Mass...>, k_predict_bnn_ranks<2, MASS, Mass...>,
+                                             k_predict_bnn_ranks<3, MASS, Mass...>, k_predict_bnn_ranks<4, MASS, Mass...>};
+  const Kernel kernel = kernels[n_in - 1];
+  // the byte counters stay below the default 64 KB beside the static LDS (two workgroups per CU): no attribute
+  if (MASS)
+    if (int rc = predict_ranks_attr(reinterpret_cast<const void*>(kernel), 1 + (int)n_in, PQW_LDS_CU - predict_bnn_lds_static(n_in)))
+      return rc;
+  const PredCols c = predict_cols(cols);
+  return predict_ranks_run(q, n, batch, s, [&](int shift, int width) -> int {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)pl.row_tiles, (unsigned)pl.slices), dim3(256), q.lds_bytes, s, theta, (int)n,
+                       (int)d, (int)n_hidden, c, X, (int)batch, pl.per, mass..., q.st, q.R, shift, width, q.wpr());
+    LAUNCH_CHECK("k_predict_bnn_ranks");
+    return STEIN_OK;
+  });
+}
+
+extern "C" int stein_predict_glm_ranks(const float* theta, int64_t n, int64_t d, int kind, int output, int64_t w_col,
+                                       int64_t n_feats, const float* X, int64_t batch, const int64_t* ranks, int64_t n_ranks,
+                                       float* out, void* workspace, size_t ws_bytes, void* stream) {
+  if (int rc = predict_ranks_check(theta, X, ranks, n_ranks, out, n, d, batch, n_feats, output)) return rc;
+  if (int rc = predict_check_glm(kind, w_col, n_feats, d)) return rc;
+  PredRanks pr = {};
+  if (int rc = predict_ranks_check_tail(ranks, n_ranks, n, batch, workspace, ws_bytes, pr)) return rc;
+  const int R = (int)n_ranks;
+  const PredGlmTile tile = predict_glm_tile(n_feats, false);
+  // The X tile and the counters share the CU's 160 KiB.  With 4 bits a level, five or more ranks beside a wide tile leave
+  // room for one workgroup per CU only, which doubled the call's time; 3 bits a level (11 levels instead of 8) halve the
+  // counters and keep two.  Both give the same bits of the same order statistic.
+  const int bits = (tile.bytes + predict_ranks_lds(R, PQ_BITS, false) > PQ_LDS_HALF_CU &&
+                    tile.bytes + predict_ranks_lds(R, PQ_BITS - 1, false) <= PQ_LDS_HALF_CU) ? PQ_BITS - 1 : PQ_BITS;
+  const PredSelect q = {nullptr, nullptr, (u32*)workspace, R, bits, tile.bytes + predict_ranks_lds(R, bits, false), pr, {}, out};
+  return predict_glm_select(theta, n, d, kind, output, w_col, n_feats, X, batch, predict_ranks_plan(n, batch), tile, q,
+                            (hipStream_t)stream);
+}
+
+extern "C" int stein_predict_bnn_ranks(const float* theta, int64_t n, int64_t d, int64_t n_in, int64_t n_hidden,
+                                       const int64_t* cols, int output, const float* X, int64_t batch, const int64_t* ranks,
+                                       int64_t n_ranks, float* out, void* workspace, size_t ws_bytes, void* stream) {
+  if (!cols) return stein_fail(STEIN_E_BADARG, "NULL pointer");
+  if (int rc = predict_ranks_check(theta, X, ranks, n_ranks, out, n, d, batch, n_hidden, output)) return rc;
+  if (int rc = predict_check_bnn(n_in, n_hidden, cols, d)) return rc;
+  PredRanks pr = {};
+  if (int rc = predict_ranks_check_tail(ranks, n_ranks, n, batch, workspace, ws_bytes, pr)) return rc;
+  const int R = (int)n_ranks;
+  const PredSelect q = {nullptr, nullptr, (u32*)workspace, R, PQ_BITS, predict_ranks_lds(R, PQ_BITS, false), pr, {}, out};
+  return predict_bnn_select(theta, n, d, n_in, n_hidden, cols, X, batch, predict_ranks_plan(n, batch), q, (hipStream_t)stream);
 }
 
 extern "C" int stein_predict_glm_ranks_weighted(const float* theta, int64_t n, int64_t d, int kind, int output, int64_t w_col,
                                                 int64_t n_feats, const float* X, int64_t batch, const uint32_t* masses,
                                                 const double* levels, int64_t n_levels, float* out, void* workspace,
                                                 size_t ws_bytes, void* stream) {
-  if (!theta || !X || !masses || !levels || !out) return stein_fail(STEIN_E_BADARG, "NULL pointer");
-  if (n_levels < 1) return stein_fail(STEIN_E_BADARG, "n_levels %lld", (long long)n_levels);
-  if (int rc = predict_check(theta, X, nullptr, n, d, batch, n_feats, output, out, nullptr, nullptr, nullptr,
-                             PredWeights{false, nullptr, nullptr}))
-    return rc;
-  if (kind != STEIN_GLM_LINEAR && kind != STEIN_GLM_LOGISTIC) return stein_fail(STEIN_E_BADARG, "kind %d", kind);
-  if (w_col < 0 || w_col + n_feats > d)
-    return stein_fail(STEIN_E_SHAPE, "weights [%lld, %lld) do not fit d=%lld", (long long)w_col, (long long)(w_col + n_feats),
-                      (long long)d);
-  if (n_feats > PR_WIDTH_MAX) return stein_fail(STEIN_E_UNSUPPORTED, "more than 1024 features per particle");
+  if (int rc = predict_wranks_check(theta, X, masses, levels, n_levels, out, n, d, batch, n_feats, output)) return rc;
+  if (int rc = predict_check_glm(kind, w_col, n_feats, d)) return rc;
   const int R = (int)(n_levels < STEIN_PRED_RANKS_MAX ? n_levels : STEIN_PRED_RANKS_MAX);
-  const int fc = (int)(n_feats <= PR_FC ? n_feats : PR_FC);
-  const int ld = fc | 1;
-  const size_t tile_bytes = ((size_t)PR_ROWS * ld + (size_t)fc * PR_PASS + PR_PASS) * sizeof(float);   // X, weights, masses
+  const PredGlmTile tile = predict_glm_tile(n_feats, true);   // X, weights, masses
   const PredPlan pl = predict_ranks_plan(n, batch);
-  const int bits = predict_wranks_bits(R, tile_bytes, (int64_t)pl.row_tiles * pl.slices);
-  const size_t lds_bytes = tile_bytes + predict_wranks_lds(R, bits);
+  const int bits = predict_wranks_bits(R, tile.bytes, (int64_t)pl.row_tiles * pl.slices);
+  const size_t lds_bytes = tile.bytes + predict_ranks_lds(R, bits, true);
   PredLevels lv = {};
   if (int rc = predict_wranks_check_tail(levels, n_levels, batch, workspace, ws_bytes, lds_bytes, lv)) return rc;
-  if (int rc = predict_wranks_attr(reinterpret_cast<const void*>(k_predict_glm_wranks), 0, PQW_LDS_CU)) return rc;
-  hipStream_t s = (hipStream_t)stream;
   u64* mpart = (u64*)workspace;
-  u32* st = (u32*)(mpart + PQW_MPARTS);
-  if (int rc = predict_wranks_setup(masses, n, mpart, st, R, batch, lv, out, s)) return rc;
-  for (int hi = 32; hi > 0;) {   // the key's bits from the top, `bits` at a time (the last level takes what is left)
-    const int width = bits < hi ? bits : hi, shift = hi - width;
-    hipLaunchKernelGGL(k_predict_glm_wranks, dim3((unsigned)pl.row_tiles, (unsigned)pl.slices), dim3(256), lds_bytes, s, theta,
-                       (int)n, (int)d, kind, output, (int)w_col, (int)n_feats, fc, ld, X, (int)batch, pl.per, masses, mpart + PQW_MPARTS - 1,
-                       st, R, shift, width, 1 << bits);
-    LAUNCH_CHECK("k_predict_glm_wranks");
-    if (int rc = predict_ranks_narrow(st, R, batch, shift, width, PredRanks{}, out, s)) return rc;
-    hi = shift;
-  }
-  return STEIN_OK;
+  const PredSelect q = {masses, mpart, (u32*)(mpart + PQW_MPARTS), R, bits, lds_bytes, {}, lv, out};
+  return predict_glm_select<PredMasses, PredPoison>(theta, n, d, kind, output, w_col, n_feats, X, batch, pl, tile, q,
+                                                    (hipStream_t)stream, masses, mpart + PQW_MPARTS - 1);
 }
 
 extern "C" int stein_predict_bnn_ranks_weighted(const float* theta, int64_t n, int64_t d, int64_t n_in, int64_t n_hidden,
@@ -628,48 +612,19 @@ extern "C" int stein_predict_bnn_ranks_weighted(const float* theta, int64_t n, i
                                                 const uint32_t* masses, const double* levels, int64_t n_levels, float* out,
                                                 void* workspace, size_t ws_bytes, void* stream) {
   if (!cols) return stein_fail(STEIN_E_BADARG, "NULL pointer");
-  if (!theta || !X || !masses || !levels || !out) return stein_fail(STEIN_E_BADARG, "NULL pointer");
-  if (n_levels < 1) return stein_fail(STEIN_E_BADARG, "n_levels %lld", (long long)n_levels);
-  if (int rc = predict_check(theta, X, nullptr, n, d, batch, n_hidden, output, out, nullptr, nullptr, nullptr,
-                             PredWeights{false, nullptr, nullptr}))
-    return rc;
-  if (n_in < 1) return stein_fail(STEIN_E_SHAPE, "bad shape n_in=%lld", (long long)n_in);
-  if (n_in > PR_NIN_MAX) return stein_fail(STEIN_E_UNSUPPORTED, "more than %d input features", PR_NIN_MAX);
-  if (n_hidden > PR_WIDTH_MAX) return stein_fail(STEIN_E_UNSUPPORTED, "more than 1024 hidden units");
-  if (int rc = predict_check_cols(cols, n_in, n_hidden, d)) return rc;
+  if (int rc = predict_wranks_check(theta, X, masses, levels, n_levels, out, n, d, batch, n_hidden, output)) return rc;
+  if (int rc = predict_check_bnn(n_in, n_hidden, cols, d)) return rc;
   const int R = (int)(n_levels < STEIN_PRED_RANKS_MAX ? n_levels : STEIN_PRED_RANKS_MAX);
   const PredPlan pl = predict_ranks_plan(n, batch);
-  const size_t lds_static = ((size_t)PR_PASS * (n_in + 2) * PR_HC + PR_PASS * 4) * sizeof(float);   // lw and lp: at most 24.8 KB
+  const size_t lds_static = predict_bnn_lds_static(n_in);
   const int bits = predict_wranks_bits(R, lds_static, (int64_t)pl.row_tiles * pl.slices);
-  const size_t lds_bytes = predict_wranks_lds(R, bits);
+  const size_t lds_bytes = predict_ranks_lds(R, bits, true);
   PredLevels lv = {};
   if (int rc = predict_wranks_check_tail(levels, n_levels, batch, workspace, ws_bytes, lds_static + lds_bytes, lv)) return rc;
-  const PredCols c = {(int)cols[0], (int)cols[1], (int)cols[2], (int)cols[3], (int)cols[5]};
-  hipStream_t s = (hipStream_t)stream;
   u64* mpart = (u64*)workspace;
-  u32* st = (u32*)(mpart + PQW_MPARTS);
-  const void* fn = n_in == 1   ? reinterpret_cast<const void*>(k_predict_bnn_wranks<1>)
-                   : n_in == 2 ? reinterpret_cast<const void*>(k_predict_bnn_wranks<2>)
-                   : n_in == 3 ? reinterpret_cast<const void*>(k_predict_bnn_wranks<3>)
-                               : reinterpret_cast<const void*>(k_predict_bnn_wranks<4>);
-  if (int rc = predict_wranks_attr(fn, (int)n_in, PQW_LDS_CU - lds_static)) return rc;
-  if (int rc = predict_wranks_setup(masses, n, mpart, st, R, batch, lv, out, s)) return rc;
-  for (int hi = 32; hi > 0;) {
-    const int width = bits < hi ? bits : hi, shift = hi - width;
-#define PQW_LAUNCH_BNN(NIN)                                                                                              \
-  hipLaunchKernelGGL(k_predict_bnn_wranks<NIN>, dim3((unsigned)pl.row_tiles, (unsigned)pl.slices), dim3(256), lds_bytes, s, \
-                     theta, (int)n, (int)d, (int)n_hidden, c, X, (int)batch, pl.per, masses, mpart + PQW_MPARTS - 1, st, R, shift, width, \
-                     1 << bits)
-    if (n_in == 1) PQW_LAUNCH_BNN(1);
-    else if (n_in == 2) PQW_LAUNCH_BNN(2);
-    else if (n_in == 3) PQW_LAUNCH_BNN(3);
-    else PQW_LAUNCH_BNN(4);
-#undef PQW_LAUNCH_BNN
-    LAUNCH_CHECK("k_predict_bnn_wranks");
-    if (int rc = predict_ranks_narrow(st, R, batch, shift, width, PredRanks{}, out, s)) return rc;
-    hi = shift;
-  }
-  return STEIN_OK;
+  const PredSelect q = {masses, mpart, (u32*)(mpart + PQW_MPARTS), R, bits, lds_bytes, {}, lv, out};
+  return predict_bnn_select<PredMasses, PredPoison>(theta, n, d, n_in, n_hidden, cols, X, batch, pl, q, (hipStream_t)stream,
+                                                    masses, mpart + PQW_MPARTS - 1);
 }
 
 // ---- masses from weights (stein_predict_rank_masses) ---------------------------------------------------------------

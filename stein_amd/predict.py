@@ -49,11 +49,26 @@ class _Predict:
         self._masses = self._mass_info = None   # weighted_quantiles: the particles' integer masses and their total
         self._mws = self._wrws = None           # ... the workspaces of the masses pass and of the weighted select
 
-    def _workspace(self, n, batch, device):
-        need = _lib.predict_workspace_bytes(n, batch)
-        if self._ws is None or self._ws.device != device or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=device)
-        return self._ws
+    def _buffer(self, name, need, device, dtype=torch.uint8):
+        """the cached buffer self.<name>, regrown when it is missing, on another device or too small"""
+        buf = getattr(self, name)
+        if buf is None or buf.device != device or buf.numel() < need:
+            buf = torch.empty(need, dtype=dtype, device=device)
+            setattr(self, name, buf)
+        return buf
+
+    @staticmethod
+    def _weights(weights, n, device, want_mode=False):
+        """-> `weights` as a contiguous float64 [n] tensor on `device`; want_mode: and how weighted_quantiles takes them,
+        an integer dtype as counts, a float dtype as weights to normalise (noted before the conversion)"""
+        w = torch.as_tensor(weights)
+        if w.dtype == torch.bool or w.is_complex():
+            raise ValueError("weights must be real-valued, not %s" % w.dtype)
+        if w.dim() != 1 or w.shape[0] != n:
+            raise ValueError("weights must be [%d], one per particle" % n)
+        mode = _lib.MASS_NORMALISED if w.dtype.is_floating_point else _lib.MASS_COUNTS
+        w = w.to(device=device, dtype=torch.float64).contiguous()
+        return (w, mode) if want_mode else w
 
     def _inputs(self, theta, feed, want_y):
         X = feed["X"]
@@ -94,7 +109,8 @@ class _Predict:
         mean = torch.empty(batch, dtype=torch.float32, device=theta.device)
         var = torch.empty_like(mean)
         out_lpd = torch.empty_like(mean) if lpd else None
-        self._launch(theta, X, y, batch, None, mean, var, out_lpd, self._workspace(theta.shape[0], batch, theta.device))
+        ws = self._buffer("_ws", _lib.predict_workspace_bytes(theta.shape[0], batch), theta.device)
+        self._launch(theta, X, y, batch, None, mean, var, out_lpd, ws)
         return mean, var, out_lpd
 
     def weighted_summary(self, theta, feed, weights, lpd=None):
@@ -107,20 +123,13 @@ class _Predict:
             lpd = feed.get("y") is not None
         X, y, batch = self._inputs(theta, feed, bool(lpd))
         n = theta.shape[0]
-        w = torch.as_tensor(weights)
-        if w.dtype == torch.bool or w.is_complex():
-            raise ValueError("weights must be real-valued, not %s" % w.dtype)
-        if w.dim() != 1 or w.shape[0] != n:
-            raise ValueError("weights must be [%d], one per particle" % n)
-        w = w.to(device=theta.device, dtype=torch.float64).contiguous()
+        w = self._weights(weights, n, theta.device)
         mean = torch.empty(batch, dtype=torch.float32, device=theta.device)
         var = torch.empty_like(mean)
         out_lpd = torch.empty_like(mean) if lpd else None
         ess = torch.empty(1, dtype=torch.float64, device=theta.device)
-        need = _lib.predict_weighted_workspace_bytes(n, batch)
-        if self._wws is None or self._wws.device != theta.device or self._wws.numel() < need:
-            self._wws = torch.empty(need, dtype=torch.uint8, device=theta.device)
-        self._launch(theta, X, y, batch, None, mean, var, out_lpd, self._wws, weights=w, ess=ess)
+        ws = self._buffer("_wws", _lib.predict_weighted_workspace_bytes(n, batch), theta.device)
+        self._launch(theta, X, y, batch, None, mean, var, out_lpd, ws, weights=w, ess=ess)
         return mean, var, out_lpd, ess
 
     def order_statistics(self, theta, feed, ranks):
@@ -137,13 +146,12 @@ class _Predict:
             if not 0 <= r < n:
                 raise ValueError("rank %d is outside [0, %d)" % (r, n))
         out = torch.empty(len(ranks), batch, dtype=torch.float32, device=theta.device)
-        need = _lib.predict_ranks_workspace_bytes(n, batch, min(len(ranks), _lib.PRED_RANKS_MAX))
-        if self._rws is None or self._rws.device != theta.device or self._rws.numel() < need:
-            self._rws = torch.empty(need, dtype=torch.uint8, device=theta.device)
+        ws = self._buffer("_rws", _lib.predict_ranks_workspace_bytes(n, batch, min(len(ranks), _lib.PRED_RANKS_MAX)),
+                          theta.device)
         for at in range(0, len(ranks), _lib.PRED_RANKS_MAX):
             part = ranks[at:at + _lib.PRED_RANKS_MAX]
             self._launch_ranks(theta, X, batch, (ctypes.c_int64 * len(part))(*part), len(part), out[at:at + len(part)],
-                               self._rws)
+                               ws)
         return out
 
     def quantiles(self, theta, feed, q, interpolation="linear"):
@@ -196,13 +204,7 @@ class _Predict:
         library, more are split."""
         X, _, batch = self._inputs(theta, feed, False)
         n = theta.shape[0]
-        w = torch.as_tensor(weights)
-        if w.dtype == torch.bool or w.is_complex():
-            raise ValueError("weights must be real-valued, not %s" % w.dtype)
-        if w.dim() != 1 or w.shape[0] != n:
-            raise ValueError("weights must be [%d], one per particle" % n)
-        mode = _lib.MASS_NORMALISED if w.dtype.is_floating_point else _lib.MASS_COUNTS
-        w = w.to(device=theta.device, dtype=torch.float64).contiguous()
+        w, mode = self._weights(weights, n, theta.device, want_mode=True)
         q = [float(v) for v in q]
         if not q:
             raise ValueError("q must not be empty")
@@ -211,22 +213,18 @@ class _Predict:
                 raise ValueError("quantiles must lie in [0, 1], not %r" % v)
         dev = theta.device
         stream = torch.cuda.current_stream(dev).cuda_stream
-        if self._masses is None or self._masses.device != dev or self._masses.numel() < n:
-            self._masses = torch.empty(n, dtype=torch.int32, device=dev)      # the uint32 masses, as bytes
-            self._mass_info = torch.empty(2, dtype=torch.float64, device=dev)
-        need = _lib.predict_rank_masses_workspace_bytes(n)
-        if self._mws is None or self._mws.device != dev or self._mws.numel() < need:
-            self._mws = torch.empty(need, dtype=torch.uint8, device=dev)
-        _lib.call_on(dev, "stein_predict_rank_masses", w.data_ptr(), n, mode, self._masses.data_ptr(),
-                     self._mass_info.data_ptr(), self._mws.data_ptr(), self._mws.numel(), stream)
-        need = _lib.predict_ranks_weighted_workspace_bytes(n, batch, min(len(q), _lib.PRED_RANKS_MAX))
-        if self._wrws is None or self._wrws.device != dev or self._wrws.numel() < need:
-            self._wrws = torch.empty(need, dtype=torch.uint8, device=dev)
+        masses = self._buffer("_masses", n, dev, torch.int32)                 # the uint32 masses, as bytes
+        info = self._buffer("_mass_info", 2, dev, torch.float64)
+        mws = self._buffer("_mws", _lib.predict_rank_masses_workspace_bytes(n), dev)
+        _lib.call_on(dev, "stein_predict_rank_masses", w.data_ptr(), n, mode, masses.data_ptr(), info.data_ptr(),
+                     mws.data_ptr(), mws.numel(), stream)
+        ws = self._buffer("_wrws", _lib.predict_ranks_weighted_workspace_bytes(n, batch, min(len(q), _lib.PRED_RANKS_MAX)),
+                          dev)
         out = torch.empty(len(q), batch, dtype=torch.float32, device=dev)
         for at in range(0, len(q), _lib.PRED_RANKS_MAX):
             part = q[at:at + _lib.PRED_RANKS_MAX]
-            self._launch_wranks(theta, X, batch, self._masses, (ctypes.c_double * len(part))(*part), len(part),
-                                out[at:at + len(part)], self._wrws)
+            self._launch_wranks(theta, X, batch, masses, (ctypes.c_double * len(part))(*part), len(part),
+                                out[at:at + len(part)], ws)
         return out
 
     @staticmethod

@@ -7,6 +7,7 @@ a workspace filled with 0xFF bytes.
                 entry; all ones equal stein_predict_glm_ranks bit for bit; counts equal np.sort(np.repeat(f, c)); one-hots;
                 one mass of 2^31 with M = 2^32 - 1; mass 0 on the NaN particles (no NaN comes back) and only on them (NaN);
                 M = 0 and M >= 2^32 give NaN rows with STEIN_OK
+  ones          every network instantiation: masses of 1 equal stein_predict_bnn_ranks bit for bit, one call each
   own pred      every case of the table, masses from stein_predict_rank_masses read back, eight weight patterns and counts in
                 COUNTS mode: exactly the definition applied to the pred that stein_predict_* writes
   masses        NORMALISED inside 0.5 + A of w_p / W 2^31 and M inside n / 2 + A of 2^31, A = n 2^-21 (W's summation error);
@@ -181,6 +182,27 @@ def test_untrusted_masses_poison_the_call(cuda, mname):
     a = _planted_args(w)
     got = _wranks(PLANT_CASE, a, _mass_tensor(dict(wq.POISON)[mname], cuda), [0.0, 0.5, 1.0], cuda).cpu().numpy()   # STEIN_OK
     assert np.isnan(got).all(), got
+
+
+# the smallest network case of the table for each n_in it covers
+ONES_CASES = [min((c for c in wq.CASES if c["model"] == "bnn" and c["n_in"] == k), key=lambda c: c["n"] * c["B"])
+              for k in sorted({c["n_in"] for c in wq.CASES if c["model"] == "bnn"})]
+
+
+@pytest.mark.parametrize("case", ONES_CASES, ids=lambda c: c["name"])
+def test_network_masses_of_one_are_the_unweighted_call(cuda, case):
+    """k_predict_bnn_ranks<NIN, true> with every mass 1 and the levels that select the ranks themselves against
+    k_predict_bnn_ranks<NIN, false>: one call each, bit for bit (the planted test has this for the GLM only)"""
+    a, tensors, _ = _case_data(case, cuda)
+    n = case["n"]
+    ranks = list(dict.fromkeys([0, 1, n // 2, n - 2, n - 1, n // 3, n // 3 + 1, 2 * n // 3]))   # deduplicated, in order
+    assert len(ranks) <= wq.LEVELS_MAX and all(0 <= r < n for r in ranks)
+    assert [wq.target(wq.half_step(t, n), n) for t in ranks] == ranks
+    weighted = _wranks(case, a, _mass_tensor(np.ones(n, np.uint64), cuda), [wq.half_step(t, n) for t in ranks], cuda,
+                       tensors=tensors)
+    plain = _ranks(case, a, ranks, cuda, tensors=tensors)
+    torch.cuda.synchronize()
+    assert not torch.isnan(plain).any() and _same(weighted, plain)
 
 
 # ---- (b) every case against the library's own pred ------------------------------------------------------------------------

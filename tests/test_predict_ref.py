@@ -24,17 +24,20 @@ OUTPUTS = ("pred", "mean", "var", "lpd")
 
 
 def _source():
-    return open(os.path.join(ROOT, "stein_amd", "csrc", "stein_predict.hip")).read()
+    """the summary kernels' source and, ahead of it, the header it shares with the rank-counting kernels"""
+    csrc = os.path.join(ROOT, "stein_amd", "csrc")
+    return open(os.path.join(csrc, "stein_predict_fwd.h")).read() + open(os.path.join(csrc, "stein_predict.hip")).read()
 
 
 # ---- (a) ------------------------------------------------------------------------------------------
 def test_constants_mirror_the_source():
     src = _source()
     for name in ("PR_ROWS", "PR_PASS", "PR_SLICE_CAP", "PR_TARGET_WGS", "PR_FC", "PR_HC", "PR_STATE"):
+        assert len(re.findall(r"constexpr int %s = " % name, src)) == 1, name          # defined once across the two files
         assert re.search(r"constexpr int %s = %d;" % (name, getattr(pc, name)), src), name
-    assert "n_feats <= PR_FC ? n_feats : PR_FC" in src and "const int ld = fc | 1;" in src
-    assert "if (nfc == 1) stage_x(0, F);" in src and "if (nfc > 1) stage_x(f0, len);" in src
-    assert "h0 += PR_HC" in src and "len4 = (len + 3) & ~3" in src and "PF_ROWS = 16, PF_GROUPS = 16" in src
+    for idiom in ("n_feats <= PR_FC ? n_feats : PR_FC", "const int ld = fc | 1;", "if (nfc == 1) stage_x(0, F);",
+                  "if (nfc > 1) stage_x(f0, len);", "h0 += PR_HC", "len4 = (len + 3) & ~3", "PF_ROWS = 16, PF_GROUPS = 16"):
+        assert src.count(idiom) == 1, idiom
     code = re.sub(r"//[^\n]*", "", src)
     assert "atomic" not in code.lower() and "__shfl" not in code   # no float atomics anywhere: no atomics at all
 

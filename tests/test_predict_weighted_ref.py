@@ -27,13 +27,16 @@ SUMMARIES = ("mean", "var", "lpd")
 
 
 def _source():
-    return open(os.path.join(ROOT, "stein_amd", "csrc", "stein_predict.hip")).read()
+    """the summary kernels' source and, ahead of it, the header it shares with the rank-counting kernels"""
+    csrc = os.path.join(ROOT, "stein_amd", "csrc")
+    return open(os.path.join(csrc, "stein_predict_fwd.h")).read() + open(os.path.join(csrc, "stein_predict.hip")).read()
 
 
 # ---- (a) ------------------------------------------------------------------------------------------
 def test_the_source_has_the_weighted_paths_the_tables_assume():
     src = _source()
-    assert "constexpr int PW_HEAD = %d;" % pwc.PW_HEAD in src and "PW_HEAD + 3 * slices" in src
+    assert src.count("constexpr int PW_HEAD = ") == 1 and "constexpr int PW_HEAD = %d;" % pwc.PW_HEAD in src
+    assert src.count("PW_HEAD + 3 * slices") == 1
     assert "template <bool WEIGHTED>" in src and "template <int NIN, bool WEIGHTED>" in src
     assert "PR_LAUNCH_BNN_AS(NIN, true)" in src and "PR_LAUNCH_GLM(true," in src and "k_predict_finish<true>" in src
     assert re.search(r"q >= FLT_MIN \? q : 0\.f", src)     # the flush the reference charges
@@ -63,7 +66,7 @@ def test_tables_reach_every_arm_weighted_and_every_pattern():
 
 def test_zero_slices_reach_the_skip_and_first_live_particle_branches():
     G = 16                                                 # PF_GROUPS
-    assert "PF_ROWS = 16, PF_GROUPS = 16" in _source()
+    assert _source().count("PF_ROWS = 16, PF_GROUPS = 16") == 1
     whole_group_dead = dead_inside_group = False
     for case, pat in pwc.CROSSED:
         if pat != "zero_slices":

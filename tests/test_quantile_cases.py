@@ -25,8 +25,17 @@ def test_constants_are_the_sources():
     assert int(re.search(r"STEIN_PRED_RANKS_MAX = (\d+)", hdr).group(1)) == qc.RANKS_MAX
     assert "%d bytes per (row, rank)" % (4 * qc.PQ_WORDS) in hdr
     assert qc.PQ_FLUSH * pc.PR_PASS <= 255                       # a byte counter cannot overflow between two flushes
-    # one forward pass, not two: the counting kernels include the summary kernels' source and call its slice walks
-    assert '#include "stein_predict.hip"' in src and "pred_glm_slice(" in src and "pred_bnn_pass<NIN>(" in src
+    # one forward pass, not two: the counting kernels and the summary kernels include one header and call its slice walks
+    summ = open(os.path.join(ROOT, "stein_amd", "csrc", "stein_predict.hip")).read()
+    fwd = open(os.path.join(ROOT, "stein_amd", "csrc", "stein_predict_fwd.h")).read()
+    assert '#include "stein_predict_fwd.h"' in src and '#include "stein_predict_fwd.h"' in summ
+    assert "pred_glm_slice(" in src and "pred_bnn_pass<NIN>(" in src and "pred_glm_slice(" in summ and "pred_bnn_pass<NIN>(" in summ
+    assert fwd.count("void pred_glm_slice(") == 1 and fwd.count("void pred_bnn_pass(") == 1
+    assert '.hip"' not in src and '.hip"' not in summ and '.hip"' not in fwd   # no source is used as a header
+    assert all("STEIN_PREDICT_SHARED_ONLY" not in text for text in (src, summ, fwd))
+    import __graft_entry__ as ge
+    hdrs = [os.path.basename(p) for p in ge.HDRS]
+    assert "stein_predict_fwd.h" in hdrs and "stein_predict.hip" not in hdrs and not any(h.endswith(".hip") for h in hdrs)
     assert "fmaf(" not in re.sub(r"//[^\n]*", "", src)             # and type no arithmetic of the forward pass again
 
 

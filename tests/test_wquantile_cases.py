@@ -32,8 +32,12 @@ def test_constants_are_the_sources():
     assert "constexpr int PQ_BITS = 4" in src and "constexpr int PQ_FLUSH = 15" in src
     assert "constexpr int PQ_WORDS = 3 + PQ_BINS;" in src and "PQ_LDS_HALF_CU = 80 * 1024;" in src
     assert re.search(r"enum \{ STEIN_PRED_RANKS_MAX = 8 \};", hdr)
-    # one forward pass: the weighted kernels call the same slice walks
-    assert src.count("pred_glm_slice(") == 2 and src.count("pred_bnn_pass<NIN>(") == 2
+    # one forward pass and one counting kernel per model: a single call site of each slice walk, whatever is counted
+    assert src.count("pred_glm_slice(") == 1 and src.count("pred_bnn_pass<NIN>(") == 1
+    assert "k_predict_glm_wranks" not in src and "k_predict_bnn_wranks" not in src
+    assert src.count("void k_predict_glm_ranks(") == 1 and src.count("void k_predict_bnn_ranks(") == 1
+    assert "template <bool MASS, class... Mass>\n__global__" in src
+    assert "template <int NIN, bool MASS, class... Mass>\n__global__" in src
     # integer atomics only: no atomic on a float or a double anywhere in the file
     code = re.sub(r"//[^\n]*", "", src)
     for m in re.finditer(r"atomicAdd\(([^;]*);", code):
