@@ -367,6 +367,12 @@ int stein_debug_thin_grid(int blocks);   /* test hook, per calling thread; 0 = d
  * waits for another: a repeated call is bit-identical, for any workspace contents; negating a row of weights leaves its
  * q_out bits unchanged (by construction: the matrix cores' sums are not sign-symmetric, so each row is contracted in the
  * sign that makes its first nonzero entry positive), and so does its position among the rows.
+ * Non-finite inputs.  The host never reads theta, score or h2_in and cannot validate them, and a finite number for a sample
+ * that contains a NaN would pass for a statistic, so: a NaN or an infinity ANYWHERE in theta or score, or h2 = 0 or NaN,
+ * makes EVERY q_out[b] and diag_out NaN, and the call returns STEIN_OK (as the weighted predictive calls do).  So does a
+ * row whose |x_i|^2, |g_i|^2, g_i.x_i or (RBF) |g_i - x_i / h2|^2 overflows fp32: these per-row sums are what the device looks
+ * at (k_boot_scale), once per call and outside the j loop.  Non-finite weights are the caller's.  (A caller that counts
+ * replicates >= the statistic must treat a NaN statistic itself: stein_goodness_of_fit returns a NaN p-value.)
  * The workspace must be 16-byte aligned (STEIN_E_BADARG); it carries nothing between calls.  With R = n rounded up to 128,
  * dk = d rounded up to 32, dc = d rounded up to 128, C = reps rounded up to 128 and P = reps rounded up to 32,
  *   stein_ksd_boot_workspace_bytes = 4 R + 4 (6 dc + 4) + 6 R dk + 4 n d + 4 (6 dc + 4) + 6 R dk + 4 (6 R + 4) + 6 C R
@@ -401,6 +407,8 @@ int stein_debug_boot_jsplit(int jsplit);   /* test hook, per calling thread; 0 =
  * atomics: a repeated call is bit-identical, for any workspace contents; rows >= n and replicates >= reps are never written.
  * V is split as given: the sign canonicalisation of the quadratic forms is not needed here and NOT promised -- out(-V) may
  * differ from -out(V) in the last bit of a partial.
+ * Non-finite inputs: as stein_ksd_boot -- a NaN or an infinity anywhere in theta or score (or a per-row sum that overflows
+ * fp32), or h2 = 0 or NaN, makes every out[b][i] NaN, and the call returns STEIN_OK; nothing outside out is written.
  * The workspace must be 16-byte aligned (STEIN_E_BADARG); it carries nothing between calls.  With R, dk, dc, C, P as above it
  * is the bootstrap's layout with the partial block holding T's partials and without the canonical weights:
  *   stein_ksd_matmul_workspace_bytes = 4 R + 4 (6 dc + 4) + 6 R dk + 4 n d + 4 (6 dc + 4) + 6 R dk + 4 (6 R + 4) + 6 C R

@@ -13,7 +13,9 @@
 //                       the matrix cores' accumulation is not sign-symmetric (observed: Q(-w) one ulp of a partial from
 //                       Q(w)), so w and -w are made the SAME operand: negating a row leaves its bits unchanged by construction
 //   k_boot_rows         per particle: b_i (RBF: g_i.x_i / h2 - r_i / (2 h2^2); IMQ: g_i.x_i), |m_i|^2, |g_i|^2 (fp64); RBF: row i of W
-//   k_boot_scale        one workgroup: a bound on |u_p| -> the power-of-two scale of the image; sum_i u_p(i, i) -> diag_out
+//   k_boot_scale        one workgroup: a bound on |u_p| -> the power-of-two scale of the image; sum_i u_p(i, i) -> diag_out;
+//                       a non-finite per-row sum (a NaN or Inf in theta or the score) or h2 = 0 / NaN -> a NaN out-scale:
+//                       every output is NaN (the element function's clamp would otherwise turn it into a finite +-60000)
 //   k_ksd_boot<Kern>    the streaming kernel (below)
 //   k_boot_sum          adds the (j range, row tile) partials of every replicate in fixed order in fp64 -> q_out
 // stein_ksd_matmul (out = V U, the products Stein importance weights and control variates need) is the
@@ -25,7 +27,7 @@
 //   Gram         S = T_j T_i^T (st_distance_tile), S1 = M_j M_i^T, and for the IMQ kernel S2 = T_j M_i^T + M_j T_i^T, the
 //                symmetric cross term as ONE Gram of depth 2 d over the operands [g | x] and [x | g] -- which are the planes
 //                already there, read in the other order
-//   element      u_p from D, the Gram values and the per-particle b (RbfBoot / ImqBoot), times the image scale, clamped to the
+//   element      u_p from D (0 on the diagonal by a select), the Gram values and the per-particle b (RbfBoot / ImqBoot), times the image scale, clamped to the
 //                fp16 range, columns j >= n forced to 0 by a select; hi + lo fp16 into the image (st_split4, st_stage4)
 //   contraction  st_contract_ktile, unchanged: A the u image, B the weights' planes
 // Tail: the wave's 128 x 32 accumulator times w_bi (the canonical floats), rows >= n masked by a select, summed over the
@@ -121,8 +123,10 @@ __global__ __launch_bounds__(ST_THREADS) void k_ksd_boot(const u16* __restrict__
   const float gc = 1.f / (sct[4 * dc] * scm[4 * dc]);        // x_j.m_i + m_j.x_i = S2 gc (powers of two: exact)
   const float us = st[0];
   float ri[2], bi[2];
+  int irow[2];
 #pragma unroll
   for (int a = 0; a < 2; ++a) {
+    irow[a] = i0 + wr * 32 + a * 16 + l15;
     ri[a] = r[i0 + wr * 32 + a * 16 + l15];      // (r and rowb are padded to the row tiles; rows >= n are masked in the tail)
     bi[a] = rowb[i0 + wr * 32 + a * 16 + l15];
   }
@@ -166,7 +170,9 @@ __global__ __launch_bounds__(ST_THREADS) void k_ksd_boot(const u16* __restrict__
         float q[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float dv = (ri[ib] + rj[e]) - two_s * s[jb][ib][e];
+          // D_ii = 0, not the rounding error of r_i + r_i - 2 x_i.x_i: one ulp of 2 r_i there moves k by r_i 2^-23 / (2 h2),
+          // 0.2 % of u_ii for a particle 100 sigma out, whose diagonal term is all it contributes
+          const float dv = (j0 + jc + e == irow[ib]) ? 0.f : (ri[ib] + rj[e]) - two_s * s[jb][ib][e];
           float g2 = 0.f;
           if constexpr (Kern::CROSS) g2 = gc * s2[jb][ib][e];
           const float uv = kern.u(dv, gm * s1[jb][ib][e], g2, bi[ib], bj[e]) * us;
@@ -296,7 +302,7 @@ __global__ __launch_bounds__(256) void k_boot_canon(const float* __restrict__ W,
 // the scaled unit, 2^-38 of the bound.
 template <int KERNEL>
 __global__ __launch_bounds__(256) void k_boot_scale(const float* __restrict__ rown, const float* __restrict__ rowb,
-                                                    const double* __restrict__ rowdiag, const float* __restrict__ h2p,
+                                                    const float* __restrict__ r, const double* __restrict__ rowdiag, const float* __restrict__ h2p,
                                                     const float* __restrict__ scw_all, float* __restrict__ st,
                                                     double* __restrict__ diag_out, int n, int d) {
   __shared__ float mx[2][256];
@@ -304,9 +310,12 @@ __global__ __launch_bounds__(256) void k_boot_scale(const float* __restrict__ ro
   const int t = threadIdx.x;
   float mn = 0.f, mb = 0.f;
   double dg[1] = {0.0};
+  // fmaxf drops a NaN: a row whose |m_i|^2 or b_i is NaN counts as +inf, so that the bound sees it (below)
+  auto seen = [](float v) { return v == v ? v : __builtin_inff(); };
   for (int i = t; i < n; i += 256) {
-    mn = fmaxf(mn, rown[i]);
-    mb = fmaxf(mb, fabsf(rowb[i]));
+    mn = fmaxf(mn, seen(rown[i]));
+    mb = fmaxf(mb, seen(fabsf(rowb[i])));
+    if (!(r[i] < __builtin_inff())) mb = __builtin_inff();   // |x_i|^2 beyond fp32 (or NaN): D, and with it k, is lost
     dg[0] += rowdiag[i];
   }
   mx[0][t] = mn;
@@ -326,9 +335,16 @@ __global__ __launch_bounds__(256) void k_boot_scale(const float* __restrict__ ro
     const float bound = KERNEL == STEIN_KERNEL_RBF ? mx[0][0] + 2.f * mx[1][0] + (float)(d + 1) * ih
                                                    : mx[0][0] + sqrtf(mx[0][0] * ih) + (float)(d + 3) * ih;
     const int se = scale_exp(__float_as_uint(bound), 100);
+    // A non-finite theta or score entry makes its row's |m_i|^2, b_i or r_i non-finite (k_boot_rows, stein_rownorms), h2 = 0
+    // or NaN the bound itself.  The element function would clamp such an entry into the image as a finite value, so the OUT-scale is
+    // poisoned here, off the j loop: every q_out[b] / out[b][i] and diag_out come out NaN (include/steinhip.h).
+    // (the IMQ bound does not hold max |b_i| = max |g_i.x_i|, the one per-row sum of that kernel theta enters: it is asked too)
+    const bool finite = bound < __builtin_inff() && mx[1][0] < __builtin_inff();
+    const float nan = __uint_as_float(0x7fc00000u);
     st[0] = pow2i(se);
-    st[1] = pow2i(-se) / *scw_all;
-    if (diag_out) *diag_out = dg[0] + (double)n * (double)d * (KERNEL == STEIN_KERNEL_RBF ? 1.0 : 0.5) / (double)h2;
+    st[1] = finite ? pow2i(-se) / *scw_all : nan;
+    if (diag_out)
+      *diag_out = finite ? dg[0] + (double)n * (double)d * (KERNEL == STEIN_KERNEL_RBF ? 1.0 : 0.5) / (double)h2 : (double)nan;
   }
 }
 
@@ -502,7 +518,7 @@ static int boot_launch(const BootLayout& L, char* ws, const float* theta, const 
   }
   if ((rc = boot_split_one(vw, Wc, reps, n, s))) return rc;
   // 5. the image's scale (after the weights' scale exists), the diagonal sum
-  hipLaunchKernelGGL(k_boot_scale<Kern::ID>, dim3(1), dim3(256), 0, s, rown, rowb, rowdiag, h2_in, vw.sc + 4 * L.rows, st, diag_out,
+  hipLaunchKernelGGL(k_boot_scale<Kern::ID>, dim3(1), dim3(256), 0, s, rown, rowb, r, rowdiag, h2_in, vw.sc + 4 * L.rows, st, diag_out,
                      (int)n, (int)d);
   LAUNCH_CHECK("k_boot_scale");
   // 6. the streaming kernel; 7. the partials in fixed order

@@ -94,7 +94,8 @@ def stein_goodness_of_fit(theta, score, n_boot=511, bandwidth="median", kernel="
     instead (statistic "v" only).  p = (1 + #{b : Q_b >= Q_0}) / (n_boot + 1); the statistic Q_0 is computed as one more
     row, all ones, of the same call, so both sides of the comparison come out of the same arithmetic.
     statistic: "v" (default) or "u" (the diagonal sum_i u_p(x_i, x_i) removed from the statistic and every replicate).
-    bandwidth, kernel: as in ksd_quadratic_forms.  One host read, at the end."""
+    bandwidth, kernel: as in ksd_quadratic_forms.  One host read, at the end.  A NaN or infinity in theta or score makes the
+    statistic and the p-value NaN."""
     if isinstance(n_boot, bool) or not isinstance(n_boot, int) or n_boot < 1:
         raise ValueError("n_boot must be an integer >= 1, got %r" % (n_boot,))
     if isinstance(flip_prob, bool) or not isinstance(flip_prob, (int, float)) or not 0.0 < float(flip_prob) < 1.0:
@@ -117,5 +118,7 @@ def stein_goodness_of_fit(theta, score, n_boot=511, bandwidth="median", kernel="
         vals = q / float(n) ** 2 if statistic == "v" else (q - diag) / (float(n) * (n - 1.0))
         count = (vals[1:] >= vals[0]).sum().to(torch.float64)
         stat, hits = torch.stack([vals[0], count]).tolist()
-    p = (1.0 + hits) / (n_boot + 1.0)
+    # a NaN or Inf in theta or score, or a zero bandwidth, makes every form NaN (include/steinhip.h): no comparison counts,
+    # which would read as p = 1 / (n_boot + 1) -- a rejection.  A statistic that is not a number has no p-value.
+    p = (1.0 + hits) / (n_boot + 1.0) if stat == stat else float("nan")
     return (stat, p, vals[1:]) if return_samples else (stat, p)
