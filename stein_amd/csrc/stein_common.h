@@ -223,19 +223,51 @@ __device__ __forceinline__ void ksd_terms(float g, double og, float ot, float th
 // ---- arithmetic that the fused call and the staged calls must do bit for bit alike: written once -------------------------
 __device__ __forceinline__ float elem_f32(const float* p) { return *p; }
 __device__ __forceinline__ float elem_f32(const unsigned short* p) { return __uint_as_float((u32)*p << 16); }   // bf16 bits
+// |v| as a bit pattern: non-negative floats order like unsigned integers, so maxima of |v| are integer maxima
+__device__ __forceinline__ u32 abs_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
+__device__ __forceinline__ u32 abs_bits(unsigned short v) { return ((u32)v << 16) & 0x7fffffffu; }
 
 // |row|^2 of one row of d elements by one wave: lane-strided fmaf chain, then the xor-shuffle sum (every lane returns it).
 // The row norms r_i of k_rownorms (staged calls) and of prologue_body (fused call).
+// amax: the lane also keeps the largest |x| it read, as a bit pattern (abs_bits), for callers that want max|X| from the same
+// pass (prologue_body on the folded step); the sum's instructions do not change with it.
 template <typename TIN>
-__device__ __forceinline__ float wave_row_sqnorm(const TIN* row, int d, int lane) {
+__device__ __forceinline__ float wave_row_sqnorm(const TIN* row, int d, int lane, u32& amax) {
   float s = 0.f;
   for (int k = lane; k < d; k += 64) {
     const float x = elem_f32(row + k);
     s = fmaf(x, x, s);
+    amax = max(amax, abs_bits(x));
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
   return s;
+}
+template <typename TIN>
+__device__ __forceinline__ float wave_row_sqnorm(const TIN* row, int d, int lane) {
+  u32 unused = 0u;
+  return wave_row_sqnorm(row, d, lane, unused);
+}
+// NR rows (`stride` elements apart) by one wave at once: the loads of all of them are issued before the first fmaf, and every
+// row keeps the chain and the shuffle sum of wave_row_sqnorm, so each s[e] has that function's bits
+template <int NR, typename TIN>
+__device__ __forceinline__ void wave_rows_sqnorm(const TIN* row, size_t stride, int d, int lane, float (&s)[NR], u32& amax) {
+#pragma unroll
+  for (int e = 0; e < NR; ++e) s[e] = 0.f;
+  for (int k = lane; k < d; k += 64) {
+    float x[NR];
+#pragma unroll
+    for (int e = 0; e < NR; ++e) x[e] = elem_f32(row + e * stride + k);
+#pragma unroll
+    for (int e = 0; e < NR; ++e) {
+      s[e] = fmaf(x[e], x[e], s[e]);
+      amax = max(amax, abs_bits(x[e]));
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < NR; ++e)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s[e] += __shfl_xor(s[e], o);
 }
 
 // Ordered fp64 sum of N values per thread over a 256-thread workgroup: xor-shuffle over each wave, lane 0 of wave w writes
@@ -259,6 +291,91 @@ __device__ __forceinline__ void block_sum256(double (&v)[N], double* red) {
 
 __device__ __forceinline__ u64 load_fresh(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ u32 load_fresh(const u32* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// ---- column maxima of |X| [n][d] as bit patterns: the body of k_colmax (stein_x3.hip) and of the maxima slice of
+// k_spec_select (stein_select.hip) ----------------------------------------------------------------------------------------
+// A workgroup owns 64 CW columns and the rows r, r + step, ... (one row per wave and iteration), so a lane keeps its columns
+// `col` .. `col` + CW - 1 whatever d.  V4 (fp32, d % 4 == 0, rows on 16-byte boundaries): CW = 4, a lane reads four columns
+// with one load and a wave one full KB of a row; otherwise CW = 1 and a wave reads 256 bytes.  The NM matrices are scanned
+// together, four independent loads of each in flight per lane (one dependent load at a time read the matrices at 2 TB/s).
+template <typename TIN, bool V4, int NM>
+__device__ __forceinline__ void colmax_scan(const TIN* const (&X)[NM], int n, int d, int col, long r, long step,
+                                            u32 (&m)[NM][V4 ? 4 : 1]) {
+  constexpr int CW = V4 ? 4 : 1;
+#pragma unroll
+  for (int z = 0; z < NM; ++z)
+#pragma unroll
+    for (int e = 0; e < CW; ++e) m[z][e] = 0u;
+  if (col >= d) return;
+  const size_t off = (size_t)step * d;          // elements between two of a wave's rows
+  const TIN* p[NM];
+#pragma unroll
+  for (int z = 0; z < NM; ++z) p[z] = X[z] + (size_t)r * d + col;
+  if constexpr (V4) {
+    auto ld = [](const TIN* q) { return *reinterpret_cast<const float4*>(q); };
+    auto up = [](u32 (&a)[CW], const float4& v) {
+      a[0] = max(a[0], abs_bits(v.x)); a[1] = max(a[1], abs_bits(v.y));
+      a[2] = max(a[2], abs_bits(v.z)); a[3] = max(a[3], abs_bits(v.w));
+    };
+    for (; r + 3 * step < n; r += 4 * step) {
+      float4 v[NM][4];
+#pragma unroll
+      for (int z = 0; z < NM; ++z) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[z][k] = ld(p[z] + k * off);
+        p[z] += 4 * off;
+      }
+#pragma unroll
+      for (int z = 0; z < NM; ++z)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) up(m[z], v[z][k]);
+    }
+    for (; r < n; r += step) {
+      float4 v[NM];
+#pragma unroll
+      for (int z = 0; z < NM; ++z) { v[z] = ld(p[z]); p[z] += off; }
+#pragma unroll
+      for (int z = 0; z < NM; ++z) up(m[z], v[z]);
+    }
+  } else {
+    for (; r + 3 * step < n; r += 4 * step) {
+      u32 v[NM][4];
+#pragma unroll
+      for (int z = 0; z < NM; ++z) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[z][k] = abs_bits(p[z][k * off]);
+        p[z] += 4 * off;
+      }
+#pragma unroll
+      for (int z = 0; z < NM; ++z) m[z][0] = max(max(m[z][0], v[z][0]), max(max(v[z][1], v[z][2]), v[z][3]));
+    }
+    for (; r < n; r += step) {
+#pragma unroll
+      for (int z = 0; z < NM; ++z) { m[z][0] = max(m[z][0], abs_bits(*p[z])); p[z] += off; }
+    }
+  }
+}
+
+// The workgroup's maxima -> cmax0[z * dc + column]: first gathered in LDS (red: NM * 64 * CW words no thread is still reading;
+// every thread of the workgroup must call), then ONE atomicMax per column and matrix whatever the number of waves -- the
+// same-address chains at the memory side were once the larger part of the kernel's time.  cmax0 zeroed by an earlier launch.
+// cx: the lane's column slot (its columns are (cb * 64 + cx) * CW ..).
+template <int CW, int NM>
+__device__ __forceinline__ void colmax_commit(const u32 (&m)[NM][CW], int cx, int cb, int d, u32* red,
+                                              u32* __restrict__ cmax0, int dc) {
+  const int t = threadIdx.x, nt = blockDim.x;
+  for (int i = t; i < NM * 64 * CW; i += nt) red[i] = 0u;
+  __syncthreads();
+#pragma unroll
+  for (int z = 0; z < NM; ++z)
+#pragma unroll
+    for (int e = 0; e < CW; ++e) atomicMax(&red[(z * 64 + cx) * CW + e], m[z][e]);
+  __syncthreads();
+  for (int i = t; i < NM * 64 * CW; i += nt) {
+    const int z = i / (64 * CW), c = cb * 64 * CW + i % (64 * CW);
+    if (c < d) atomicMax(&cmax0[(size_t)z * dc + c], red[i]);
+  }
+}
 
 // Add `valid` lanes' digits to an LDS histogram.  Distances cluster (a handful of top-level bins hold
 // everything), so the wave first merges lanes that share the leader's digit into one atomic, twice,
@@ -677,8 +794,21 @@ struct PrologueArgs {
   float* neutral_sc; int dc;
   u32* hsync; int hsync_words;   // HistSync of k_hist_all (zeroed here)
   u32 folded;                    // -> FuseState::folded
+  // folded step without dK / KSD: workgroup b stores max|theta| over the rows it read, as a bit pattern, in wgmax[b] (a
+  // plain store of every word by this launch: nothing is zeroed first and nothing old is read).  k_split_rows reduces the
+  // words to the one scale of theta's row-major planes (stein_x3.hip).  NULL otherwise.
+  u32* wgmax;
 };
 constexpr int PRO_INIT_BLOCKS = 16;   // (k_prologue's grid: one workgroup per four rows + these; any grid works)
+// ... capped on the folded step that takes max|theta| here: the rows are dealt round-robin, wgmax stays 4 KB (every workgroup
+// of k_split_rows reads all of it), and a wave has PRO_ROWS rows in flight at once (wave_rows_sqnorm).  Measured at C3
+// (profiles/fold_prepare_ab.txt, 5.): 2048 workgroups x 1 row 7.3 us and k_split_rows 10.2; 2048 x 2 6.5 and 10.1; 1024 x 4 6.5
+// and 9.2 (the uncapped grid of one row per wave: 7.0)
+constexpr int PRO_MAX_WGS = 1024;
+constexpr int PRO_ROWS = 4;
+// wgmax lives behind HistSync in the rank-summed window table, which a single-rank fused call has no other use for
+constexpr size_t PRO_WGMAX_AT = (sizeof(HistSync) + 255) / 256 * 256;   // bytes from the table's start
+static_assert(PRO_WGMAX_AT + (size_t)PRO_MAX_WGS * 4 <= (size_t)SPEC_TABLE * 8, "wgmax must fit behind HistSync in the table");
 template <typename TIN>
 __device__ __forceinline__ void prologue_body(const TIN* __restrict__ T, const PrologueArgs& a, int b, int nb) {
   const int gt = b * 256 + (int)threadIdx.x, gn = nb * 256;
@@ -691,8 +821,33 @@ __device__ __forceinline__ void prologue_body(const TIN* __restrict__ T, const P
   for (int i = gt; i < a.hsync_words; i += gn) a.hsync[i] = 0u;
   median_init_body(gt, gn, a.st, a.sp, a.total, a.hist, a.slots, a.allow_window);
   const int lane = threadIdx.x & 63;
-  for (int row = gt >> 6; row < a.n; row += gn >> 6) {
-    const float s = wave_row_sqnorm(T + (size_t)row * a.d, a.d, lane);
+  u32 amax = 0u;
+  const int wstep = gn >> 6;
+  int row = gt >> 6;
+  if constexpr (PRO_ROWS > 1) {
+    if (a.wgmax) {   // (the capped grid: a wave has several rows, PRO_ROWS of them at once)
+      for (; (long)row + (PRO_ROWS - 1) * (long)wstep < a.n; row += PRO_ROWS * wstep) {
+        float s[PRO_ROWS];
+        wave_rows_sqnorm<PRO_ROWS>(T + (size_t)row * a.d, (size_t)wstep * a.d, a.d, lane, s, amax);
+        if (lane == 0) {
+#pragma unroll
+          for (int e = 0; e < PRO_ROWS; ++e) a.r[row + e * wstep] = s[e];
+        }
+      }
+    }
+  }
+  for (; row < a.n; row += wstep) {
+    const float s = wave_row_sqnorm(T + (size_t)row * a.d, a.d, lane, amax);
     if (lane == 0) a.r[row] = s;
+  }
+  if (a.wgmax) {   // (uniform over the launch)
+    __shared__ u32 s_amax;
+    if (threadIdx.x == 0) s_amax = 0u;
+    __syncthreads();
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) amax = max(amax, (u32)__shfl_xor((int)amax, o));
+    if (lane == 0) atomicMax(&s_amax, amax);
+    __syncthreads();
+    if (threadIdx.x == 0) a.wgmax[b] = s_amax;
   }
 }

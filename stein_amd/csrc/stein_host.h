@@ -91,9 +91,11 @@ int stein_take_device_error(void);
 int stein_stream_jsplit_hook(void);
 
 // stein_select.hip: the fused call's median behind its distance pass (k_spec_select, then k_hist_all unless n is small)
-// theta_all / score_all: the call's inputs, read (and dropped) by the select launch's warm slice when the operand is folded
+// theta_all / score_all: the call's inputs, read by the select launch's slice when the operand is folded: dropped, or --
+// want_maxima -- reduced to the column maxima in v.cmax (zeroed by the prologue).  *took_maxima: whether the slice ran and
+// did so (not under stein_debug_no_warm: the caller then launches the column maxima itself)
 int stein_fused_select(const StepViews& v, int64_t n, int64_t d, float* h2_out, const void* theta_all, const void* score_all,
-                       hipStream_t stream);
+                       bool want_maxima, bool* took_maxima, hipStream_t stream);
 
 // stein_fp32.hip: the fp32-input MFMA kernels, for calls without the split planes (what stein_x3_distance and
 // stein_x3_contract_partial are for the split path).  window: also feed the speculative median window (v.spec, v.spec_buf)

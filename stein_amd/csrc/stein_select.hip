@@ -674,15 +674,43 @@ __device__ __forceinline__ void solo_select(const float* __restrict__ D, long ld
 
 // D != NULL ("solo", fused call on a small symmetric block): a miss is resolved here by solo_select
 // Workgroups 1 .. gridDim.x - 1 (fused call with the folded operand only; the select is workgroup 0, one workgroup on an
-// otherwise idle chip) read warm0 and warm1 -- theta and the score, warm4 16-byte pieces each -- and drop the values: the
-// distance pass has just pushed 0.5 GB of D through the memory-side cache, and k_split_w, next but one in the stream, then
-// finds its inputs there again.  They store nothing, wait for nothing and nothing waits for them.
+// otherwise idle chip) are a slice that reads warm0 and warm1 -- the score and theta: the distance pass has just pushed
+// 0.5 GB of D through the memory-side cache, and k_split_w, next but one in the stream, then finds its inputs there again.
+// They wait for nothing and the select does not wait for them.
+//   slice = SLICE_READ (the step also contracts K with theta: dK / KSD): warm4 16-byte pieces of each, values dropped
+//   slice = SLICE_MAX16 / SLICE_MAX4 (phi alone): the same bytes as [n][d] matrices, reduced to their column maxima in
+//     cmax = [score | theta] (zeroed by the prologue), which k_split_w turns into W's and theta's scales -- the step has no
+//     k_colmax launch.  Workgroup 1 + rg * ncg + cb scans column block cb (256 columns in the 16-byte form for d % 4 == 0
+//     and aligned inputs, 64 in the 4-byte form) of the rows 16 rg + wave, + 16 nrg, ... of BOTH matrices: eight loads in
+//     flight per lane, and nrg atomics per column (colmax_scan, colmax_commit: stein_common.h)
+enum { SLICE_READ = 0, SLICE_MAX16 = 1, SLICE_MAX4 = 2 };
+template <bool V4>
+__device__ __forceinline__ void slice_maxima(const float* __restrict__ G, const float* __restrict__ T, int n, int d,
+                                             u32* __restrict__ cmax, int dc, int ncg, int nrg, u32* red) {
+  constexpr int CW = V4 ? 4 : 1;
+  const int w = (int)blockIdx.x - 1, cb = w % ncg, rg = w / ncg;
+  const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
+  const float* const X[2] = {G, T};
+  u32 m[2][CW];
+  colmax_scan<float, V4, 2>(X, n, d, (cb * 64 + cx) * CW, (long)rg * 16 + ry, (long)nrg * 16, m);
+  colmax_commit<CW, 2>(m, cx, cb, d, red, cmax, dc);
+}
+
 __global__ __launch_bounds__(1024) void k_spec_select(SelState* st, SpecState* sp, const u64* __restrict__ slots,
                                                       float ln_n, float* h2_out, int update,
                                                       const float* __restrict__ D, long ldD, int n,
                                                       const float4* __restrict__ warm0, const float4* __restrict__ warm1,
-                                                      long warm4) {
+                                                      long warm4, int slice, int d, u32* __restrict__ cmax, int dc, int ncg,
+                                                      int nrg) {
   if (blockIdx.x) {
+    if (slice != SLICE_READ) {
+      __shared__ u32 red[2 * 256];
+      if (slice == SLICE_MAX16)
+        slice_maxima<true>((const float*)warm0, (const float*)warm1, n, d, cmax, dc, ncg, nrg, red);
+      else
+        slice_maxima<false>((const float*)warm0, (const float*)warm1, n, d, cmax, dc, ncg, nrg, red);
+      return;
+    }
     const long stride = (long)(gridDim.x - 1) * 1024;
     auto keep = [](const float4& a) { asm volatile("" ::"v"(a.x), "v"(a.y), "v"(a.z), "v"(a.w)); };
     long i = (long)(blockIdx.x - 1) * 1024 + threadIdx.x;
@@ -957,22 +985,41 @@ extern "C" int stein_debug_hist_all_vblocks(int nvb) {   // (tuning aid: virtual
 
 // ---- the fused call's select ----------------------------------------------------------------------------------------
 int stein_fused_select(const StepViews& v, int64_t n, int64_t d, float* h2_out, const void* theta_all,
-                       const void* score_all, hipStream_t s) {
+                       const void* score_all, bool want_maxima, bool* took_maxima, hipStream_t s) {
   // the window either yields the median now (spec->hit) or the radix-select passes below run; each of them
   // checks the flag on the device, so nothing here waits for the host
   const bool solo = n <= SOLO_MAX_N;   // small block: a miss is resolved inside k_spec_select, no histogram launches
-  // the warm slice (k_spec_select): folded operand, fp32 inputs on 16-byte boundaries; one workgroup per 128 KB of a
-  // matrix, at most SPEC_WARM_WGS (one per compute unit beside the select's)
+  // the slice (k_spec_select): folded operand, fp32 inputs
   long warm4 = 0;
-  int warm_wgs = 0;
-  if (v.L.fold && !g_no_warm && theta_all && score_all && (((uintptr_t)theta_all | (uintptr_t)score_all) & 15u) == 0) {
+  int warm_wgs = 0, slice = SLICE_READ, ncg = 1, nrg = 1;
+  const bool aligned = (((uintptr_t)theta_all | (uintptr_t)score_all) & 15u) == 0;
+  *took_maxima = false;
+  if (v.L.fold && !g_no_warm && theta_all && score_all && want_maxima) {
+    // column maxima: column blocks x row groups, about SPEC_WARM_WGS workgroups (one per compute unit beside the select's).
+    // A wave takes the rows of its slot (n / 16 slots) four at a time: the row groups are as few as make every wave's
+    // rows a whole number of such rounds where n allows it -- a fifth row would be a second trip to memory for one load
+    // (C3: 1024 slots -> 2 rounds of 128 groups, not 255 groups with a ragged tail) -- and fewer groups are fewer
+    // same-address atomics per column
+    const bool v4 = aligned && d % 4 == 0;
+    slice = v4 ? SLICE_MAX16 : SLICE_MAX4;
+    const int64_t cw = v4 ? 256 : 64;
+    const int64_t blocks = (d + cw - 1) / cw, slots = (n + 15) / 16;
+    const int64_t max_rg = SPEC_WARM_WGS / blocks > 0 ? SPEC_WARM_WGS / blocks : 1;
+    const int64_t rounds = (slots + 4 * max_rg - 1) / (4 * max_rg);
+    ncg = (int)blocks;
+    nrg = (int)((slots + 4 * rounds - 1) / (4 * rounds));
+    warm_wgs = ncg * nrg;
+    *took_maxima = true;
+  } else if (v.L.fold && !g_no_warm && theta_all && score_all && aligned) {
+    // the pure reader: 16-byte boundaries only; one workgroup per 128 KB of a matrix, at most SPEC_WARM_WGS
     warm4 = (long)(n * d) >> 2;
     const long want = (warm4 + 8191) / 8192;
     warm_wgs = (int)(want < SPEC_WARM_WGS ? want : SPEC_WARM_WGS);
   }
+  // (the slice's matrices in cmax's order: the score first)
   hipLaunchKernelGGL(k_spec_select, dim3(1 + warm_wgs), dim3(1024), 0, s, v.sel, v.spec, v.spec_buf, (float)log((double)n),
                      h2_out, 1, solo ? (const float*)v.D : (const float*)nullptr, (long)v.L.ld_dist, (int)n,
-                     (const float4*)theta_all, (const float4*)score_all, warm4);
+                     (const float4*)score_all, (const float4*)theta_all, warm4, slice, (int)d, v.cmax, (int)v.L.x3_dc, ncg, nrg);
   LAUNCH_CHECK("k_spec_select");
   if (solo) return STEIN_OK;
   // chained radix select, ONE launch whatever n (k_hist_all: in-launch level barriers that need no co-residency; it returns

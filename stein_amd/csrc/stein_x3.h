@@ -12,6 +12,9 @@ struct SplitFused {
   HistSync* done;
   const PrologueArgs* prologue;   // bf16 inputs: the launch also does the prologue's work (which writes the neutral scales)
   int fold;   // folded operand: the score only feeds the column maxima; 1: no theta^T planes either, 2: with them
+  // fold == 1: no column maxima here at all.  The prologue left max|theta| of each of its nwg workgroups in wgmax, and
+  // k_split_rows makes the scale of theta's row-major planes (and sc[4 dc + 0 .. 2]) of them; the maxima come with the select
+  const u32* wgmax; int nwg;
 };
 int stein_x3_split(const StepViews& v, const void* theta_all, const void* score_all, int dtype, int64_t n, int64_t d,
                    hipStream_t stream, const SplitFused* fused);
@@ -19,6 +22,10 @@ int stein_x3_split(const StepViews& v, const void* theta_all, const void* score_
 bool stein_fold_pays(int64_t n, int64_t d);   // the default gate (STEIN_FLAG_FOLD / STEIN_FLAG_NO_FOLD override it)
 int stein_x3_split_w(const StepViews& v, const float* theta_all, const float* score_all, int64_t n, int64_t d,
                      const float* h2_dev, hipStream_t stream);   // after the median, before the contraction
+// the column maxima of both matrices into v.cmax (zeroed by the caller's prologue), no scales: the folded step's fallback
+// when the select launch runs without its slice
+int stein_x3_colmax(const StepViews& v, const float* theta_all, const float* score_all, int64_t n, int64_t d,
+                    hipStream_t stream);
 int stein_x3_contract_fold(const StepViews& v, const float* h2_dev, int64_t n, int64_t d, bool with_theta,
                            hipStream_t stream);
 // window: also feed the speculative median window (v.spec, v.spec_buf; needs v.hist)

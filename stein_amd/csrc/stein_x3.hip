@@ -16,7 +16,11 @@
 //
 //   k_colmax, k_make_scales   column maxima -> power-of-two scales (KIND 2; all ones otherwise)
 //   k_split         theta, score -> 16-bit operand tiles ("planes", layout below)
-//   k_split_w       theta, score, h2 -> the planes of W = score - theta / h2 (the fused call's folded operand, behind the median)
+//   k_split_rows    theta -> its row-major planes alone, scaled by max|theta| as the fused call's prologue found it (the folded
+//                   step that is asked for phi alone: it launches neither k_colmax nor k_make_scales -- the column maxima are
+//                   taken by the select launch's slice, stein_select.hip, and turned into scales by k_split_w)
+//   k_split_w       theta, score, h2 -> the planes of W = score - theta / h2 (the fused call's folded operand, behind the median);
+//                   W's column scales and theta's, from the column maxima
 //   k_distance_x3   S = T T^T from the planes; shares the fp32 kernel's epilogue (D, level-0 histogram or window counting).
 //                   Single rank: only the 128 x 128 tiles on and above the diagonal are computed AND stored
 //   k_phi_x3fs      warp-specialised contraction: producer waves build P = exp2(c D) (split on the fly) in LDS -- a k tile
@@ -51,7 +55,7 @@
 //   [4dc + 0]     in-scale of theta for T3 (one factor: S = T T^T mixes the columns)
 //   [4dc + 1]     two_s = 2 / in^2:  D = r_i + r_j - two_s * S'
 //   [4dc + 2]     2^-PEXP, the rowsum(K) unscale
-//   then u32 [2][dc]: bit patterns of the column maxima of |score|, |theta| (scratch of k_colmax)
+//   then u32 [2][dc]: bit patterns of the column maxima of |score|, |theta| (k_colmax, or the slice of k_spec_select)
 
 #include "stein_x3.h"
 
@@ -87,39 +91,43 @@ __device__ __forceinline__ void split_pair(float x, float y, u32 (&w)[3]) {
 // ------------------------------------------------------------------------------------------------
 // scales (KIND 2)
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ u32 abs_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
-__device__ __forceinline__ u32 abs_bits(u16 v) { return ((u32)v << 16) & 0x7fffffffu; }
-// (pow2i and scale_exp: stein_x3_dev.h, the bootstrap kernel scales its image with them too)
+// (abs_bits: stein_common.h; pow2i and scale_exp: stein_x3_dev.h, the bootstrap kernel scales its image with them too)
 
-// maxima -> the scales area (see the header), by one workgroup of 256 threads.  enable = 0 writes the neutral scales.
+// the three entries behind the column scales (see the header) from the exponent of theta's one scale
+__device__ __forceinline__ void write_global_scales(float* __restrict__ sc, int dc, int sa, int pexp) {
+  sc[4 * dc + 0] = pow2i(sa);
+  sc[4 * dc + 1] = pow2i(1 - 2 * sa);
+  sc[4 * dc + 2] = pow2i(-pexp);
+}
+
+// maxima -> the scales area (see the header), by the first 256 threads of one workgroup (every thread of it must call:
+// barriers inside; red: 256 words).  enable = 0 writes the neutral scales.
 __device__ __forceinline__ void make_scales_body(const u32* cmax, int dc, float* __restrict__ sc, int pexp, int enable,
                                                  u32* red) {
   const int t = threadIdx.x;
-  u32 m = 0u;
-  for (int c = t; c < dc; c += 256) {
-    const u32 mg = load_fresh(cmax + c), mt = load_fresh(cmax + dc + c);
-    const int sg = enable ? scale_exp(mg, 100) : 0, st = enable ? scale_exp(mt, 100) : 0;
-    sc[c] = pow2i(sg);
-    sc[dc + c] = pow2i(st);
-    sc[2 * dc + c] = pow2i(-sg - pexp);
-    sc[3 * dc + c] = pow2i(-st - pexp);
-    m = max(m, mt);
+  if (t < 256) {
+    u32 m = 0u;
+    for (int c = t; c < dc; c += 256) {
+      const u32 mg = load_fresh(cmax + c), mt = load_fresh(cmax + dc + c);
+      const int sg = enable ? scale_exp(mg, 100) : 0, st = enable ? scale_exp(mt, 100) : 0;
+      sc[c] = pow2i(sg);
+      sc[dc + c] = pow2i(st);
+      sc[2 * dc + c] = pow2i(-sg - pexp);
+      sc[3 * dc + c] = pow2i(-st - pexp);
+      m = max(m, mt);
+    }
+    red[t] = m;
   }
-  red[t] = m;
   __syncthreads();
   for (int o = 128; o > 0; o >>= 1) {
     if (t < o) red[t] = max(red[t], red[t + o]);
     __syncthreads();
   }
-  if (t == 0) {
-    const int sa = enable ? scale_exp(red[0], 60) : 0;
-    sc[4 * dc + 0] = pow2i(sa);
-    sc[4 * dc + 1] = pow2i(1 - 2 * sa);
-    sc[4 * dc + 2] = pow2i(-pexp);
-  }
+  if (t == 0) write_global_scales(sc, dc, enable ? scale_exp(red[0], 60) : 0, pexp);
 }
 
-// column maxima of |X| [n][d] as bit patterns (non-negative floats order like unsigned integers)
+// column maxima of |X| [n][d] as bit patterns (non-negative floats order like unsigned integers): colmax_scan and
+// colmax_commit of stein_common.h on a grid of (column blocks, row groups, matrices)
 // blockIdx.z = 0: X0 -> cmax[0, dc), 1: X1 -> cmax[dc, 2 dc)
 // done != NULL (fused call: both matrices given, completion counters zeroed by the prologue): the last workgroup to finish
 // also turns the maxima into the scales, which saves the k_make_scales launch (round 4: a two-level count, so whatever the grid).
@@ -127,64 +135,21 @@ __device__ __forceinline__ void make_scales_body(const u32* cmax, int dc, float*
 // KB of a row instead of 256 bytes, sixteen waves walk sixteen rows at a time, and the workgroup's maxima are added by 256
 // threads, one column each (coalesced atomics, and a quarter as many per column as with 256-thread workgroups: the
 // same-address atomic chains were the larger part of the 4-byte form's 14-16 us at C3).
+// The folded step that is asked for phi alone does not launch this kernel: the same body runs in the select launch's slice
+// (k_spec_select, stein_select.hip); only under stein_debug_no_warm does it launch, with done = NULL.
 template <typename TIN, bool V4>
 __global__ __launch_bounds__(V4 ? 1024 : 256) void k_colmax(const TIN* __restrict__ X0, const TIN* __restrict__ X1, int n, int d,
                                                             u32* __restrict__ cmax0, int dc, int zbase, float* __restrict__ sc,
                                                             int pexp, HistSync* done) {
   const int z = blockIdx.z + zbase;
-  const TIN* __restrict__ X = z ? X1 : X0;
-  u32* __restrict__ cmax = cmax0 + (z ? dc : 0);
   constexpr int CW = V4 ? 4 : 1;                 // columns per lane
   constexpr int NW = V4 ? 16 : 4;                // waves = rows in flight per workgroup
-  __shared__ u32 red[NW][64 * CW];
+  __shared__ u32 red[256];                       // (64 CW words for the maxima, 256 for make_scales_body)
   const int t = threadIdx.x, cx = t & 63, ry = t >> 6;
-  const int col = (blockIdx.x * 64 + cx) * CW;
-  u32 m[CW];
-#pragma unroll
-  for (int e = 0; e < CW; ++e) m[e] = 0u;
-  if (col < d) {
-    // four independent loads in flight per lane (one dependent load at a time read the matrices at 2 TB/s)
-    const long step = (long)gridDim.y * NW;
-    long r = (long)blockIdx.y * NW + ry;
-    if constexpr (V4) {
-      if constexpr (std::is_same<TIN, float>::value) {
-        u32 m1[4] = {0u, 0u, 0u, 0u}, m2[4] = {0u, 0u, 0u, 0u}, m3[4] = {0u, 0u, 0u, 0u};
-        auto ld = [&](long row) { return *reinterpret_cast<const float4*>(X + (size_t)row * d + col); };
-        auto up = [&](u32 (&acc)[4], const float4& v) {
-          acc[0] = max(acc[0], abs_bits(v.x)); acc[1] = max(acc[1], abs_bits(v.y));
-          acc[2] = max(acc[2], abs_bits(v.z)); acc[3] = max(acc[3], abs_bits(v.w));
-        };
-        for (; r + 3 * step < n; r += 4 * step) {
-          const float4 a0 = ld(r), a1 = ld(r + step), a2 = ld(r + 2 * step), a3 = ld(r + 3 * step);
-          up(m, a0); up(m1, a1); up(m2, a2); up(m3, a3);
-        }
-        for (; r < n; r += step) { const float4 a0 = ld(r); up(m, a0); }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) m[e] = max(max(m[e], m1[e]), max(m2[e], m3[e]));
-      }
-    } else {
-      u32 m1 = 0u, m2 = 0u, m3 = 0u;
-      for (; r + 3 * step < n; r += 4 * step) {
-        const u32 a0 = abs_bits(X[(size_t)r * d + col]), a1 = abs_bits(X[(size_t)(r + step) * d + col]);
-        const u32 a2 = abs_bits(X[(size_t)(r + 2 * step) * d + col]), a3 = abs_bits(X[(size_t)(r + 3 * step) * d + col]);
-        m[0] = max(m[0], a0); m1 = max(m1, a1); m2 = max(m2, a2); m3 = max(m3, a3);
-      }
-      for (; r < n; r += step) m[0] = max(m[0], abs_bits(X[(size_t)r * d + col]));
-      m[0] = max(max(m[0], m1), max(m2, m3));
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < CW; ++e) red[ry][cx * CW + e] = m[e];
-  __syncthreads();
-  if (t < 64 * CW) {                             // one thread per column of the workgroup's span
-    const int c = blockIdx.x * 64 * CW + t;
-    if (c < d) {
-      u32 v = 0u;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) v = max(v, red[w][t]);
-      atomicMax(&cmax[c], v);
-    }
-  }
+  const TIN* const X[1] = {z ? X1 : X0};
+  u32 m[1][CW];
+  colmax_scan<TIN, V4, 1>(X, n, d, ((int)blockIdx.x * 64 + cx) * CW, (long)blockIdx.y * NW + ry, (long)gridDim.y * NW, m);
+  colmax_commit<CW, 1>(m, cx, (int)blockIdx.x, d, red, cmax0 + (z ? dc : 0), dc);
   if (done) {
     __shared__ u32 s_last;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's maxima have been acknowledged
@@ -194,7 +159,7 @@ __global__ __launch_bounds__(V4 ? 1024 : 256) void k_colmax(const TIN* __restric
       s_last = tree_report_done(done->cm_leaf, &done->cm_top, id, gridDim.x * gridDim.y * gridDim.z) ? 1u : 0u;
     }
     __syncthreads();
-    if (s_last) make_scales_body(cmax0, dc, sc, pexp, 1, &red[0][0]);   // (written for 256 threads; more of them repeat columns: same values)
+    if (s_last) make_scales_body(cmax0, dc, sc, pexp, 1, red);
   }
 }
 
@@ -324,10 +289,53 @@ __global__ __launch_bounds__(256) void k_split(const TIN* __restrict__ X0, const
   tp_store<KIND>(tile, Tt, ntk_t, dc, nk, row0, col0, t);
 }
 
+// k_split for the folded step that is asked for phi alone (fp32): theta's row-major image R and nothing else -- no
+// transposed image, so no LDS tile -- with the image's one scale formed here instead of read: the prologue left max|theta| of
+// each of its nwg workgroups in wgmax (PrologueArgs::wgmax), every workgroup reduces the words (issued in front of its row
+// loads, so the two latencies overlap) to sa = scale_exp(max, 60), the value make_scales_body forms from the maximum over
+// theta's column maxima, and workgroup (0, 0) writes sc[4 dc + 0 .. 2] for the distance pass, the contraction and the
+// finish pass to find.  Tiles, thread mapping and arithmetic are k_split's: R keeps its bits.
+__global__ __launch_bounds__(256) void k_split_rows(const float* __restrict__ X, int n, int d, u16* __restrict__ R, long r_rows,
+                                                    int dk, int dc, float* __restrict__ sc, int vec,
+                                                    const u32* __restrict__ wgmax, int nwg) {
+  __shared__ u32 s_wmax[4];
+  const int t = threadIdx.x;
+  const int row0 = blockIdx.y * 64, col = blockIdx.x * 64 + (t & 15) * 4;
+  const long ntk_r = dk >> 5;
+  u32 m = 0u;
+  for (int i = t; i < nwg; i += 256) m = max(m, wgmax[i]);
+  float v[2][2][4];
+#pragma unroll
+  for (int p = 0; p < 2; ++p)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) load_row4(X, row0 + 2 * tp_pair(t, p) + h, col, n, d, vec, v[p][h]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = max(m, (u32)__shfl_xor((int)m, o));
+  if ((t & 63) == 0) s_wmax[t >> 6] = m;
+  __syncthreads();
+  const int sae = scale_exp(max(max(s_wmax[0], s_wmax[1]), max(s_wmax[2], s_wmax[3])), 60);
+  const float sa = pow2i(sae);
+  if (t == 0 && blockIdx.x == 0 && blockIdx.y == 0) write_global_scales(sc, dc, sae, PEXP_H2);
+#pragma unroll
+  for (int p = 0; p < 2; ++p)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int row = row0 + 2 * tp_pair(t, p) + h;
+      if (row < r_rows && col < dk) {   // col % 4 == 0: the 4 entries stay inside one 32-wide k tile
+        u32 wa[3], wb[3];
+        split_pair<2>(v[p][h][0] * sa, v[p][h][1] * sa, wa);
+        split_pair<2>(v[p][h][2] * sa, v[p][h][3] * sa, wb);
+        u16* dst = R + (((size_t)(row >> 7) * ntk_r + (col >> 5)) * 3) * XTILE_E + vfrag_offset(row & 127, (col & 31) >> 3) + (col & 7);
+#pragma unroll
+        for (int s = 0; s < 2; ++s) *reinterpret_cast<uint2*>(dst + s * XTILE_E) = make_uint2(wa[s], wb[s]);
+      }
+    }
+}
+
 // The folded operand (fused call, fp32 inputs; stein_fold_pays): phi_i = (sum_j K_ij w_j + rowsum_i theta_i / h2) / n with
 // w_j = g_j - theta_j / h2, so the contraction multiplies K with ONE matrix.  W depends on h2: this kernel runs between the
 // median and the contraction.  One 64 x 64 tile of W per workgroup, written like k_split's transposed image into Wt (the
-// score's plane storage).  Column c's in-scale puts the bound max_c|g| + max_c|theta| / h2 (from k_colmax's maxima: no
+// score's plane storage).  Column c's in-scale puts the bound max_c|g| + max_c|theta| / h2 (from the column maxima: no
 // pass over the inputs) into [2^13, 2^14); it replaces the score's scales ([0, dc) and [2dc, 3dc) of the scales area).  The
 // bound can be twice the true maximum of |w| and more where the terms cancel: the absolute error stays 2^-38 of the bound,
 // which is what K.G and K.theta / h2 carry separately on the unfolded path.  h2 = 0: 1 / h2 = inf, the bound is inf or NaN,
@@ -351,6 +359,11 @@ __global__ __launch_bounds__(256) void k_split_w(const float* __restrict__ T, co
     if (blockIdx.y == 0 && (t >> 4) == 0 && c < dc) {
       sc[c] = scq[q];
       sc[2 * dc + c] = pow2i(-se - PEXP_H2);
+      // theta's own column scales, as make_scales_body writes them: the folded step that takes its maxima in the select
+      // launch has nobody else to (elsewhere these stores repeat what is there)
+      const int st = scale_exp(cmax[dc + c], 100);
+      sc[dc + c] = pow2i(st);
+      sc[3 * dc + c] = pow2i(-st - PEXP_H2);
     }
   }
 #pragma unroll
@@ -1013,6 +1026,27 @@ static void launch_split(hipStream_t stream, const TIN* theta, const TIN* score,
                      (long)L.x3_rows, (int)L.x3_dk, Tt3, Gt3, (int)L.x3_dc, (long)L.x3_nk, sc, zbase, PrologueArgs{}, vec);
 }
 
+// k_colmax over the matrices given (a NULL one is left out: its half of cmax keeps its values)
+static void launch_colmax(const StepViews& v, const float* score_all, const float* theta_all, int64_t n, int64_t d,
+                          HistSync* fuse_done, hipStream_t stream) {
+  const int dc = (int)v.L.x3_dc;
+  const int zbase = score_all ? 0 : 1;
+  const unsigned nz = (score_all ? 1u : 0u) + (theta_all ? 1u : 0u);
+  int gy = (int)((n + 63) / 64);
+  if (gy > 256) gy = 256;
+  const bool v4 = d % 4 == 0 && (!score_all || ((uintptr_t)score_all & 15) == 0) && (!theta_all || ((uintptr_t)theta_all & 15) == 0);
+  if (v4) {
+    const int gy4 = gy > 64 ? 64 : gy;
+    const dim3 grid((unsigned)((d + 255) / 256), (unsigned)gy4, nz);
+    hipLaunchKernelGGL((k_colmax<float, true>), grid, dim3(1024), 0, stream, score_all, theta_all, (int)n, (int)d, v.cmax, dc,
+                       zbase, v.sc, PEXP_H2, fuse_done);
+  } else {
+    const dim3 grid((unsigned)((d + 63) / 64), (unsigned)gy, nz);
+    hipLaunchKernelGGL((k_colmax<float, false>), grid, dim3(256), 0, stream, score_all, theta_all, (int)n, (int)d, v.cmax, dc,
+                       zbase, v.sc, PEXP_H2, fuse_done);
+  }
+}
+
 int stein_x3_split(const StepViews& v, const void* theta_all, const void* score_all, int dtype, int64_t n, int64_t d,
                    hipStream_t stream, const SplitFused* fused) {
   const SteinLayout& L = v.L;
@@ -1021,23 +1055,22 @@ int stein_x3_split(const StepViews& v, const void* theta_all, const void* score_
   HistSync* fuse_done = fused && theta_all && score_all ? fused->done : nullptr;
   const PrologueArgs* prologue = fused ? fused->prologue : nullptr;
   const int fold = fused ? fused->fold : 0;
+  // the fused call's folded step, phi alone: no maxima and no scales here -- k_split_rows takes theta's one scale from the
+  // prologue's per-workgroup maxima, the column maxima come with the select launch, the column scales with k_split_w
+  const u32* wgmax = fused && kind == 2 && fold == 1 ? fused->wgmax : nullptr;
+  if (wgmax) {
+    const int vec = d % 4 == 0 && ((uintptr_t)theta_all & 15u) == 0;   // 16-byte loads (load_row4)
+    const dim3 grid((unsigned)((L.x3_dk + 63) / 64), (unsigned)((L.x3_rows + 63) / 64));
+    hipLaunchKernelGGL(k_split_rows, grid, dim3(256), 0, stream, (const float*)theta_all, (int)n, (int)d, v.T3, (long)L.x3_rows,
+                       (int)L.x3_dk, dc, v.sc, vec, wgmax, fused->nwg);
+    LAUNCH_CHECK("k_split_rows");
+    return STEIN_OK;
+  }
   if (kind == 2) {   // column maxima of the matrices given (cmax = [score | theta]); the other half keeps its values
     const int zbase = score_all ? 0 : 1;
     const unsigned nz = (score_all ? 1u : 0u) + (theta_all ? 1u : 0u);
     if (!fuse_done) HIP_TRY(hipMemsetAsync(v.cmax + (size_t)zbase * dc, 0, (size_t)nz * dc * sizeof(u32), stream));
-    int gy = (int)((n + 63) / 64);
-    if (gy > 256) gy = 256;
-    const bool v4 = d % 4 == 0 && (!score_all || ((uintptr_t)score_all & 15) == 0) && (!theta_all || ((uintptr_t)theta_all & 15) == 0);
-    if (v4) {
-      const int gy4 = gy > 64 ? 64 : gy;
-      const dim3 grid((unsigned)((d + 255) / 256), (unsigned)gy4, nz);
-      hipLaunchKernelGGL((k_colmax<float, true>), grid, dim3(1024), 0, stream, (const float*)score_all, (const float*)theta_all,
-                         (int)n, (int)d, v.cmax, dc, zbase, v.sc, PEXP_H2, fuse_done);
-    } else {
-      const dim3 grid((unsigned)((d + 63) / 64), (unsigned)gy, nz);
-      hipLaunchKernelGGL((k_colmax<float, false>), grid, dim3(256), 0, stream, (const float*)score_all, (const float*)theta_all,
-                         (int)n, (int)d, v.cmax, dc, zbase, v.sc, PEXP_H2, fuse_done);
-    }
+    launch_colmax(v, (const float*)score_all, (const float*)theta_all, n, d, fuse_done, stream);
     LAUNCH_CHECK("k_colmax");
   }
   if (kind == 2 ? !fuse_done : !prologue) {   // (bf16 inputs: the fused call's prologue writes the neutral scales)
@@ -1061,6 +1094,13 @@ int stein_x3_split(const StepViews& v, const void* theta_all, const void* score_
 // at the smallest block measured to gain (4096 x 256: n^2 d = 4.3e9); below it the step is a chain of latency-bound launches.
 constexpr double FOLD_MIN_WORK = 4.0e9;   // n * n * d
 bool stein_fold_pays(int64_t n, int64_t d) { return d > 128 && (double)n * (double)n * (double)d >= FOLD_MIN_WORK; }
+
+int stein_x3_colmax(const StepViews& v, const float* theta_all, const float* score_all, int64_t n, int64_t d,
+                    hipStream_t stream) {
+  launch_colmax(v, score_all, theta_all, n, d, nullptr, stream);
+  LAUNCH_CHECK("k_colmax");
+  return STEIN_OK;
+}
 
 int stein_x3_split_w(const StepViews& v, const float* theta_all, const float* score_all, int64_t n, int64_t d,
                      const float* h2_dev, hipStream_t stream) {

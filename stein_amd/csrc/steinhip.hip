@@ -120,7 +120,7 @@ __global__ __launch_bounds__(256) void k_phi_finish(const float* __restrict__ OG
   const double ih = 1.0 / (double)h2;
   const bool need_t = !FOLD || KSD || dK != nullptr;
   auto kg = [&](float o, float t) { return FOLD ? (double)o + (double)t * ih : (double)o; };   // (K.G)_e for the statistic
-  if (vec) {   // host: d % 4 == 0 and every pointer aligned for four columns at a time
+  if (vec == 1) {   // host: d % 4 == 0 and every pointer aligned for four columns at a time
     // four consecutive columns of one row per step, 16-byte loads and stores (one entry at a time with an integer
     // division each, the kernel moved its 68 MB at 2.8 TB/s; bf16 inputs took that path until round 4: 19 us at C2)
     // NZ j ranges of OG and RS and NT of OT known at compile time (NZ = 1, 2, 4, NT = NZ or, folded, 0 or 1; NZ = 0: any
@@ -212,6 +212,34 @@ __global__ __launch_bounds__(256) void k_phi_finish(const float* __restrict__ OG
     else if (split == 2) run_nz(integral_constant<int, 2>());
     else if (split == 4) run_nz(integral_constant<int, 4>());
     else run(integral_constant<int, 0>(), integral_constant<int, 0>());
+  } else if (vec == 2) {
+    // d % 4 == 0 and only the input rows (theta; the score of the statistic) off their 16-byte boundaries -- a view into a
+    // larger buffer: the entries one at a time, but a thread takes the four of an element group of the branch above and adds
+    // their squares as that branch does, so |phi|^2 is to the bit what aligned inputs give (the branch below deals the
+    // entries to the threads one by one and adds them in another order)
+    for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < (total >> 2); q += (long)gridDim.x * 256) {
+      const int i = (int)(q / (d >> 2));
+      float rs = 0.f;
+      for (int z = 0; z < split; ++z) rs += RS[(size_t)z * n_local + i];
+      double p2[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const long e = (q << 2) + c;
+        float og = 0.f, ot = 0.f;
+        for (int z = 0; z < split; ++z) {
+          og += OG[z * zs + e];
+          if (FOLD ? need_t && z < tsplit : true) ot += OT[z * zs + e];
+        }
+        const float th = elem_f32(T + (size_t)row0 * d + e);
+        const float dk = (rs * th - ot) / h2;
+        const float ph = FOLD ? (og + rs * th / h2) / fn : (og + dk) / fn;
+        phi[e] = ph;
+        if (dK) dK[e] = dk;
+        p2[c] = (double)ph * (double)ph;
+        if constexpr (KSD) ksd_terms(elem_f32(G + (size_t)row0 * d + e), kg(og, ot), ot, th, rs, ih, ks, kd);
+      }
+      sq += (p2[0] + p2[1]) + (p2[2] + p2[3]);
+    }
   } else {
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
       const int i = (int)(e / d);
@@ -551,8 +579,9 @@ static int finish_stage(const StepViews& v, const BlockShape& b, const void* the
   auto al16 = [](const void* p) { return ((uintptr_t)p & 15u) == 0; };
   const size_t tsz = b.dtype == STEIN_BF16 ? 2 : 4;
   auto rows_aligned = [&](const void* p) { return (((uintptr_t)p + (size_t)b.row0 * b.d * tsz) & (4 * tsz - 1)) == 0; };
-  const int vec = (b.d % 4 == 0) && al16(v.OG) && al16(v.OT) && al16(phi_local) && al16(dK_out) && rows_aligned(theta_all) &&
-                  (!ksd || rows_aligned(score_all));
+  // 0: one entry at a time; 1: four columns at a time; 2: as 1 with the input rows off their 16-byte boundaries (k_phi_finish)
+  const bool group4 = (b.d % 4 == 0) && al16(v.OG) && al16(v.OT) && al16(phi_local) && al16(dK_out);
+  const int vec = !group4 ? 0 : (rows_aligned(theta_all) && (!ksd || rows_aligned(score_all))) ? 1 : 2;
   auto launch = [&](auto tin, auto ksd_tag, auto fold_tag) {
     using TIN = decltype(tin);
     hipLaunchKernelGGL((k_phi_finish<TIN, decltype(ksd_tag)::value, decltype(fold_tag)::value>), dim3((unsigned)L.sq_blocks),
@@ -925,9 +954,14 @@ static int fused_prologue(const StepViews& v, const BlockShape& b, const void* t
   pa.neutral_sc = bf16_split ? v.sc : (float*)nullptr;
   pa.dc = (int)v.L.x3_dc;
   pa.folded = fold ? 1u : 0u;
-  const SplitFused fused{(HistSync*)v.table, bf16_split ? &pa : nullptr, fold};
+  // fold == 1: no launch of the column maxima in front of the distance pass -- the prologue takes max|theta| (all the
+  // distance pass needs of them) and k_split_rows turns it into the scale; the maxima themselves come with the select launch
+  pa.wgmax = fold == 1 ? (u32*)((char*)v.table + PRO_WGMAX_AT) : (u32*)nullptr;
+  int64_t nwg = (b.n + 3) / 4 + PRO_INIT_BLOCKS;
+  if (pa.wgmax && nwg > PRO_MAX_WGS) nwg = PRO_MAX_WGS;   // (every other path keeps its grid)
+  const SplitFused fused{(HistSync*)v.table, bf16_split ? &pa : nullptr, fold, pa.wgmax, (int)nwg};
   if (bf16_split) return stein_x3_split(v, theta_all, score_all, b.dtype, b.n, b.d, s, &fused);
-  const dim3 grid((unsigned)((b.n + 3) / 4 + PRO_INIT_BLOCKS));
+  const dim3 grid((unsigned)nwg);
   if (b.dtype == STEIN_BF16)
     hipLaunchKernelGGL(k_prologue<unsigned short>, grid, dim3(256), 0, s, (const unsigned short*)theta_all, pa);
   else
@@ -973,7 +1007,12 @@ extern "C" int stein_svgd_phi(const void* theta_all, const void* score_all, int6
   // eight launches whatever n (the last workgroups of k_colmax and k_phi_finish are found with two-level completion counts,
   // HistSync, so no grid is too large for them); bf16 inputs: six.
   // folded operand (L.fold: split path, fp32 inputs, where it pays or is forced): the contraction multiplies K with
-  // W = G - theta / h2 alone; with dK_out or the Stein discrepancy, with [W | theta] -- phi comes from the W half either way
+  // W = G - theta / h2 alone; with dK_out or the Stein discrepancy, with [W | theta] -- phi comes from the W half either way.
+  // Its launches: k_prologue, k_colmax, k_split (theta), distance, k_spec_select (+ a slice that reads theta and the score
+  // into the cache), k_hist_all, k_split_w, contraction, k_phi_finish.  With nothing but phi asked for (fold == 1) k_colmax
+  // leaves: k_prologue, k_split_rows, distance, k_spec_select, k_hist_all, k_split_w, contraction, k_phi_finish -- the prologue
+  // takes max|theta| from the rows it reads anyway, k_split_rows makes the distance pass's scale of it, and the select launch's
+  // slice takes the column maxima from the bytes it streams anyway, for k_split_w, which writes theta's scales too.
   const bool fold_theta = L.fold && (dK_out || ksd);
   if ((rc = fused_prologue(v, b, theta_all, score_all, flags, s, L.fold ? (fold_theta ? 2 : 1) : 0))) return rc;
   if ((rc = clk.mark(STEIN_T_DISTANCE, s))) return rc;
@@ -982,7 +1021,13 @@ extern "C" int stein_svgd_phi(const void* theta_all, const void* score_all, int6
   const int sf = STEIN_STAGE_SYMMETRIC | ((flags & STEIN_FLAG_TILE_DISTANCE) ? STEIN_STAGE_TILES : 0);
   if ((rc = distance_stage(v, b, theta_all, sf, true, s))) return rc;
   if ((rc = clk.mark(STEIN_T_MEDIAN, s))) return rc;
-  if ((rc = stein_fused_select(v, n, d, h2_out, theta_all, score_all, s))) return rc;
+  // fold == 1: the select launch's slice takes the column maxima k_split_w needs; with the slice switched off
+  // (stein_debug_no_warm) a k_colmax launch of its own does
+  const bool want_maxima = L.fold && !fold_theta;
+  bool slice_maxima = false;
+  if ((rc = stein_fused_select(v, n, d, h2_out, theta_all, score_all, want_maxima, &slice_maxima, s))) return rc;
+  if (want_maxima && !slice_maxima && (rc = stein_x3_colmax(v, (const float*)theta_all, (const float*)score_all, n, d, s)))
+    return rc;
   // the split path's symmetric distance pass stores only the tiles on and above the diagonal
   const bool upper = v.planes != nullptr;
   if (K_out && (rc = stein_kernel_matrix(v.D, L.ld_dist, n_local, n, h2_out, K_out, n,
