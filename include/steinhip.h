@@ -820,6 +820,70 @@ int stein_predict_rank_masses_workspace_bytes(int64_t n, size_t* out_bytes);
 int stein_predict_rank_masses(const double* weights, int64_t n, int mode, uint32_t* masses, double* info /* [2] */,
                               void* workspace, size_t ws_bytes, void* stream);
 
+/* The predictive distribution of y itself, observation noise included: the Gaussian mixture over the particles
+ *   F_b(t) = sum_p w_p Phi((t - z_pb) sqrt(tau_p)) / W
+ * with z_pb the linear output -- bit for bit what stein_predict_* write to pred with STEIN_PRED_LINK (the same device code) --
+ * tau_p = noise_precision (STEIN_GLM_LINEAR) or exp(log_gamma_p) (the network), and w_p = 1 (weights == NULL) or the
+ * caller's weights.  STEIN_GLM_LOGISTIC is refused (STEIN_E_UNSUPPORTED): y is Bernoulli there, and the predictive
+ * probability is the mean of the outputs with STEIN_PRED_MEAN (output="mean").
+ *
+ * stein_predict_*_ycdf: out[i][b] = F_b(t[i][b]), t and out [n_pts][batch] device floats, 1 <= n_pts <=
+ * STEIN_PRED_Y_POINTS_MAX.  With t = y this is the probability integral transform of the held-out rows; F_b(u) - F_b(l) is
+ * the mass of an interval.  Phi(x) = erfcf(-x / sqrt 2) / 2 in fp32; every lane keeps n_pts running fp32 sums over its
+ * particle slice, and a finish kernel adds the slices in slice order in fp64.
+ *
+ * stein_predict_*_yquantiles: out[i][b] and out_lo[i][b] (optional) bracket the levels[i]-quantile of F_b: predictive
+ * intervals of y.  levels: a HOST array of n_levels <= STEIN_PRED_RANKS_MAX doubles strictly inside (0, 1), read before the
+ * call returns; passes in [1, 12].  Method, passes + 1 forward passes and no host read of device memory:
+ *   bracket   [lo, hi] = the least and the largest component quantile z_pb + Phi^-1(level) / sqrt(tau_p) over the particles
+ *             with w_p > 0 (Phi^-1 on the host in fp64), each moved outward by 2^-21 (|z_pb| + |Phi^-1 / sqrt tau_p|) for what the
+ *             fp32 evaluation can lose: below the least every component's distribution function is under the level, at the
+ *             largest it has reached it, so the mixture's quantile lies between.
+ *   refine    7 interior points p_j = min(fma(hi - lo, j / 8, lo), hi) per (row, level); one pass sums F at all 7 n_levels
+ *             points (at most 56 running sums a lane); [lo, hi] becomes [p_(j-1), p_j] for the first j with F(p_j) >= level
+ *             (p_0 = lo), or [p_7, hi] when there is none.  lo <= hi always, and no end ever moves outward.
+ * The width shrinks eightfold per pass whatever the data: hi - lo <= (hi_0 - lo_0) / 8^passes plus one ulp of the bracket's
+ * ends; 8 passes reach neighbouring floats from any start.  out = hi, out_lo = lo: F evaluated as above is >= level at hi
+ * and < level at lo (or lo is the bracket pass's), which is the certificate.  A level's row does not depend on its company.
+ *
+ * Weights: as for the weighted summaries above, word for word -- fp64 device data, w >= 0, W > 0, never read on the host;
+ * the lanes hold fl32(w_p / W), the quotient in fp64, so a power-of-two rescaling changes no bit; a particle of weight zero
+ * is skipped even when its output is NaN; bad weights give NaN rows and STEIN_OK.  weights == NULL: every particle counts 1
+ * and the finish kernel divides by n.
+ * Deterministic: no atomics, the slices are merged in slice order; a repeated call is bit-identical.
+ * Workspace: stein_predict_ycdf_workspace_bytes(n, batch, n_pts) / stein_predict_yquantiles_workspace_bytes(n, batch,
+ * n_levels): the weight pass's header (16 bytes and 24 per particle slice), for the quantiles two floats per (row, level),
+ * and the partial sums, A = n_pts or 7 n_levels floats per (slice, row).  That is up to eleven times the summaries' state,
+ * so the calls cut the summaries' slice count down until the partial sums of a full call (8 points, 8 levels) fit 2^23 floats
+ * (then down to whole rounds of 512 workgroups where that leaves any, or to one slice; the slices of a call do not depend on
+ * how many points or levels it carries): they take at
+ * most 4 A min(min(ceil(n / 16), 1024) batch, 2^19 + batch, 2^23 / A + batch) bytes.  Monotone in every argument, independent
+ * of d, a multiple of 8; 8-byte aligned; it may hold anything on entry and carries nothing from call to call.
+ * Refused before any launch, in this order: a NULL pointer (cols, theta, X, t / levels, out) or n_pts / n_levels < 1
+ * (STEIN_E_BADARG); the shape, kind, column and width checks of stein_predict_* with their codes and messages; the logistic
+ * kind (STEIN_E_UNSUPPORTED); a noise_precision that is not positive and finite (STEIN_E_BADARG); n_pts >
+ * STEIN_PRED_Y_POINTS_MAX or n_levels > STEIN_PRED_RANKS_MAX (STEIN_E_UNSUPPORTED); a level outside (0, 1), NaN included, or
+ * passes outside [1, 12] (STEIN_E_BADARG); no workspace, too small a one or a misaligned one (STEIN_E_WORKSPACE). */
+enum { STEIN_PRED_Y_POINTS_MAX = 8, STEIN_PRED_Y_PASSES_MAX = 12 };
+int stein_predict_ycdf_workspace_bytes(int64_t n, int64_t batch, int64_t n_pts, size_t* out_bytes);
+int stein_predict_yquantiles_workspace_bytes(int64_t n, int64_t batch, int64_t n_levels, size_t* out_bytes);
+int stein_predict_glm_ycdf(const float* theta, int64_t n, int64_t d, int kind, int64_t w_col, int64_t n_feats, const float* X,
+                           int64_t batch, double noise_precision, const float* t /* device, [n_pts][batch] */, int64_t n_pts,
+                           const double* weights /* device [n] or NULL */, float* out /* [n_pts][batch] */,
+                           void* workspace, size_t ws_bytes, void* stream);
+int stein_predict_bnn_ycdf(const float* theta, int64_t n, int64_t d, int64_t n_in, int64_t n_hidden, const int64_t* cols,
+                           const float* X, int64_t batch, const float* t, int64_t n_pts, const double* weights, float* out,
+                           void* workspace, size_t ws_bytes, void* stream);
+int stein_predict_glm_yquantiles(const float* theta, int64_t n, int64_t d, int kind, int64_t w_col, int64_t n_feats,
+                                 const float* X, int64_t batch, double noise_precision, const double* levels /* host */,
+                                 int64_t n_levels, int passes, const double* weights /* device [n] or NULL */,
+                                 float* out /* [n_levels][batch] */, float* out_lo /* [n_levels][batch] or NULL */,
+                                 void* workspace, size_t ws_bytes, void* stream);
+int stein_predict_bnn_yquantiles(const float* theta, int64_t n, int64_t d, int64_t n_in, int64_t n_hidden, const int64_t* cols,
+                                 const float* X, int64_t batch, const double* levels, int64_t n_levels, int passes,
+                                 const double* weights, float* out, float* out_lo, void* workspace, size_t ws_bytes,
+                                 void* stream);
+
 /* small helpers used by the host layer */
 int stein_cast_f64_to_f32(const double* src, float* dst, int64_t count, void* stream);
 int stein_cast_f32_to_bf16(const float* src, void* dst, int64_t count, void* stream);

@@ -36,6 +36,8 @@ GLM_LINEAR, GLM_LOGISTIC = 0, 1
 PRED_LINK, PRED_MEAN = 0, 1
 PRED_RANKS_MAX = 8                # STEIN_PRED_RANKS_MAX: order statistics per stein_predict_*_ranks call
 MASS_NORMALISED, MASS_COUNTS = 0, 1   # STEIN_MASS_* (stein_predict_rank_masses)
+PRED_Y_POINTS_MAX = 8             # STEIN_PRED_Y_POINTS_MAX: points per stein_predict_*_ycdf call
+PRED_Y_PASSES_MAX = 12            # STEIN_PRED_Y_PASSES_MAX: refinement passes of a stein_predict_*_yquantiles call
 KERNEL_RBF, KERNEL_IMQ = 0, 1     # STEIN_KERNEL_* (stein_thin, stein_ksd_boot, stein_ksd_matmul, stein_weights)
 SPEC_TABLE_WORDS = 65544          # uint64 words of the rank-summed window table ...
 SPEC_TABLE_OFFSET_WORDS = 1 << 21  # ... which starts 2^21 words into the SPEC section (slots + entry buffer)
@@ -85,6 +87,14 @@ _SIGNATURES = {
     "stein_debug_predict_ranks_weighted_bits": [_int],
     "stein_predict_rank_masses_workspace_bytes": [_i64, _c.POINTER(_sz)],
     "stein_predict_rank_masses": [_vp, _i64, _int, _vp, _vp, _vp, _sz, _vp],
+    "stein_predict_ycdf_workspace_bytes": [_i64, _i64, _i64, _c.POINTER(_sz)],
+    "stein_predict_yquantiles_workspace_bytes": [_i64, _i64, _i64, _c.POINTER(_sz)],
+    "stein_predict_glm_ycdf": [_vp, _i64, _i64, _int, _i64, _i64, _vp, _i64, _dbl, _vp, _i64, _vp, _vp, _vp, _sz, _vp],
+    "stein_predict_bnn_ycdf": [_vp, _i64, _i64, _i64, _i64, _c.POINTER(_i64), _vp, _i64, _vp, _i64, _vp, _vp, _vp, _sz, _vp],
+    "stein_predict_glm_yquantiles": [_vp, _i64, _i64, _int, _i64, _i64, _vp, _i64, _dbl, _c.POINTER(_dbl), _i64, _int, _vp, _vp,
+                                     _vp, _vp, _sz, _vp],
+    "stein_predict_bnn_yquantiles": [_vp, _i64, _i64, _i64, _i64, _c.POINTER(_i64), _vp, _i64, _c.POINTER(_dbl), _i64, _int, _vp,
+                                     _vp, _vp, _vp, _sz, _vp],
     "stein_rank_begin": [_vp, _i64, _i64, _i64, _i64, _int, _vp, _sz, _int, _vp],
     "stein_rank_pick": [_i64, _i64, _i64, _i64, _int, _vp, _sz, _int, _vp, _vp, _vp, _vp],
     "stein_rank_radix": [_int, _int, _i64, _i64, _i64, _i64, _int, _vp, _sz, _int, _vp, _vp, _vp],
@@ -404,6 +414,22 @@ def debug_predict_ranks_weighted_bits(bits):
     """Test hook (per calling thread): digit bits per level of the stein_predict_*_ranks_weighted calls (1 .. 4); 0 restores
     the rule.  No bit of the result depends on it."""
     call("stein_debug_predict_ranks_weighted_bits", int(bits))
+
+
+def predict_ycdf_workspace_bytes(n, batch, n_pts):
+    """Workspace bytes of a stein_predict_*_ycdf call: the weight pass's header and n_pts floats per (slice, row), independent
+    of d.  Host arithmetic."""
+    total = _sz(0)
+    call("stein_predict_ycdf_workspace_bytes", n, batch, n_pts, ctypes.byref(total))
+    return int(total.value)
+
+
+def predict_yquantiles_workspace_bytes(n, batch, n_levels):
+    """Workspace bytes of a stein_predict_*_yquantiles call: the weight pass's header, two floats per (row, level) and
+    7 n_levels floats per (slice, row), independent of d.  Host arithmetic."""
+    total = _sz(0)
+    call("stein_predict_yquantiles_workspace_bytes", n, batch, n_levels, ctypes.byref(total))
+    return int(total.value)
 
 
 def version():

@@ -33,7 +33,6 @@
 // The forward passes themselves (pred_glm_slice, pred_bnn_pass), the plan and the argument checks are stein_predict_fwd.h's:
 // the rank-counting kernels of stein_predict_ranks.hip run the same ones.
 #include "stein_predict_fwd.h"
-#include <cfloat>
 
 // of the particles seen so far (their count is the caller's loop index): the slice's first output as a shift, mean and M2 of
 // the outputs minus that shift (a common offset of the outputs then costs no digits), running max and sum exp(l - max)
@@ -94,17 +93,6 @@ __device__ __forceinline__ void pred_accumulate_weighted(PredState& st, float& w
       }
     }
   }
-}
-
-// The header of a weighted call's workspace, in doubles: W (NaN: bad weights), sum w^2, then per slice W_s (0 after
-// k_predict_wtotal when none of the slice's weights survives the rounding to fp32), sum w^2 and max w.  The states follow.
-constexpr int PW_HEAD = 2;
-__host__ __device__ constexpr size_t pw_doubles(int64_t slices) { return (size_t)(PW_HEAD + 3 * slices); }
-
-// fl32(w / W) as the lanes hold it: below the normal range it counts as zero (whatever the denormal mode); W = NaN gives 0
-__device__ __forceinline__ float pred_norm_weight(double w, double W) {
-  const float q = (float)(w / W);
-  return q >= FLT_MIN ? q : 0.f;
 }
 
 __device__ __forceinline__ void pred_store_state(const PredState& st, float* __restrict__ part, int slice, int B, int row,
@@ -429,8 +417,9 @@ static float* predict_states(const PredPlan& pl, void* workspace, const PredWeig
   return pw.on ? (float*)((double*)workspace + pw_doubles(pl.slices)) : (float*)workspace;
 }
 
-// the weight pass, queued ahead of the forward kernel of a weighted call that asks for any summary
-static int predict_weight_pass(const PredPlan& pl, int64_t n, const PredWeights& pw, void* workspace, hipStream_t s) {
+// the weight pass, queued ahead of the forward kernel of a weighted call that asks for any summary (declared in
+// stein_predict_fwd.h: the calls of stein_predict_y.hip queue it too)
+int predict_weight_pass(const PredPlan& pl, int64_t n, const PredWeights& pw, void* workspace, hipStream_t s) {
   hipLaunchKernelGGL(k_predict_wsum, dim3((unsigned)pl.slices), dim3(256), 0, s, pw.w, (int)n, pl.per, pl.slices, (double*)workspace);
   LAUNCH_CHECK("k_predict_wsum");
   hipLaunchKernelGGL(k_predict_wtotal, dim3(1), dim3(256), 0, s, pl.slices, (double*)workspace, pw.ess);

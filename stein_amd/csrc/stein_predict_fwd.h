@@ -5,6 +5,7 @@
 // kernels take them (predict_cols).  The models, the outputs and the mapping are described at the head of stein_predict.hip.
 #pragma once
 #include "stein_common.h"
+#include <cfloat>
 
 constexpr int PR_ROWS = 256;         // rows of X per workgroup: one per lane
 constexpr int PR_PASS = 16;          // particles per pass: their outputs are 16 registers of every lane
@@ -143,6 +144,18 @@ __device__ __forceinline__ void pred_bnn_pass(float (&z)[PR_PASS], const float* 
   }
 }
 
+// ---- the weights of a weighted call as the lanes and the workspace hold them ---------------------------------------------------
+// The header of a weighted call's workspace, in doubles: W (NaN: bad weights), sum w^2, then per slice W_s (0 after
+// k_predict_wtotal when none of the slice's weights survives the rounding to fp32), sum w^2 and max w.  The states follow.
+constexpr int PW_HEAD = 2;
+__host__ __device__ constexpr size_t pw_doubles(int64_t slices) { return (size_t)(PW_HEAD + 3 * slices); }
+
+// fl32(w / W) as the lanes hold it: below the normal range it counts as zero (whatever the denormal mode); W = NaN gives 0
+__device__ __forceinline__ float pred_norm_weight(double w, double W) {
+  const float q = (float)(w / W);
+  return q >= FLT_MIN ? q : 0.f;
+}
+
 // ---- host side: the plan of a call's grid and the checks of the entry points -----------------------------------------------
 struct PredPlan { int row_tiles, slices, per; };
 
@@ -170,6 +183,10 @@ static PredGlmTile predict_glm_tile(int64_t n_feats, bool extra_row) {
 
 // the weights of a weighted call (on = false: an unweighted call, for which every check and launch is what it was)
 struct PredWeights { bool on; const double* w; double* ess; };
+
+// the weight pass of a weighted call (stein_predict.hip): W, sum w^2 and the per-slice sums of pl's slices into the header at
+// the start of `workspace`, and ess when pw.ess is set; queued ahead of the forward kernel that reads the header
+int predict_weight_pass(const PredPlan& pl, int64_t n, const PredWeights& pw, void* workspace, hipStream_t s);
 
 // the checks the entry points share, in the order the header lists them
 static int predict_check(const float* theta, const float* X, const float* y, int64_t n, int64_t d, int64_t batch,

@@ -17,7 +17,11 @@ hand-written HIP kernels (csrc/stein_predict.hip) in two forms:
   without [n, batch] (``posterior_predictive(..., quantiles=(0.05, 0.5, 0.95))``);
 * ``producer.weighted_quantiles(theta_matrix, feed, weights, q)`` -> [len(q), batch]: the band under importance weights or
   of a thinned multiset (counts), by the inverted weighted distribution function -- an element of the ensemble, not
-  interpolated (``sampler.predictive_quantiles(producer, feed, q, weights=w)``).
+  interpolated (``sampler.predictive_quantiles(producer, feed, q, weights=w)``);
+* ``producer.y_cdf(theta_matrix, feed, t)`` / ``producer.y_quantiles(theta_matrix, feed, q)``: the predictive distribution of
+  y itself, observation noise included -- the Gaussian mixture over the particles, evaluated at points (``t=None``: at
+  ``feed["y"]``, the probability integral transform) and inverted at levels (predictive intervals), with or without weights
+  (csrc/stein_predict_y.hip; ``sampler.predictive_cdf`` / ``sampler.predictive_interval``).  Regression models only.
 """
 import ctypes
 import math
@@ -48,6 +52,7 @@ class _Predict:
         self._rws = None              # the workspace of order_statistics: 76 bytes per (row, rank of one call)
         self._masses = self._mass_info = None   # weighted_quantiles: the particles' integer masses and their total
         self._mws = self._wrws = None           # ... the workspaces of the masses pass and of the weighted select
+        self._ycws = self._yqws = None          # the workspaces of y_cdf and y_quantiles
 
     def _buffer(self, name, need, device, dtype=torch.uint8):
         """the cached buffer self.<name>, regrown when it is missing, on another device or too small"""
@@ -227,6 +232,68 @@ class _Predict:
                                 out[at:at + len(part)], ws)
         return out
 
+    def _check_y_model(self):
+        """y_cdf / y_quantiles: the models with a Gaussian y (GlmPredict overrides this for the logistic kind)"""
+
+    def y_cdf(self, theta, feed, t=None, weights=None):
+        """-> F_b(t) = sum_p w_p Phi((t - z_pb) sqrt(tau_p)) / W, the predictive distribution function of y_b -- the mixture
+        over the particles of the model's Gaussian likelihood, tau the noise precision (``noise_precision`` for the linear
+        model, each particle's exp(log_gamma) for the network).  `t`: a float32 device tensor of [n_pts, batch] or [batch],
+        any n_pts (eight go into one call of the library) -> float32 [n_pts, batch]; ``t=None`` takes ``feed["y"]`` and
+        returns [batch], the probability integral transform of the rows: uniform on (0, 1) for a calibrated model.
+        `weights`: None (every particle counts alike) or [n] as for ``weighted_summary``; never read on the host, bad
+        weights give NaN rows.  No [n, batch] matrix."""
+        self._check_y_model()
+        pit = t is None
+        X, y, batch = self._inputs(theta, feed, pit)
+        if pit:
+            t = y.reshape(1, batch)
+        else:
+            _device_f32("t", t)
+            if t.dim() == 1:
+                t = t.reshape(1, -1)
+            if t.dim() != 2 or t.shape[1] != batch or t.shape[0] < 1:
+                raise ValueError("t must be [n_pts, %d] or [%d]" % (batch, batch))
+        n, dev = theta.shape[0], theta.device
+        w = None if weights is None else self._weights(weights, n, dev)
+        n_pts = t.shape[0]
+        out = torch.empty(n_pts, batch, dtype=torch.float32, device=dev)
+        ws = self._buffer("_ycws", _lib.predict_ycdf_workspace_bytes(n, batch, min(n_pts, _lib.PRED_Y_POINTS_MAX)), dev)
+        for at in range(0, n_pts, _lib.PRED_Y_POINTS_MAX):
+            m = min(_lib.PRED_Y_POINTS_MAX, n_pts - at)
+            self._launch_ycdf(theta, X, batch, t[at:at + m], m, w, out[at:at + m], ws)
+        return out[0] if pit else out
+
+    def y_quantiles(self, theta, feed, q, weights=None, passes=8, return_bracket=False):
+        """-> [len(q), batch] float32 device tensor: the q-quantiles of the predictive distribution of y per test point --
+        ``y_quantiles(theta, feed, (0.05, 0.95))`` is the 90 % predictive interval, noise included.  q strictly inside
+        (0, 1).  A bracketed search on the device: one pass brackets every quantile between the least and the largest
+        component quantile, then `passes` (1 .. 12) passes cut each bracket to an eighth; 8 reach neighbouring floats.  The
+        result is the bracket's upper end; ``return_bracket=True`` -> (lower ends, upper ends): the distribution function as
+        the device evaluates it is below q at the lower end and at least q at the upper.  `weights` as for ``y_cdf``.  Eight
+        levels go into one call of the library, more are split.  No [n, batch] matrix."""
+        self._check_y_model()
+        X, _, batch = self._inputs(theta, feed, False)
+        q = [float(v) for v in q]
+        if not q:
+            raise ValueError("q must not be empty")
+        for v in q:
+            if not 0.0 < v < 1.0:         # NaN too
+                raise ValueError("quantiles of y must lie strictly inside (0, 1), not %r" % v)
+        passes = int(passes)
+        if not 1 <= passes <= _lib.PRED_Y_PASSES_MAX:
+            raise ValueError("passes must lie in [1, %d]" % _lib.PRED_Y_PASSES_MAX)
+        n, dev = theta.shape[0], theta.device
+        w = None if weights is None else self._weights(weights, n, dev)
+        hi = torch.empty(len(q), batch, dtype=torch.float32, device=dev)
+        lo = torch.empty_like(hi) if return_bracket else None
+        ws = self._buffer("_yqws", _lib.predict_yquantiles_workspace_bytes(n, batch, min(len(q), _lib.PRED_RANKS_MAX)), dev)
+        for at in range(0, len(q), _lib.PRED_RANKS_MAX):
+            part = q[at:at + _lib.PRED_RANKS_MAX]
+            self._launch_yquantiles(theta, X, batch, (ctypes.c_double * len(part))(*part), len(part), passes, w,
+                                    hi[at:at + len(part)], None if lo is None else lo[at:at + len(part)], ws)
+        return (lo, hi) if return_bracket else hi
+
     @staticmethod
     def _ptr(t):
         return None if t is None else t.data_ptr()
@@ -271,6 +338,24 @@ class GlmPredict(_Predict):
                      self.w_col, self.n_feats, X.data_ptr(), batch, masses.data_ptr(), levels, n_levels, out.data_ptr(),
                      ws.data_ptr(), ws.numel(), torch.cuda.current_stream(theta.device).cuda_stream)
 
+    def _check_y_model(self):
+        if self.kind != _lib.GLM_LINEAR:
+            raise ValueError("y of the logistic model is Bernoulli, not Gaussian: its predictive probability is the mean of "
+                             "the outputs of GlmPredict(..., output=\"mean\")")
+
+    def _launch_ycdf(self, theta, X, batch, t, n_pts, weights, out, ws):
+        n, d = theta.shape
+        _lib.call_on(theta.device, "stein_predict_glm_ycdf", theta.data_ptr(), n, d, self.kind, self.w_col, self.n_feats,
+                     X.data_ptr(), batch, self.noise_precision, t.data_ptr(), n_pts, self._ptr(weights), out.data_ptr(),
+                     ws.data_ptr(), ws.numel(), torch.cuda.current_stream(theta.device).cuda_stream)
+
+    def _launch_yquantiles(self, theta, X, batch, levels, n_levels, passes, weights, out, out_lo, ws):
+        n, d = theta.shape
+        _lib.call_on(theta.device, "stein_predict_glm_yquantiles", theta.data_ptr(), n, d, self.kind, self.w_col,
+                     self.n_feats, X.data_ptr(), batch, self.noise_precision, levels, n_levels, passes, self._ptr(weights),
+                     out.data_ptr(), self._ptr(out_lo), ws.data_ptr(), ws.numel(),
+                     torch.cuda.current_stream(theta.device).cuda_stream)
+
 
 class BnnPredict(_Predict):
     """Outputs of the one-hidden-layer network of BnnScore: relu(X w1 + b1) w2 + b2 per particle.
@@ -302,3 +387,15 @@ class BnnPredict(_Predict):
         _lib.call_on(theta.device, "stein_predict_bnn_ranks_weighted", theta.data_ptr(), n, d, self.n_in, self.n_hidden,
                      self._cols, self.output, X.data_ptr(), batch, masses.data_ptr(), levels, n_levels, out.data_ptr(),
                      ws.data_ptr(), ws.numel(), torch.cuda.current_stream(theta.device).cuda_stream)
+
+    def _launch_ycdf(self, theta, X, batch, t, n_pts, weights, out, ws):
+        n, d = theta.shape
+        _lib.call_on(theta.device, "stein_predict_bnn_ycdf", theta.data_ptr(), n, d, self.n_in, self.n_hidden, self._cols,
+                     X.data_ptr(), batch, t.data_ptr(), n_pts, self._ptr(weights), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                     torch.cuda.current_stream(theta.device).cuda_stream)
+
+    def _launch_yquantiles(self, theta, X, batch, levels, n_levels, passes, weights, out, out_lo, ws):
+        n, d = theta.shape
+        _lib.call_on(theta.device, "stein_predict_bnn_yquantiles", theta.data_ptr(), n, d, self.n_in, self.n_hidden,
+                     self._cols, X.data_ptr(), batch, levels, n_levels, passes, self._ptr(weights), out.data_ptr(),
+                     self._ptr(out_lo), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(theta.device).cuda_stream)

@@ -365,6 +365,38 @@ class AbstractSteinSampler:
                 band = producer.weighted_quantiles(self._matrix_f32(), feed, weights, q)
         return band.cpu().numpy()
 
+    def predictive_cdf(self, producer, feed, t=None, weights=None):
+        """-> NumPy: the predictive distribution function of y, observation noise included, over the current particles --
+        ``producer.y_cdf``.  t=None: at ``feed["y"]`` -> [batch], the probability integral transform of the rows (its
+        histogram is flat for a calibrated sampler); t [n_pts, batch] (NumPy or a tensor) -> [n_pts, batch].  weights ([n]:
+        ``importance_weights(...)``, or the integer counts ``torch.bincount(thin(m), minlength=n)``, taken as they are): the
+        mixture under these weights.  Regression models only; one rank only.  Bad weights give NaN."""
+        if self._group is not None:
+            raise ValueError("predictive_cdf works on one rank only: a sharded sampler would have to merge the ranks' "
+                             "sums; use function_posterior, which gathers the outputs")
+        if not hasattr(producer, "y_cdf"):
+            raise ValueError("predictive_cdf needs a predictive producer (GlmPredict / BnnPredict)")
+        with torch.no_grad():
+            if t is not None:
+                t = torch.as_tensor(t).to(device=self.device, dtype=torch.float32).contiguous()
+            out = producer.y_cdf(self._matrix_f32(), feed, t, weights=weights)
+        return out.cpu().numpy()
+
+    def predictive_interval(self, producer, feed, q, weights=None, passes=8):
+        """-> NumPy [len(q), batch]: the q-quantiles of the predictive distribution of y per test point, observation noise
+        included -- ``predictive_interval(producer, feed, (0.05, 0.95))`` is the 90 % interval that should hold 90 % of
+        held-out observations, which the credible band of ``predictive_quantiles`` (the spread of the model outputs alone)
+        does not.  ``producer.y_quantiles``: q strictly inside (0, 1), `passes` bracket refinements (8 reach neighbouring
+        floats); weights as for ``predictive_cdf``.  Regression models only; one rank only."""
+        if self._group is not None:
+            raise ValueError("predictive_interval works on one rank only: a sharded sampler would have to merge the ranks' "
+                             "sums; use function_posterior, which gathers the outputs")
+        if not hasattr(producer, "y_quantiles"):
+            raise ValueError("predictive_interval needs a predictive producer (GlmPredict / BnnPredict)")
+        with torch.no_grad():
+            band = producer.y_quantiles(self._matrix_f32(), feed, q, weights=weights, passes=passes)
+        return band.cpu().numpy()
+
     def samples_all(self):
         """All n particles as one float64 [n, d] NumPy array on every rank (the reference's `samples`, stein_sampler.py:73-78,
         for a sharded sampler; on one rank it equals `samples`).  Collective when sharded."""
