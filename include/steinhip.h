@@ -677,6 +677,16 @@ int stein_score_bnn(const float* theta, int64_t n, int64_t d, int64_t n_in, int6
                     const float* X, const float* y, int64_t batch, double n_train, double gamma_a, double gamma_b,
                     float* score, void* stream);
 
+/* The same network with up to 128 input features (tabular regression sets: 6 .. 90 inputs): the arguments, the model, the
+ * formulas and the output conventions of stein_score_bnn.  Domain: 1 <= n_in <= 128, n_hidden <= 1024 and
+ * n_in * n_hidden <= 16384 (a particle's first layer and its gradient, 64 KB each, lie in one workgroup's LDS);
+ * STEIN_E_UNSUPPORTED beyond, with a message that names the limit.  The other checks are stein_score_bnn's, in its order.
+ * For n_in <= 4 the call runs stein_score_bnn itself: bit-identical.  No workspace, no atomics: a repeated call is
+ * bit-identical, and the row of a particle depends on nothing but the particle (not on n, the grid or the other particles). */
+int stein_score_bnn_wide(const float* theta, int64_t n, int64_t d, int64_t n_in, int64_t n_hidden, const int64_t* cols,
+                         const float* X, const float* y, int64_t batch, double n_train, double gamma_a, double gamma_b,
+                         float* score, void* stream);
+
 /* ---- posterior predictive producers (the step after the update) --------------------
  * The forward pass of the same three models for every particle: what the reference's examples hand to function_posterior
  * (stein/samplers/abstract_stein_sampler.py:157-168) and then average.  One call gives any non-empty subset of
@@ -733,6 +743,21 @@ int stein_predict_bnn_weighted(const float* theta, int64_t n, int64_t d, int64_t
                                const int64_t* cols, int output, const float* X, const float* y, int64_t batch,
                                const double* weights, float* pred, float* mean, float* var, float* lpd, double* ess,
                                void* workspace, size_t ws_bytes, void* stream);
+
+/* The network with up to 128 input features: stein_predict_bnn / stein_predict_bnn_weighted with the domain of
+ * stein_score_bnn_wide (1 <= n_in <= 128, n_hidden <= 1024, n_in * n_hidden <= 16384; STEIN_E_UNSUPPORTED beyond, naming the
+ * limit).  Arguments, outputs, checks and their order, workspace (stein_predict_workspace_bytes /
+ * stein_predict_weighted_workspace_bytes, unchanged), determinism and the conventions of the weights are the narrow calls'.
+ * For n_in <= 4 the calls run the narrow calls themselves: bit-identical.  pred[p][b] depends on the particle and the row
+ * alone (not on n, the slicing or the other rows), and mean, var and lpd are summaries of exactly the values pred holds.
+ * Not built for n_in > 4: the order statistics and the y calls below. */
+int stein_predict_bnn_wide(const float* theta, int64_t n, int64_t d, int64_t n_in, int64_t n_hidden, const int64_t* cols,
+                           int output, const float* X, const float* y, int64_t batch,
+                           float* pred, float* mean, float* var, float* lpd, void* workspace, size_t ws_bytes, void* stream);
+int stein_predict_bnn_wide_weighted(const float* theta, int64_t n, int64_t d, int64_t n_in, int64_t n_hidden,
+                                    const int64_t* cols, int output, const float* X, const float* y, int64_t batch,
+                                    const double* weights, float* pred, float* mean, float* var, float* lpd, double* ess,
+                                    void* workspace, size_t ws_bytes, void* stream);
 
 /* Order statistics of the outputs: credible bands and the ensemble median per test point, without pred.
  *   out [n_ranks][batch]   out[i][b] = the ranks[i]-th smallest (0-based) of the n values f_pb, p = 0 .. n-1

@@ -66,6 +66,7 @@ _SIGNATURES = {
     "stein_spec_update": [_vp, _vp],
     "stein_score_glm": [_vp, _i64, _i64, _int, _i64, _i64, _i64, _vp, _vp, _i64, _dbl, _dbl, _dbl, _vp, _vp],
     "stein_score_bnn": [_vp, _i64, _i64, _i64, _i64, _c.POINTER(_i64), _vp, _vp, _i64, _dbl, _dbl, _dbl, _vp, _vp],
+    "stein_score_bnn_wide": [_vp, _i64, _i64, _i64, _i64, _c.POINTER(_i64), _vp, _vp, _i64, _dbl, _dbl, _dbl, _vp, _vp],
     "stein_predict_workspace_bytes": [_i64, _i64, _c.POINTER(_sz)],
     "stein_predict_glm": [_vp, _i64, _i64, _int, _int, _i64, _i64, _vp, _vp, _i64, _dbl, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "stein_predict_bnn": [_vp, _i64, _i64, _i64, _i64, _c.POINTER(_i64), _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
@@ -74,6 +75,10 @@ _SIGNATURES = {
                                    _vp, _sz, _vp],
     "stein_predict_bnn_weighted": [_vp, _i64, _i64, _i64, _i64, _c.POINTER(_i64), _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _sz, _vp],
+    "stein_predict_bnn_wide": [_vp, _i64, _i64, _i64, _i64, _c.POINTER(_i64), _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz,
+                               _vp],
+    "stein_predict_bnn_wide_weighted": [_vp, _i64, _i64, _i64, _i64, _c.POINTER(_i64), _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
+                                        _vp, _vp, _vp, _sz, _vp],
     "stein_predict_ranks_workspace_bytes": [_i64, _i64, _i64, _c.POINTER(_sz)],
     "stein_predict_glm_ranks": [_vp, _i64, _i64, _int, _int, _i64, _i64, _vp, _i64, _c.POINTER(_i64), _i64, _vp, _vp, _sz, _vp],
     "stein_predict_bnn_ranks": [_vp, _i64, _i64, _i64, _i64, _c.POINTER(_i64), _int, _vp, _i64, _c.POINTER(_i64), _i64, _vp, _vp,

@@ -199,6 +199,57 @@ __global__ __launch_bounds__(256) void k_predict_bnn(const float* __restrict__ t
   if (live && part) pred_store_state(st, part, blockIdx.y, B, row, want_mv, want_lpd);
 }
 
+// More than PR_NIN_MAX input features (stein_predict_bnn_wide): the same mapping with the row's inputs in LDS
+// (pred_bnn_wide_pass); xs [PR_ROWS][ld] is staged once for the slice, rows past the batch as zeros, lw behind it.
+template <bool WEIGHTED>
+__global__ __launch_bounds__(256) void k_predict_bnn_wide(const float* __restrict__ theta, int n, int d, int NIN, int H,
+                                                          PredCols c, const float* __restrict__ X, const float* __restrict__ y,
+                                                          int B, int per, int ld, int ps, int hc, float* __restrict__ pred,
+                                                          float* __restrict__ part, int want_mv, int want_lpd,
+                                                          const double* __restrict__ wts, const double* __restrict__ head) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* xs = lds;                 // [PR_ROWS][ld]
+  float* lw = lds + PR_ROWS * ld;  // [ps][NIN + 2][hc]
+  __shared__ float lp[PR_PASS][4];
+  float wk = 0.f;
+  const double wtot = WEIGHTED ? head[0] : 0.0;
+  const int t = threadIdx.x;
+  const int row0 = blockIdx.x * PR_ROWS, row = row0 + t;
+  const bool live = row < B;
+  const int p_begin = blockIdx.y * per, p_end = min(n, p_begin + per);
+  for (int i = t; i < PR_ROWS * NIN; i += 256) {
+    const int r = i / NIN, f = i - r * NIN;
+    xs[r * ld + f] = row0 + r < B ? X[(size_t)(row0 + r) * NIN + f] : 0.f;
+  }
+  const float* xr = xs + t * ld;
+  const float yb = (want_lpd && live) ? y[row] : 0.f;
+  PredState st = {0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int p0 = p_begin; p0 < p_end; p0 += PR_PASS) {
+    const int cnt = min(PR_PASS, p_end - p0);
+    float z[PR_PASS];
+#pragma unroll
+    for (int k = 0; k < PR_PASS; ++k) z[k] = 0.f;
+    pred_bnn_wide_pass(z, theta, d, NIN, H, c, xr, p0, cnt, ps, hc, lw, lp, t, [&](int k) {
+      if (WEIGHTED) lp[k][3] = pred_norm_weight(wts[p0 + k], wtot);
+    });
+#pragma unroll
+    for (int k = 0; k < PR_PASS; ++k) {
+      if (k < cnt) {
+        const float f = z[k] + lp[k][0];
+        if (pred && live) pred[(size_t)(p0 + k) * B + row] = f;
+        float l = 0.f;
+        if (want_lpd) {
+          const float r = yb - f;
+          l = fmaf(-lp[k][2], r * r, lp[k][1]);
+        }
+        if constexpr (WEIGHTED) pred_accumulate_weighted(st, wk, lp[k][3], f, l, want_mv, want_lpd);
+        else pred_accumulate(st, p0 - p_begin + k, f, l, want_mv, want_lpd);
+      }
+    }
+  }
+  if (live && part) pred_store_state(st, part, blockIdx.y, B, row, want_mv, want_lpd);
+}
+
 // The slices' states merged in slice order, in fp64.  A workgroup takes PF_ROWS rows; its PF_GROUPS thread groups each merge
 // a contiguous range of the slices in order, then one thread per row merges the groups in order: a fixed tree, so the
 // result depends on nothing but the states.  (One thread walking all the slices of a row took longer than the forward
@@ -499,6 +550,69 @@ static int predict_bnn(const float* theta, int64_t n, int64_t d, int64_t n_in, i
 #undef PR_LAUNCH_BNN_AS
   LAUNCH_CHECK("k_predict_bnn");
   return summary ? predict_finish(pl, n, batch, part, mean, var, lpd, head, s) : STEIN_OK;
+}
+
+// the wide kernels take up to 160 KB of dynamic LDS: raise each one's limit once per device
+static int predict_wide_attr(const void* fn, int slot) {
+  static bool attr_set[2][64] = {{false}};
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64 || !attr_set[slot][dev]) {
+    HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, PR_WIDE_LDS * (int)sizeof(float)));
+    if (dev >= 0 && dev < 64) attr_set[slot][dev] = true;
+  }
+  return STEIN_OK;
+}
+
+// stein_predict_bnn_wide / _weighted: up to PR_NIN_MAX features the narrow entry points' own code; past them the same
+// checks in the same order with the wide domain, the same plan, workspace, weight pass and finish, and k_predict_bnn_wide
+static int predict_bnn_wide(const float* theta, int64_t n, int64_t d, int64_t n_in, int64_t n_hidden, const int64_t* cols,
+                            int output, const float* X, const float* y, int64_t batch, float* pred, float* mean, float* var,
+                            float* lpd, void* workspace, size_t ws_bytes, void* stream, const PredWeights& pw) {
+  if (n_in >= 1 && n_in <= PR_NIN_MAX)
+    return predict_bnn(theta, n, d, n_in, n_hidden, cols, output, X, y, batch, pred, mean, var, lpd, workspace, ws_bytes, stream, pw);
+  if (!cols) return stein_fail(STEIN_E_BADARG, "NULL pointer");
+  if (int rc = predict_check(theta, X, y, n, d, batch, n_hidden, output, pred, mean, var, lpd, pw)) return rc;
+  if (int rc = predict_check_bnn_wide(n_in, n_hidden, cols, d)) return rc;
+  const bool summary = mean || var || lpd;
+  if (int rc = predict_check_ws(n, batch, summary || pw.ess, workspace, ws_bytes, pw)) return rc;
+  const PredPlan pl = predict_plan(n, batch);
+  const PredCols c = predict_cols(cols);
+  hipStream_t s = (hipStream_t)stream;
+  if (pw.on && (summary || pw.ess))
+    if (int rc = predict_weight_pass(pl, n, pw, workspace, s)) return rc;
+  if (!pred && !summary) return STEIN_OK;   // ess alone
+  float* part = summary ? predict_states(pl, workspace, pw) : nullptr;
+  const double* head = (pw.on && summary) ? (const double*)workspace : nullptr;
+  const PredWideTile w = predict_wide_tile(n_in);
+#define PR_LAUNCH_WIDE(WEIGHTED, SLOT)                                                                                   \
+  do {                                                                                                                   \
+    if (int rc = predict_wide_attr(reinterpret_cast<const void*>(k_predict_bnn_wide<WEIGHTED>), SLOT)) return rc;        \
+    hipLaunchKernelGGL(k_predict_bnn_wide<WEIGHTED>, dim3((unsigned)pl.row_tiles, (unsigned)pl.slices), dim3(256),        \
+                       w.bytes, s, theta, (int)n, (int)d, (int)n_in, (int)n_hidden, c, X, y, (int)batch, pl.per, w.ld,    \
+                       w.ps, w.hc, pred, part, (mean || var) ? 1 : 0, lpd ? 1 : 0, pw.w, head);                           \
+  } while (0)
+  if (head) PR_LAUNCH_WIDE(true, 1);
+  else PR_LAUNCH_WIDE(false, 0);
+#undef PR_LAUNCH_WIDE
+  LAUNCH_CHECK("k_predict_bnn_wide");
+  return summary ? predict_finish(pl, n, batch, part, mean, var, lpd, head, s) : STEIN_OK;
+}
+
+extern "C" int stein_predict_bnn_wide(const float* theta, int64_t n, int64_t d, int64_t n_in, int64_t n_hidden,
+                                      const int64_t* cols /*[6]: w1, b1, w2, b2, log_lambda, log_gamma*/, int output,
+                                      const float* X, const float* y, int64_t batch, float* pred, float* mean, float* var,
+                                      float* lpd, void* workspace, size_t ws_bytes, void* stream) {
+  return predict_bnn_wide(theta, n, d, n_in, n_hidden, cols, output, X, y, batch, pred, mean, var, lpd, workspace, ws_bytes,
+                          stream, PredWeights{false, nullptr, nullptr});
+}
+
+extern "C" int stein_predict_bnn_wide_weighted(const float* theta, int64_t n, int64_t d, int64_t n_in, int64_t n_hidden,
+                                               const int64_t* cols, int output, const float* X, const float* y, int64_t batch,
+                                               const double* weights, float* pred, float* mean, float* var, float* lpd,
+                                               double* ess, void* workspace, size_t ws_bytes, void* stream) {
+  return predict_bnn_wide(theta, n, d, n_in, n_hidden, cols, output, X, y, batch, pred, mean, var, lpd, workspace, ws_bytes,
+                          stream, PredWeights{true, weights, ess});
 }
 
 extern "C" int stein_predict_glm(const float* theta, int64_t n, int64_t d, int kind, int output, int64_t w_col,

@@ -144,6 +144,86 @@ __device__ __forceinline__ void pred_bnn_pass(float (&z)[PR_PASS], const float* 
   }
 }
 
+// Network with more than PR_NIN_MAX input features (up to PR_WIDE_NIN_MAX): the lane's inputs no longer fit its registers, so
+// the workgroup's X tile lies in LDS ([PR_ROWS][ld], ld odd; xr = the lane's row) and a particle's hidden units are taken
+// PR_WT at a time: PR_WT accumulators start at b1, the features stream through them in ascending order (one own-row read of x
+// and four 16-byte broadcasts of w1 per 16 FMAs), and relu(.) . w2 of the tile is summed in one fixed order.  Staging unit: ps
+// particles x hc hidden units (hc a multiple of PR_WT; predict_wide_tile: hc = PR_WT, ps shrinks with n_in); per particle
+// b1 [hc], w2 [hc], w1 [NIN][hc], hidden units past H staged as zeros.  (hc stays a run-time argument: with the unit fixed at
+// PR_WT at compile time and the tile loop gone the kernel came out slower -- 5.21 against 3.88 ms at 90 inputs x 100 hidden x
+// 1024 particles x 4000 rows, 2.66 against 2.49 ms at 13 x 50 x 16384 x 4000, profiles/bnn_wide_ab.txt B4; not looked into.)  z, lp and extra as in pred_bnn_pass.  What a particle's output is summed
+// from, and in which order, follows from (NIN, H) alone: not from its place in the pass, cnt, or the slicing.
+constexpr int PR_WT = 16;
+constexpr int PR_WIDE_NIN_MAX = 128;
+constexpr int PR_WIDE_W1_MAX = 16384;   // n_in * n_hidden at most
+constexpr int PR_WIDE_LDS = 160 * 1024 / 4 - 128;   // floats of dynamic LDS at most (lp and some slack stay free)
+
+template <class Extra>
+__device__ __forceinline__ void pred_bnn_wide_pass(float (&z)[PR_PASS], const float* theta, int d, int NIN, int H,
+                                                   const PredCols& c, const float* xr, int p0, int cnt, int ps, int hc,
+                                                   float* lw, float (*lp)[4], int t, Extra&& extra) {
+  const int pw = (NIN + 2) * hc;
+  for (int k0 = 0; k0 < cnt; k0 += ps) {
+    const int kn = min(ps, cnt - k0);
+    for (int h0 = 0; h0 < H; h0 += hc) {
+      const int len = min(hc, H - h0), len16 = (len + PR_WT - 1) & ~(PR_WT - 1);
+      __syncthreads();   // every lane is past its last read of lw and lp
+      for (int i = t; i < kn * len16; i += 256) {
+        const int kk = i / len16, h = i - kk * len16;
+        const bool ok = h < len;
+        const float* th = theta + (size_t)(p0 + k0 + kk) * d + h0 + (ok ? h : 0);
+        float* dst = lw + kk * pw + h;
+        dst[0] = ok ? th[c.b1] : 0.f;
+        dst[hc] = ok ? th[c.w2] : 0.f;
+        for (int f = 0; f < NIN; ++f) dst[(2 + f) * hc] = ok ? th[c.w1 + f * H] : 0.f;
+      }
+      if (k0 == 0 && h0 == 0 && t < cnt) {
+        const float* th = theta + (size_t)(p0 + t) * d;
+        const float lg = th[c.loggam];
+        lp[t][0] = th[c.b2];
+        lp[t][1] = fmaf(0.5f, lg, -PR_HALF_LOG_2PI);
+        lp[t][2] = 0.5f * expf(lg);
+        extra(t);
+      }
+      __syncthreads();
+      for (int kk = 0; kk < kn; ++kk) {
+        const float* wk = lw + kk * pw;
+        float sp = 0.f;
+        for (int j = 0; j < len16; j += PR_WT) {
+          float4 a[PR_WT / 4];
+#pragma unroll
+          for (int q = 0; q < PR_WT / 4; ++q) a[q] = *reinterpret_cast<const float4*>(wk + j + 4 * q);
+#pragma unroll 2
+          for (int f = 0; f < NIN; ++f) {
+            const float x = xr[f];
+            const float4* w4 = reinterpret_cast<const float4*>(wk + (2 + f) * hc + j);
+#pragma unroll
+            for (int q = 0; q < PR_WT / 4; ++q) {
+              const float4 w = w4[q];
+              a[q].x = fmaf(x, w.x, a[q].x);
+              a[q].y = fmaf(x, w.y, a[q].y);
+              a[q].z = fmaf(x, w.z, a[q].z);
+              a[q].w = fmaf(x, w.w, a[q].w);
+            }
+          }
+          float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+#pragma unroll
+          for (int q = 0; q < PR_WT / 4; ++q) {
+            const float4 w2 = *reinterpret_cast<const float4*>(wk + hc + j + 4 * q);
+            s0 = fmaf(fmaxf(a[q].x, 0.f), w2.x, s0);
+            s1 = fmaf(fmaxf(a[q].y, 0.f), w2.y, s1);
+            s2 = fmaf(fmaxf(a[q].z, 0.f), w2.z, s2);
+            s3 = fmaf(fmaxf(a[q].w, 0.f), w2.w, s3);
+          }
+          sp += (s0 + s1) + (s2 + s3);
+        }
+#pragma unroll
+        for (int q = 0; q < PR_PASS; ++q) z[q] = q == k0 + kk ? z[q] + sp : z[q];   // (z stays in registers: no dynamic index)
+      }
+    }
+  }
+}
+
 // ---- the weights of a weighted call as the lanes and the workspace hold them ---------------------------------------------------
 // The header of a weighted call's workspace, in doubles: W (NaN: bad weights), sum w^2, then per slice W_s (0 after
 // k_predict_wtotal when none of the slice's weights survives the rounding to fp32), sum w^2 and max w.  The states follow.
@@ -231,6 +311,34 @@ static int predict_check_bnn(int64_t n_in, int64_t n_hidden, const int64_t* cols
   if (n_in > PR_NIN_MAX) return stein_fail(STEIN_E_UNSUPPORTED, "more than %d input features", PR_NIN_MAX);
   if (n_hidden > PR_WIDTH_MAX) return stein_fail(STEIN_E_UNSUPPORTED, "more than 1024 hidden units");
   return predict_check_cols(cols, n_in, n_hidden, d);
+}
+
+// the wide network entry points' own checks (n_in > PR_NIN_MAX), in the place of predict_check_bnn
+static int predict_check_bnn_wide(int64_t n_in, int64_t n_hidden, const int64_t* cols, int64_t d) {
+  if (n_in < 1) return stein_fail(STEIN_E_SHAPE, "bad shape n_in=%lld", (long long)n_in);
+  if (n_in > PR_WIDE_NIN_MAX) return stein_fail(STEIN_E_UNSUPPORTED, "more than %d input features", PR_WIDE_NIN_MAX);
+  if (n_hidden > PR_WIDTH_MAX) return stein_fail(STEIN_E_UNSUPPORTED, "more than 1024 hidden units");
+  if (n_in * n_hidden > PR_WIDE_W1_MAX)
+    return stein_fail(STEIN_E_UNSUPPORTED, "more than %d first-layer weights (n_in * n_hidden)", PR_WIDE_W1_MAX);
+  return predict_check_cols(cols, n_in, n_hidden, d);
+}
+
+// the wide network kernels' LDS: the X tile [PR_ROWS][ld] and behind it the staging unit of ps particles x hc hidden units:
+// one tile of PR_WT hidden units of as many of a pass's PR_PASS particles as the LDS holds beside the X tile -- all of them up
+// to n_in = 78, 11 at 90, 3 at 128 (where the X tile alone is 129 KB).  Measured (profiles/bnn_wide_ab.txt): more hidden units
+// per unit cost resident workgroups at 13 inputs (16 | 32 | 64 units: 2.33 | 2.65 | 2.99 ms), fewer particles cost barriers at
+// 90 (2 | 5 | 11 particles: 6.37 | 4.67 | 3.86 ms).
+struct PredWideTile { int ld, ps, hc; size_t bytes; };
+
+static PredWideTile predict_wide_tile(int64_t n_in) {
+  PredWideTile w;
+  w.hc = PR_WT;
+  w.ld = (int)(n_in | 1);
+  const int xt = PR_ROWS * w.ld, unit = (int)(n_in + 2) * PR_WT;
+  w.ps = (PR_WIDE_LDS - xt) / unit;
+  if (w.ps > PR_PASS) w.ps = PR_PASS;
+  w.bytes = ((size_t)xt + (size_t)w.ps * unit) * sizeof(float);
+  return w;
 }
 
 // the network's columns as the kernels take them (log_lambda, cols[4], enters no output)

@@ -362,16 +362,50 @@ class BnnPredict(_Predict):
 
     cols: first column of (w1, b1, w2, b2, log_lambda, log_gamma) in the packed particle matrix, as for BnnScore
     (``BnnScore.columns(sampler._access)``).  output: "link" and "mean" are the same for this model.
+
+    More than NARROW_MAX = 4 input features (up to 128, n_in * n_hidden <= 16384) take the library's wide kernels
+    (stein_predict_bnn_wide): the outputs, ``summary`` and ``weighted_summary`` -- so ``function_posterior`` and
+    ``posterior_predictive(..., weights=)`` -- work as for a narrow network; ``quantiles``, ``order_statistics``,
+    ``weighted_quantiles``, ``y_cdf`` and ``y_quantiles`` are built for n_in <= 4 only and raise a ValueError.
     """
+    NARROW_MAX = 4
+
     def __init__(self, n_in, n_hidden, cols, output="link"):
         super().__init__(output, n_in)
         self.n_in, self.n_hidden = int(n_in), int(n_hidden)
         self._cols = (ctypes.c_int64 * 6)(*[int(c) for c in cols])
 
+    def _narrow_only(self, what):
+        if self.n_in > self.NARROW_MAX:
+            raise ValueError("%s is built for n_in <= %d only (this producer has n_in = %d): take the [n, batch] outputs "
+                             "through function_posterior and sort or integrate them there" % (what, self.NARROW_MAX, self.n_in))
+
+    def order_statistics(self, theta, feed, ranks):
+        self._narrow_only("order_statistics")
+        return super().order_statistics(theta, feed, ranks)
+
+    def quantiles(self, theta, feed, q, interpolation="linear"):
+        self._narrow_only("quantiles")
+        return super().quantiles(theta, feed, q, interpolation)
+
+    def weighted_quantiles(self, theta, feed, weights, q):
+        self._narrow_only("weighted_quantiles")
+        return super().weighted_quantiles(theta, feed, weights, q)
+
+    def y_cdf(self, theta, feed, t=None, weights=None):
+        self._narrow_only("y_cdf")
+        return super().y_cdf(theta, feed, t, weights)
+
+    def y_quantiles(self, theta, feed, q, weights=None, passes=8, return_bracket=False):
+        self._narrow_only("y_quantiles")
+        return super().y_quantiles(theta, feed, q, weights, passes, return_bracket)
+
     def _launch(self, theta, X, y, batch, pred, mean, var, lpd, ws, weights=None, ess=None):
         n, d = theta.shape
         name, w, e = ("stein_predict_bnn", (), ()) if weights is None else \
             ("stein_predict_bnn_weighted", (weights.data_ptr(),), (ess.data_ptr(),))
+        if self.n_in > self.NARROW_MAX:      # (up to four features the old names: no existing path changes)
+            name = name.replace("stein_predict_bnn", "stein_predict_bnn_wide")
         _lib.call_on(theta.device, name, theta.data_ptr(), n, d, self.n_in, self.n_hidden, self._cols, self.output,
                      X.data_ptr(), self._ptr(y), batch, *w, self._ptr(pred), self._ptr(mean), self._ptr(var), self._ptr(lpd),
                      *e, self._ptr(ws), 0 if ws is None else ws.numel(), torch.cuda.current_stream(theta.device).cuda_stream)

@@ -58,6 +58,9 @@ class BnnScore:
 
     cols: first column of (w1, b1, w2, b2, log_lambda, log_gamma) in the packed particle matrix -- use
     ``BnnScore.columns(sampler)`` for a SteinSampler built with the variable names of the example.
+
+    Up to four input features run stein_score_bnn; 5 .. 128 (n_in * n_hidden <= 16384: the tabular regression sets) run
+    stein_score_bnn_wide, which keeps a particle's first layer and its gradient in LDS (csrc/stein_score_wide.hip).
     """
     wants_matrix = True
     NAMES = ("model/w_1:0", "model/b_1:0", "model/w_2:0", "model/b_2:0", "model/log_lambda:0", "model/log_gamma:0")
@@ -84,7 +87,8 @@ class BnnScore:
             raise ValueError("X must be [batch, %d] and y [batch]" % self.n_in)
         if out is None:
             out = torch.empty_like(theta)
-        _lib.call_on(theta.device, "stein_score_bnn", theta.data_ptr(), n, d, self.n_in, self.n_hidden, self._cols, X.data_ptr(),
+        name = "stein_score_bnn" if self.n_in <= 4 else "stein_score_bnn_wide"
+        _lib.call_on(theta.device, name, theta.data_ptr(), n, d, self.n_in, self.n_hidden, self._cols, X.data_ptr(),
                   y.data_ptr(), batch, self.n_train, self.gamma_a, self.gamma_b, out.data_ptr(),
                   torch.cuda.current_stream(theta.device).cuda_stream)
         return out
