@@ -687,6 +687,31 @@ int stein_score_bnn_wide(const float* theta, int64_t n, int64_t d, int64_t n_in,
                          const float* X, const float* y, int64_t batch, double n_train, double gamma_a, double gamma_b,
                          float* score, void* stream);
 
+/* Softmax (multi-class logistic) regression: the first model beyond the reference's three examples.
+ *   theta [n][d] float   particle i holds W [n_feats][n_classes] row-major at w_col (W_fc at column w_col + f * n_classes + c:
+ *                        how a [F, C] variable flattens) and, when alpha_col >= 0, log(alpha) at alpha_col; any other column
+ *                        gets score 0.  No bias term: append a column of ones to X.
+ *   X [batch][n_feats] float, labels [batch] int32 class indices (device; never read on the host)
+ *   z_bc = sum_f x_bf W_fc;  log p = scale * sum_b [z_{b,y_b} - logsumexp_c z_bc] + sum_fc log N(W_fc; 0, 1/alpha)
+ *          + log Gamma(alpha; 1, gamma_rate), the density at alpha = exp(theta[alpha_col]) without a Jacobian term, as
+ *          STEIN_GLM_LOGISTIC; alpha_col < 0: alpha = prior_precision
+ *   score [n][d] float   d/dW_fc = scale * sum_b x_bf (1[y_b = c] - p_bc) - alpha W_fc, p_b. = softmax(z_b.) evaluated with the
+ *                        row maximum subtracted;  d/dlog alpha = F C / 2 - alpha (sum_fc W_fc^2 / 2 + gamma_rate)
+ * Domain: 2 <= n_classes <= 32, 1 <= n_feats <= 1024, n_feats * n_classes <= 16384 (a particle's W and its gradient lie in
+ * one workgroup's LDS); STEIN_E_UNSUPPORTED beyond, with a message that names the limit.  NULL pointers: STEIN_E_BADARG;
+ * weights or the alpha column that do not fit d, or the alpha column inside the weights: STEIN_E_SHAPE (after the domain).
+ * A label outside [0, n_classes) is no error code: the call returns STEIN_OK and every weight entry of every particle is
+ * NaN (the convention of the weights of the weighted calls below).
+ * One launch, no workspace, no atomics: a repeated call is bit-identical, and the row of a particle depends on nothing but
+ * the particle (not on n, the grid or the other particles). */
+enum { STEIN_SOFTMAX_C_MIN = 2, STEIN_SOFTMAX_C_MAX = 32, STEIN_SOFTMAX_F_MAX = 1024, STEIN_SOFTMAX_FC_MAX = 16384 };
+int stein_score_softmax(const float* theta, int64_t n, int64_t d, int64_t w_col, int64_t n_feats, int64_t n_classes,
+                        int64_t alpha_col, const float* X, const int32_t* labels, int64_t batch, double scale,
+                        double prior_precision, double gamma_rate, float* score, void* stream);
+/* test hook, per calling thread: lanes that share a row in the forward phase (a power of two up to 64; the order in which a
+ * logit's F terms are summed follows it); 0 restores the rule */
+int stein_debug_score_softmax_lanes(int lanes);
+
 /* ---- posterior predictive producers (the step after the update) --------------------
  * The forward pass of the same three models for every particle: what the reference's examples hand to function_posterior
  * (stein/samplers/abstract_stein_sampler.py:157-168) and then average.  One call gives any non-empty subset of
@@ -758,6 +783,32 @@ int stein_predict_bnn_wide_weighted(const float* theta, int64_t n, int64_t d, in
                                     const int64_t* cols, int output, const float* X, const float* y, int64_t batch,
                                     const double* weights, float* pred, float* mean, float* var, float* lpd, double* ess,
                                     void* workspace, size_t ws_bytes, void* stream);
+
+/* Softmax regression (the model, theta, X, labels and the domain of stein_score_softmax; the alpha column is not read): the
+ * class probabilities of every particle and their per-test-point summaries.  One call gives any non-empty subset of
+ *   pred  [n][batch][n_classes]  STEIN_PRED_MEAN: p_pbc = softmax_c(z_pb.);  STEIN_PRED_LINK: the logits z_pbc
+ *   prob  [batch][n_classes]     1/n sum_p p_pbc, the posterior predictive class probabilities
+ *   lpd   [batch]                log(1/n sum_p p_{pb,y_b}); needs labels
+ *   ent   [batch]                1/n sum_p H(p_pb.), the expected entropy, H = logsumexp(z) - sum_c p_c z_c; the mutual
+ *                                information between the label and the particle is H(prob_b.) - ent_b
+ *   label [batch] int32          argmax_c prob_bc, ties to the lowest class, taken of the very floats prob receives
+ * and the summaries never materialise [n][batch][n_classes]; an output passed as NULL is not computed.  The summaries are
+ * of the probabilities whatever `output` says.  A label outside [0, n_classes) is no error code: the call returns STEIN_OK
+ * and that row's lpd is NaN, nothing else.  pred[p][b][.] depends on the particle and the row alone.
+ * Workspace: a call that asks for prob, lpd, ent or label needs stein_predict_softmax_workspace_bytes(n, batch, n_classes)
+ * bytes: 4 (n_classes + 2) per row and particle slice -- the slices are those of stein_predict_glm, so at most
+ * 4 (n_classes + 2) * min(1024 * batch, 2^19 + batch); the slice count is not cut further, which is 71 MB + 136 bytes a
+ * row at 32 classes and far less at the usual counts.  Monotone in n and batch, independent of d; it may hold anything on
+ * entry.  STEIN_E_WORKSPACE without it; a call that only asks for pred needs none (NULL, 0).
+ * Deterministic: no atomics; the slices are summed in slice order in fp64, so a repeated call is bit-identical.
+ * Refused before any launch, in this order: theta or X NULL, all five outputs NULL, lpd without labels, an unknown output
+ * (STEIN_E_BADARG); a bad shape (STEIN_E_SHAPE); the domain (STEIN_E_UNSUPPORTED, naming the limit); weights that do not
+ * fit d (STEIN_E_SHAPE); the workspace (STEIN_E_WORKSPACE). */
+int stein_predict_softmax_workspace_bytes(int64_t n, int64_t batch, int64_t n_classes, size_t* out_bytes);
+int stein_predict_softmax(const float* theta, int64_t n, int64_t d, int output, int64_t w_col, int64_t n_feats,
+                          int64_t n_classes, const float* X, const int32_t* labels, int64_t batch,
+                          float* pred, float* prob, float* lpd, float* ent, int32_t* label,
+                          void* workspace, size_t ws_bytes, void* stream);
 
 /* Order statistics of the outputs: credible bands and the ensemble median per test point, without pred.
  *   out [n_ranks][batch]   out[i][b] = the ranks[i]-th smallest (0-based) of the n values f_pb, p = 0 .. n-1

@@ -33,6 +33,7 @@ FLAG_FOLD = 512     # the fused call takes the folded contraction (K.W, W = G - 
 FLAG_NO_FOLD = 1024  # ... never takes it
 FLAG_KSD = 256      # also the kernelized Stein discrepancy sums: sqnorm is double[3] = |phi|^2, S, S_diag
 GLM_LINEAR, GLM_LOGISTIC = 0, 1
+SOFTMAX_C_MIN, SOFTMAX_C_MAX, SOFTMAX_F_MAX, SOFTMAX_FC_MAX = 2, 32, 1024, 16384   # STEIN_SOFTMAX_*: the domain of the softmax calls
 PRED_LINK, PRED_MEAN = 0, 1
 PRED_RANKS_MAX = 8                # STEIN_PRED_RANKS_MAX: order statistics per stein_predict_*_ranks call
 MASS_NORMALISED, MASS_COUNTS = 0, 1   # STEIN_MASS_* (stein_predict_rank_masses)
@@ -67,6 +68,10 @@ _SIGNATURES = {
     "stein_score_glm": [_vp, _i64, _i64, _int, _i64, _i64, _i64, _vp, _vp, _i64, _dbl, _dbl, _dbl, _vp, _vp],
     "stein_score_bnn": [_vp, _i64, _i64, _i64, _i64, _c.POINTER(_i64), _vp, _vp, _i64, _dbl, _dbl, _dbl, _vp, _vp],
     "stein_score_bnn_wide": [_vp, _i64, _i64, _i64, _i64, _c.POINTER(_i64), _vp, _vp, _i64, _dbl, _dbl, _dbl, _vp, _vp],
+    "stein_score_softmax": [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _dbl, _dbl, _dbl, _vp, _vp],
+    "stein_debug_score_softmax_lanes": [_int],
+    "stein_predict_softmax_workspace_bytes": [_i64, _i64, _i64, _c.POINTER(_sz)],
+    "stein_predict_softmax": [_vp, _i64, _i64, _int, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "stein_predict_workspace_bytes": [_i64, _i64, _c.POINTER(_sz)],
     "stein_predict_glm": [_vp, _i64, _i64, _int, _int, _i64, _i64, _vp, _vp, _i64, _dbl, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "stein_predict_bnn": [_vp, _i64, _i64, _i64, _i64, _c.POINTER(_i64), _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
@@ -377,6 +382,20 @@ def predict_workspace_bytes(n, batch):
     total = _sz(0)
     call("stein_predict_workspace_bytes", n, batch, ctypes.byref(total))
     return int(total.value)
+
+
+def predict_softmax_workspace_bytes(n, batch, n_classes):
+    """Workspace bytes of a stein_predict_softmax call that asks for a summary (prob, lpd, ent, label): 4 (n_classes + 2)
+    bytes per row and particle slice, independent of d.  Host arithmetic."""
+    total = _sz(0)
+    call("stein_predict_softmax_workspace_bytes", n, batch, n_classes, ctypes.byref(total))
+    return int(total.value)
+
+
+def debug_score_softmax_lanes(lanes):
+    """Test hook (per calling thread): lanes per row of stein_score_softmax's forward phase (a power of two up to 64); 0
+    restores the rule.  The order in which a logit's terms are summed follows it."""
+    call("stein_debug_score_softmax_lanes", int(lanes))
 
 
 def predict_weighted_workspace_bytes(n, batch):

@@ -22,6 +22,11 @@ hand-written HIP kernels (csrc/stein_predict.hip) in two forms:
   y itself, observation noise included -- the Gaussian mixture over the particles, evaluated at points (``t=None``: at
   ``feed["y"]``, the probability integral transform) and inverted at levels (predictive intervals), with or without weights
   (csrc/stein_predict_y.hip; ``sampler.predictive_cdf`` / ``sampler.predictive_interval``).  Regression models only.
+
+``SoftmaxPredict`` (csrc/stein_predict_softmax.hip) is the producer of the softmax regression model of
+``stein_amd.scores.SoftmaxScore``: a vector of class probabilities per test point, so ``producer(theta_matrix, feed)`` is
+[n, batch, C] and its summaries -- class probabilities, label, expected entropy, log predictive density -- come from
+``producer.summary`` / ``sampler.predictive_classes``; the scalar-output methods above refuse it.
 """
 import ctypes
 import math
@@ -38,9 +43,37 @@ def _device_f32(name, t):
         raise ValueError("%s must be a contiguous float32 device tensor" % name)
 
 
-class _Predict:
-    """What the two producers share: argument checks, the workspace each object holds and regrows, the two call forms."""
+def _labels_i32(y, batch, device):
+    """feed["y"] of the softmax model: any integer-dtype tensor of [batch] -> contiguous int32 on `device` (never read on
+    the host: a label outside [0, n_classes) shows as NaN in the results)"""
+    if not isinstance(y, torch.Tensor):
+        y = torch.as_tensor(y)
+    if y.dtype.is_floating_point or y.is_complex() or y.dtype == torch.bool:
+        raise ValueError("y must hold integer class indices (an integer dtype), not %s" % y.dtype)
+    if y.numel() != batch:
+        raise ValueError("y must be [batch]")
+    return y.reshape(batch).to(device=device, dtype=torch.int32).contiguous()
+
+
+class _Buffers:
+    """What every producer holds: cached device buffers that regrow, and pointers of optional tensors."""
     wants_matrix = True   # function_posterior hands this callable the packed [n, d] matrix, not the dict of views
+
+    def _buffer(self, name, need, device, dtype=torch.uint8):
+        """the cached buffer self.<name>, regrown when it is missing, on another device or too small"""
+        buf = getattr(self, name)
+        if buf is None or buf.device != device or buf.numel() < need:
+            buf = torch.empty(need, dtype=dtype, device=device)
+            setattr(self, name, buf)
+        return buf
+
+    @staticmethod
+    def _ptr(t):
+        return None if t is None else t.data_ptr()
+
+
+class _Predict(_Buffers):
+    """What the two producers share: argument checks, the workspace each object holds and regrows, the two call forms."""
 
     def __init__(self, output, width):
         if output not in _OUTPUTS:
@@ -53,14 +86,6 @@ class _Predict:
         self._masses = self._mass_info = None   # weighted_quantiles: the particles' integer masses and their total
         self._mws = self._wrws = None           # ... the workspaces of the masses pass and of the weighted select
         self._ycws = self._yqws = None          # the workspaces of y_cdf and y_quantiles
-
-    def _buffer(self, name, need, device, dtype=torch.uint8):
-        """the cached buffer self.<name>, regrown when it is missing, on another device or too small"""
-        buf = getattr(self, name)
-        if buf is None or buf.device != device or buf.numel() < need:
-            buf = torch.empty(need, dtype=dtype, device=device)
-            setattr(self, name, buf)
-        return buf
 
     @staticmethod
     def _weights(weights, n, device, want_mode=False):
@@ -294,10 +319,6 @@ class _Predict:
                                     hi[at:at + len(part)], None if lo is None else lo[at:at + len(part)], ws)
         return (lo, hi) if return_bracket else hi
 
-    @staticmethod
-    def _ptr(t):
-        return None if t is None else t.data_ptr()
-
 
 class GlmPredict(_Predict):
     """Outputs of the generalised linear models of GlmScore: z = X w per particle.
@@ -433,3 +454,84 @@ class BnnPredict(_Predict):
         _lib.call_on(theta.device, "stein_predict_bnn_yquantiles", theta.data_ptr(), n, d, self.n_in, self.n_hidden,
                      self._cols, X.data_ptr(), batch, levels, n_levels, passes, self._ptr(weights), out.data_ptr(),
                      self._ptr(out_lo), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(theta.device).cuda_stream)
+
+
+class SoftmaxPredict(_Buffers):
+    """Class probabilities of the softmax regression model of SoftmaxScore: softmax(X W) per particle
+    (csrc/stein_predict_softmax.hip).
+
+    n_feats, n_classes, w_col : as for SoftmaxScore (W [n_feats, n_classes] row-major at w_col)
+    output                    : "mean" -> the probabilities p_pbc; "link" -> the logits z_pbc
+
+    ``producer(theta_matrix, feed)`` -> [n, batch, n_classes], a valid ``function_posterior`` callable
+    (``sampler.function_posterior`` flattens every callable's result per particle, so it hands back NumPy [n, batch * C]:
+    reshape it to (n, batch, C));
+    ``producer.summary(theta_matrix, feed)`` -> {"prob" [batch, C], "label" [batch] int32, "ent" [batch], "lpd" [batch]}:
+    the posterior predictive class probabilities mean_p p_pbc, their argmax, the expected entropy mean_p H(p_pb.) and -- only
+    when the feed has a "y" -- the log predictive density log(mean_p p_{pb,y_b}); device tensors, no [n, batch, C] formed.
+    ``sampler.predictive_classes(producer, feed)`` hands them back as NumPy with the entropy of prob and the mutual
+    information.  The scalar-output methods of GlmPredict / BnnPredict (mean and variance, order statistics, quantiles, the
+    distribution of y) have no meaning for a vector of class probabilities and raise a ValueError.
+    """
+    classes = True    # the samplers' scalar-output methods refuse this producer and name predictive_classes
+
+    def __init__(self, n_feats, n_classes, w_col=0, output="mean"):
+        if output not in _OUTPUTS:
+            raise ValueError("output must be 'link' or 'mean'")
+        self.output = _OUTPUTS[output]
+        self.n_feats, self.n_classes, self.w_col = int(n_feats), int(n_classes), int(w_col)
+        self._ws = None
+
+    def _inputs(self, theta, feed, want_y):
+        X = feed["X"]
+        _device_f32("theta", theta)
+        _device_f32("X", X)
+        if theta.dim() != 2:
+            raise ValueError("theta must be the packed [n, d] particle matrix")
+        batch = X.shape[0]
+        if X.shape != (batch, self.n_feats):
+            raise ValueError("X must be [batch, %d]" % self.n_feats)
+        y = None
+        if want_y:
+            y = _labels_i32(feed["y"], batch, theta.device)
+        return X, y, batch
+
+    def _launch(self, theta, X, y, batch, pred, prob, lpd, ent, label, ws):
+        n, d = theta.shape
+        p = self._ptr
+        _lib.call_on(theta.device, "stein_predict_softmax", theta.data_ptr(), n, d, self.output, self.w_col, self.n_feats,
+                     self.n_classes, X.data_ptr(), p(y), batch, p(pred), p(prob), p(lpd), p(ent), p(label), p(ws),
+                     0 if ws is None else ws.numel(), torch.cuda.current_stream(theta.device).cuda_stream)
+
+    def __call__(self, theta, feed, out=None):
+        """-> [n, batch, n_classes] float32 device tensor (written into `out` when given)."""
+        X, _, batch = self._inputs(theta, feed, False)
+        n = theta.shape[0]
+        if out is None:
+            out = torch.empty(n, batch, self.n_classes, dtype=torch.float32, device=theta.device)
+        else:
+            _device_f32("out", out)
+            if out.shape != (n, batch, self.n_classes):
+                raise ValueError("out must be [%d, %d, %d]" % (n, batch, self.n_classes))
+        self._launch(theta, X, None, batch, out, None, None, None, None, None)
+        return out
+
+    def summary(self, theta, feed):
+        """-> {"prob", "label", "ent"} and, when `feed` has a "y", "lpd": device tensors (see the class)."""
+        want_y = feed.get("y") is not None
+        X, y, batch = self._inputs(theta, feed, want_y)
+        dev = theta.device
+        out = {"prob": torch.empty(batch, self.n_classes, dtype=torch.float32, device=dev),
+               "label": torch.empty(batch, dtype=torch.int32, device=dev),
+               "ent": torch.empty(batch, dtype=torch.float32, device=dev)}
+        if want_y:
+            out["lpd"] = torch.empty(batch, dtype=torch.float32, device=dev)
+        ws = self._buffer("_ws", _lib.predict_softmax_workspace_bytes(theta.shape[0], batch, self.n_classes), dev)
+        self._launch(theta, X, y, batch, None, out["prob"], out.get("lpd"), out["ent"], out["label"], ws)
+        return out
+
+    def _scalar_only(self, *args, **kw):
+        raise ValueError("a SoftmaxPredict gives a vector of class probabilities per test point, not a scalar output: its "
+                         "summaries come from sampler.predictive_classes(producer, feed) (or producer.summary)")
+
+    weighted_summary = order_statistics = quantiles = weighted_quantiles = y_cdf = y_quantiles = _scalar_only

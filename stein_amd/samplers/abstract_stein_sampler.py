@@ -327,6 +327,9 @@ class AbstractSteinSampler:
                              "ranks' states; use function_posterior, which gathers the outputs")
         if not hasattr(producer, "summary"):
             raise ValueError("posterior_predictive needs a predictive producer (GlmPredict / BnnPredict)")
+        if getattr(producer, "classes", False):
+            raise ValueError("posterior_predictive summarises a scalar output per test point; a SoftmaxPredict gives class "
+                             "probabilities: use predictive_classes(producer, feed)")
         ess = None
         with torch.no_grad():
             if weights is None:
@@ -341,6 +344,31 @@ class AbstractSteinSampler:
             out["lpd"] = lpd.cpu().numpy()
         if ess is not None:
             out["ess"] = float(ess.item())
+        return out
+
+    def predictive_classes(self, producer, feed):
+        """Per-test-point summaries of a class-probability producer (stein_amd.predict.SoftmaxPredict) under the current
+        particles, NumPy arrays: "prob" [batch, C], the posterior predictive class probabilities mean_p p_pbc; "label"
+        [batch] int32, their argmax (ties to the lowest class); "entropy" [batch], H(prob_b.), the total predictive
+        uncertainty; "mutual_information" [batch], entropy minus the expected entropy mean_p H(p_pb.), clipped at 0 -- the
+        part of the uncertainty that comes from the particles disagreeing, large far from the training data; and, when
+        `feed` has a "y", "lpd" [batch] = log(mean_p p_{pb,y_b}).  The [n, batch, C] tensor that function_posterior returns
+        is never formed.  One rank only."""
+        if self._group is not None:
+            raise ValueError("predictive_classes works on one rank only: a sharded sampler would have to merge the ranks' "
+                             "sums; use function_posterior, which gathers the outputs")
+        if not getattr(producer, "classes", False):
+            raise ValueError("predictive_classes needs a class-probability producer (SoftmaxPredict); GlmPredict and "
+                             "BnnPredict go to posterior_predictive")
+        with torch.no_grad():
+            s = producer.summary(self._matrix_f32(), feed)
+        prob = s["prob"].cpu().numpy()
+        p64 = prob.astype(np.float64)
+        entropy = -(p64 * np.log(np.where(p64 > 0, p64, 1.0))).sum(-1)
+        out = {"prob": prob, "label": s["label"].cpu().numpy(), "entropy": entropy.astype(np.float32)}
+        out["mutual_information"] = np.maximum(out["entropy"] - s["ent"].cpu().numpy(), np.float32(0))
+        if "lpd" in s:
+            out["lpd"] = s["lpd"].cpu().numpy()
         return out
 
     def predictive_quantiles(self, producer, feed, q, weights=None):

@@ -8,6 +8,7 @@ a closed form; ``GlmScore`` evaluates it with one hand-written HIP kernel (csrc/
 import torch
 
 from . import _lib
+from .predict import _labels_i32
 
 
 class GlmScore:
@@ -94,4 +95,40 @@ class BnnScore:
         return out
 
 
-from .predict import BnnPredict, GlmPredict  # noqa: E402,F401  (the producers of the step after the update, beside these)
+class SoftmaxScore:
+    """Score of softmax (multi-class logistic) regression, for every particle in one launch (csrc/stein_score_softmax.hip).
+
+    score(theta_matrix, feed) -> [n, d] float32 device tensor, feed = {"X": [batch, n_feats] float32, "y": [batch] class
+    indices in any integer dtype}.  A particle packs W [n_feats, n_classes] row-major at w_col -- how a [F, C] variable
+    flattens -- and log(alpha) at alpha_col (None: the fixed prior precision); there is no bias term, append a column of
+    ones to X.  Prior and scaling as GlmScore's logistic model: W ~ N(0, 1/alpha), alpha ~ Gamma(1, gamma_rate), the batch's
+    log-likelihood times n_train / batch.  2 <= n_classes <= 32, n_feats <= 1024, n_feats * n_classes <= 16384.
+    """
+    wants_matrix = True
+
+    def __init__(self, n_feats, n_classes, w_col=0, alpha_col=None, n_train=None, prior_precision=1.0, gamma_rate=0.01):
+        self.n_feats, self.n_classes, self.w_col = int(n_feats), int(n_classes), int(w_col)
+        self.alpha_col = -1 if alpha_col is None else int(alpha_col)
+        self.n_train = n_train
+        self.prior_precision, self.gamma_rate = float(prior_precision), float(gamma_rate)
+
+    def __call__(self, theta, feed, out=None):
+        X = feed["X"]
+        for name, t in (("theta", theta), ("X", X)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                raise ValueError("%s must be a contiguous float32 device tensor" % name)
+        n, d = theta.shape
+        batch = X.shape[0]
+        if X.shape != (batch, self.n_feats):
+            raise ValueError("X must be [batch, %d]" % self.n_feats)
+        y = _labels_i32(feed["y"], batch, theta.device)
+        if out is None:
+            out = torch.empty_like(theta)
+        scale = 1.0 if self.n_train is None else float(self.n_train) / batch
+        _lib.call_on(theta.device, "stein_score_softmax", theta.data_ptr(), n, d, self.w_col, self.n_feats, self.n_classes,
+                     self.alpha_col, X.data_ptr(), y.data_ptr(), batch, scale, self.prior_precision, self.gamma_rate,
+                     out.data_ptr(), torch.cuda.current_stream(theta.device).cuda_stream)
+        return out
+
+
+from .predict import BnnPredict, GlmPredict, SoftmaxPredict  # noqa: E402,F401  (the producers of the step after the update)
