@@ -571,7 +571,8 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
   const int wpm = FOLD ? (cblocks + 1) >> 1 : cblocks;
   constexpr int FS_KTB = NP * PLN;            // one k tile in LDS: NP planes, packed
   constexpr int FS_STAGE = FS_KT * FS_KTB;    // 2 stages x FS_KT x NP x 8 KB: 128 KB (NP 2), 64 KB (NP 1)
-  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * FS_STAGE];
+  // (+ 1 KB behind the stages: the row-sum exchange of the `up` path, which the output image below does not cover)
+  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * FS_STAGE + 1024];
 
   const int logical = xcd_remap(blockIdx.x, gridDim.x);
   // Which (row tile, column block) a workgroup takes.  An XCD runs 32 consecutive logical ids at a time (one workgroup per
@@ -643,6 +644,83 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
   const int ntr = up ? max(0, min(nstage, (i0 - jbeg) / (FS_KT * BK))) : 0;
 
   const int t = threadIdx.x;
+  // ---- the output tail: the partial sums leave through LDS in whole lines ------------------------------------------------
+  // An accumulator is four ROWS of one column, so a matrix wave's own store is a dword per lane and touches four 64-byte
+  // half lines per instruction: 64 such stores per lane, 128 KB per workgroup, while the producers idle -- and the tail of a
+  // kernel that runs one workgroup per CU in a single round is all exposed.  Instead: behind the loop's last barrier the
+  // stage buffers are dead; the matrix waves write their scaled accumulators (the same multiplication as before: the same
+  // bits) into an image of the workgroup's tile there, one barrier, and all twelve waves store the image row-major with
+  // 16-byte stores, eight consecutive lanes to a 128-byte line.
+  //   Image: unit (c, rg) = the 16 bytes { rows 4 rg .. 4 rg + 3 of image column c } at byte rg * IMG_PITCH +
+  //   16 * (c ^ (rg & 3)): row-group-major, one row group = IMG_COLS units.  NP 2: all 256 columns, 128 KB = both stages;
+  //   NP 1 (64 KB of stages): 128 columns, the two halves of the matrix waves one after the other (two more barriers).
+  //   Writes (ds_write_b128: groups of 8 contiguous lanes, 32 banks): the lanes of a group are 8 consecutive columns of one row
+  //   group, and the XOR permutes inside aligned fours: 8 distinct 16-byte slots of a 128-byte bank row.  Reads, 16-byte form
+  //   (ds_read_b128: lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31} and the same + 32, 64 banks): lane l reads column
+  //   4 (l & 7) + k of row group R + (l >> 3), so a group holds every (l & 3) once in each of four row groups with four
+  //   different rg & 3: slot ((4 (l & 3) + k) ^ (rg & 3)) & 15 takes all 16 values.  4-byte form: a wave reads 64 consecutive
+  //   columns of one row group, a lane group sees 16 different c & 15 under one XOR.  No conflicts in any of the three.
+  //   The row-sum exchange of the `up` path has 1 KB of its own behind the stages, so it needs no barrier of its own any
+  //   more: the image's barrier orders it, on every path both roles pass 1 (NP 2) or 3 (NP 1) barriers behind the loop.
+  constexpr int IMG_COLS = NP == 2 ? 256 : 128;
+  constexpr int IMG_PITCH = IMG_COLS * 16;
+  constexpr int IMG_PASSES = 256 / IMG_COLS;
+  static_assert(32 * IMG_PITCH <= 2 * FS_STAGE, "the output image lives in the stage buffers");
+  // 16-byte stores need rows on 16-byte boundaries (d % 4 == 0 makes every z slice and row start one if the bases are).
+  // OG and OT are workspace sections, each a multiple of 256 bytes from the workspace's base (stein_make_layout), so the
+  // pointer half of this test only fails for a workspace that is itself off a 16-byte boundary -- which no allocation of the
+  // package is, and which finish_stage (steinhip.hip) allows for in the same way.  The loop it then takes is the one every
+  // d % 4 != 0 call takes.
+  const bool vec16 = (d & 3) == 0 && ((((size_t)OG) | ((size_t)OT)) & 15) == 0;
+  auto image_store = [&](int ps) {   // all twelve waves; ps: which half of the column pair the image holds (NP 1)
+    const int wv = __builtin_amdgcn_readfirstlane(t >> 6), ln = t & 63;
+    if (vec16) {
+      // task = 8 row groups (32 rows) x 32 columns: four reads and four stores per lane, a store = 8 rows x one whole line
+      constexpr int MB = IMG_COLS / 32, NT = 4 * MB;
+#pragma unroll
+      for (int q = 0; q < (NT + 11) / 12; ++q) {
+        const int task = wv + 12 * q;
+        if (task >= NT) break;
+        const int mb = task % MB, rg = (task / MB) * 8 + (ln >> 3);
+        const int g = 2 * cb + (NP == 2 ? mb >> 2 : ps);
+        if (FOLD && g >= cblocks) continue;   // (an odd block count: this half stores nothing)
+        const bool first = FOLD ? half == 0 : g < cblocks;
+        float* __restrict__ Oz = (first ? OG : OT) + (size_t)z * n_local * d;
+        const int c = 32 * mb + 4 * (ln & 7);
+        const int col = (FOLD || first ? g : g - cblocks) * BN + (c & (BN - 1));
+        const int row = i0 + 4 * rg;
+        if (col < d && row < n_local) {
+          const unsigned char* src = smem + rg * IMG_PITCH;
+          f32x4 u[4];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) u[k] = *reinterpret_cast<const f32x4*>(src + (((c + k) ^ (rg & 3)) * 16));
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (row + e < n_local)
+              *reinterpret_cast<f32x4*>(Oz + (size_t)(row + e) * d + col) = f32x4{u[0][e], u[1][e], u[2][e], u[3][e]};
+        }
+      }
+    } else {
+      // item = one row group x 64 columns: one read and four dword stores per lane, a store = 256 consecutive bytes of a row
+      constexpr int CH = IMG_COLS / 64, NI = 32 * CH;
+      for (int item = wv; item < NI; item += 12) {
+        const int ch = item % CH, rg = item / CH;
+        const int g = 2 * cb + (NP == 2 ? ch >> 1 : ps);
+        if (FOLD && g >= cblocks) continue;
+        const bool first = FOLD ? half == 0 : g < cblocks;
+        float* __restrict__ Oz = (first ? OG : OT) + (size_t)z * n_local * d;
+        const int c = 64 * ch + ln;
+        const int col = (FOLD || first ? g : g - cblocks) * BN + (c & (BN - 1));
+        const int row = i0 + 4 * rg;
+        if (col < d && row < n_local) {
+          const f32x4 u = *reinterpret_cast<const f32x4*>(smem + rg * IMG_PITCH + ((c ^ (rg & 3)) * 16));
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (row + e < n_local) Oz[(size_t)(row + e) * d + col] = u[e];
+        }
+      }
+    }
+  };
   // The two roles run separate loops (so neither carries the other's registers) with the same number of
   // barriers: one after the prologue, one per k tile.  The role test is wave-uniform (waves 0-3 / 4-11).
   if (t < 256) {
@@ -853,10 +931,10 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
     }
     if (up) {
       // natural tiles: rows lr + 32 p, the 8 threads of a row are 8 consecutive lanes; mirrored tiles: rows 4 ig + e, the 8
-      // threads of a row are the lanes jq = 0..7 (lane bits 3..5).  The two row sets meet in LDS (the stage buffers are
-      // dead: every wave is past the loop's last barrier; the matrix waves take the same extra barrier) and are added in a
-      // fixed order.
-      float* red = reinterpret_cast<float*>(smem);   // [128] natural sums | [128] mirrored sums
+      // threads of a row are the lanes jq = 0..7 (lane bits 3..5).  The two row sets meet in LDS (behind the stage buffers,
+      // where the matrix waves are writing the output image by now; the image's barrier orders the exchange) and are added
+      // in a fixed order.
+      float* red = reinterpret_cast<float*>(smem + 2 * FS_STAGE);   // [128] natural sums | [128] mirrored sums
 #pragma unroll
       for (int p = 0; p < 4; ++p) {
         float a = rs[p], b = rst[p];
@@ -866,9 +944,6 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
         if ((pt & 7) == 0) red[lr + 32 * p] = a;
         if (jq == 0) red[128 + 4 * ig + p] = b;
       }
-      __syncthreads();
-      const int row = i0 + pt;
-      if (cb == 0 && !half && pt < 128 && row < n_local) RS[(size_t)z * n_local + row] = (red[pt] + red[128 + pt]) * sc[4 * dc + 2];
     } else if (cb == 0 && !half) {   // rowsum: the 8 threads of a row are 8 consecutive lanes
 #pragma unroll
       for (int p = 0; p < PR; ++p) {
@@ -879,6 +954,18 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
         const int row = i0 + lr + 32 * p;
         if ((pt & 7) == 0 && row < n_local) RS[(size_t)z * n_local + row] = sum * sc[4 * dc + 2];
       }
+    }
+    __syncthreads();   // the matrix waves have written the output image (and, up: the row sums have met)
+    if (up) {
+      const float* red = reinterpret_cast<const float*>(smem + 2 * FS_STAGE);
+      const int row = i0 + pt;
+      if (cb == 0 && !half && pt < 128 && row < n_local) RS[(size_t)z * n_local + row] = (red[pt] + red[128 + pt]) * sc[4 * dc + 2];
+    }
+    image_store(0);
+    if (IMG_PASSES == 2) {   // the second half's image: the same two barriers as the matrix waves
+      __syncthreads();
+      __syncthreads();
+      image_store(1);
     }
   } else {
     // ================================ CONSUMER ================================
@@ -973,27 +1060,37 @@ __global__ __launch_bounds__(FS_THREADS) void k_phi_x3fs(const float* __restrict
       }
       __syncthreads();
     }
-    if (up) __syncthreads();   // the producers' row-sum exchange (same barrier count in both roles)
-    // Never taken (cb < cblocks, so g <= 2 cblocks - 1).  It stays on measurement: without it the compiler places the
-    // matrix-wave loops 16 bytes lower, and the launch is 0.4 - 1.2 % slower at 8192 x 2001 (C3 and C2 do not move;
-    // profiles/contraction_one_geometry_ab.txt).
-    if (FOLD ? g >= cblocks : g >= 2 * cblocks) return;
+    // the scaled accumulators -> the output image (the tail's comment in front of the role split); a block past the
+    // matrix's last (FOLD, odd block count) writes nothing, nor does a column past d: nobody stores those units
     const bool first = FOLD ? half == 0 : g < cblocks;   // this wave's matrix: G (FOLD: W) or theta
-    float* __restrict__ Oz = (first ? OG : OT) + (size_t)z * n_local * d;
     const int cbase = (FOLD || first ? g : g - cblocks) * BN + wcol + l15;
     const float* __restrict__ osc = sc + (first ? 2 : 3) * dc;   // out-scales of this wave's matrix
+    // unit (c, rg = 4 i + lq): lq = rg & 3, and the XOR stays inside the low two bits of c, so i and j are immediates
+    unsigned char* const img = smem + lq * IMG_PITCH + ((((NP == 2 ? (cw >> 2) * BN : 0) + wcol + l15) ^ lq) * 16);
+    auto image_write = [&]() {
+      if (FOLD ? g >= cblocks : g >= 2 * cblocks) return;
 #pragma unroll
-    for (int j = 0; j < CJ; ++j) {
-      const int col = cbase + j * 16;
-      if (col >= d) continue;
-      const float os = osc[col];
+      for (int j = 0; j < CJ; ++j) {
+        const int col = cbase + j * 16;
+        if (col >= d) continue;
+        const float os = osc[col];
 #pragma unroll
-      for (int i = 0; i < FS_IB; ++i)
+        for (int i = 0; i < FS_IB; ++i) {
+          f32x4 v;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int row = i0 + i * 16 + 4 * lq + e;
-          if (row < n_local) Oz[(size_t)row * d + col] = acc[i][j][e] * os;
+          for (int e = 0; e < 4; ++e) v[e] = acc[i][j][e] * os;
+          *reinterpret_cast<f32x4*>(img + i * 4 * IMG_PITCH + j * 16 * 16) = v;
         }
+      }
+    };
+    if (NP == 2 || (cw >> 2) == 0) image_write();
+    __syncthreads();   // (the producers' row-sum exchange rides on this barrier: same count in both roles)
+    image_store(0);
+    if (IMG_PASSES == 2) {
+      __syncthreads();   // everybody has stored the first half's image
+      if ((cw >> 2) == 1) image_write();
+      __syncthreads();
+      image_store(1);
     }
   }
 }
