@@ -1,0 +1,97 @@
+"""A Bayesian network classifier with SVGD on synthetic data made here: points on three interleaved arcs in the plane, which
+no linear model separates, two inputs and a column of ones; nothing is read from disk.  One hidden ReLU layer of 20 units and
+a softmax head over 3 classes; every weight ~ N(0, 1/lambda), lambda ~ Gamma(1, 0.01) sampled in log space:
+d = 3 * 20 + 20 + 20 * 3 + 3 + 1 = 144 parameters per particle.
+
+    python examples/network_classifier/main.py [--particles 100] [--iters 1000] [--autograd]
+
+The score comes from the HIP score producer (stein_amd.scores.BnnClassScore -> stein_score_bnn_class) and the held-out
+readout -- accuracy and the mean log predictive density -- from sampler.predictive_classes
+(stein_amd.predict.BnnClassPredict -> stein_predict_bnn_class), with no [n, batch, C] tensor.  --autograd differentiates the
+same log posterior with torch instead, for comparison; the readout stays.
+"""
+import argparse
+import math
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
+from stein_amd.optimizers import AdagradGradientDescent  # noqa: E402
+from stein_amd.predict import BnnClassPredict  # noqa: E402
+from stein_amd.samplers import SteinSampler  # noqa: E402
+from stein_amd.scores import BnnClassScore  # noqa: E402
+
+N_IN, HIDDEN, C, BATCH = 3, 20, 3, 100
+GAMMA_RATE = 0.01
+W1, B1, W2, B2, LOG_LAMBDA = BnnClassScore.NAMES
+
+
+def make_data(rng, n_points):
+    """class k: the arc r = 0.4 + 0.9 s at the angle s + 2 pi k / 3, s in [0, 2.5], with a little noise"""
+    y = rng.integers(0, C, size=n_points)
+    s = rng.uniform(0.0, 2.5, size=n_points)
+    angle, r = s + 2.0 * math.pi * y / C, 0.4 + 0.9 * s
+    X = np.stack([r * np.cos(angle), r * np.sin(angle)], axis=1) + 0.06 * rng.normal(size=(n_points, 2))
+    return np.concatenate([X, np.ones((n_points, 1))], axis=1).astype(np.float32), y.astype(np.int64)
+
+
+def make_log_posterior(n_train):
+    def log_posterior(theta, feed):
+        w1, b1, w2, b2, log_lambda = theta[W1], theta[B1], theta[W2], theta[B2], theta[LOG_LAMBDA]
+        hid = torch.relu(torch.einsum("bf,nfh->nbh", feed["X"], w1) + b1[:, None, :])
+        logp = torch.log_softmax(torch.einsum("nbh,nhc->nbc", hid, w2) + b2[:, None, :], dim=-1)
+        lik = logp[:, torch.arange(feed["X"].shape[0], device=w1.device), feed["y"]].sum(-1)
+        lam = log_lambda.exp()
+        every = torch.cat([w1.reshape(w1.shape[0], -1), b1, w2.reshape(w2.shape[0], -1), b2], dim=1)
+        prior = (0.5 * log_lambda[:, None] - 0.5 * lam[:, None] * every ** 2 - 0.5 * math.log(2 * math.pi)).sum(-1)
+        prior = prior + math.log(GAMMA_RATE) - GAMMA_RATE * lam      # Gamma(1, rate) density at lambda, no Jacobian
+        return lik * n_train / feed["X"].shape[0] + prior
+    return log_posterior
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--particles", type=int, default=100)
+    ap.add_argument("--iters", type=int, default=1000)
+    ap.add_argument("--autograd", action="store_true", help="differentiate log_posterior with torch instead of the HIP score producer")
+    args = ap.parse_args()
+    rng = np.random.default_rng(0)
+    n_train = 2000
+    X, y = make_data(rng, n_train + 500)
+    dev = "cuda"
+    Xtr, ytr = torch.tensor(X[:n_train], device=dev), torch.tensor(y[:n_train], device=dev)
+    held_out = {"X": torch.tensor(X[n_train:], device=dev), "y": torch.tensor(y[n_train:], device=dev)}
+    shapes = {W1: [N_IN, HIDDEN], B1: [HIDDEN], W2: [HIDDEN, C], B2: [C], LOG_LAMBDA: []}
+    n = args.particles
+    init = {W1: rng.normal(size=(n, N_IN, HIDDEN)), B1: rng.normal(size=(n, HIDDEN)),
+            W2: rng.normal(size=(n, HIDDEN, C)) / math.sqrt(HIDDEN), B2: 0.1 * rng.normal(size=(n, C)), LOG_LAMBDA: 0.1 * rng.normal(size=n)}
+    sampler = SteinSampler(n, make_log_posterior(n_train), AdagradGradientDescent(learning_rate=5e-2), theta=init, model_vars=shapes)
+    cols = BnnClassScore.columns(sampler._access)
+    assert sampler.n_params == N_IN * HIDDEN + HIDDEN + HIDDEN * C + C + 1
+    if not args.autograd:   # the closed form of the same log posterior's gradient in one HIP launch (stein_amd/scores.py)
+        sampler.score = BnnClassScore(N_IN, HIDDEN, C, cols, n_train=n_train, gamma_rate=GAMMA_RATE)
+    predictive = BnnClassPredict(N_IN, HIDDEN, C, cols)
+
+    def readout():
+        out = sampler.predictive_classes(predictive, held_out)
+        return float((out["label"] == y[n_train:]).mean()), float(out["lpd"].mean())
+
+    order = torch.randperm(n_train, device=dev, generator=torch.Generator(device=dev).manual_seed(0))
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for i in range(args.iters):
+        at = (i * BATCH) % n_train
+        idx = order[at:at + BATCH]
+        sampler.train_on_batch({"X": Xtr[idx].contiguous(), "y": ytr[idx].contiguous()})
+        if i % 250 == 0 or i == args.iters - 1:
+            print("iteration %5d: held-out accuracy %.3f, mean log predictive density %.4f" % ((i,) + readout()))
+    torch.cuda.synchronize()
+    print("%d iterations with the %s score: %.2f s (readouts included)" % (args.iters, "autograd" if args.autograd else "HIP", time.perf_counter() - t0))
+
+
+if __name__ == "__main__":
+    main()

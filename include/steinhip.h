@@ -712,6 +712,38 @@ int stein_score_softmax(const float* theta, int64_t n, int64_t d, int64_t w_col,
  * logit's F terms are summed follows it); 0 restores the rule */
 int stein_debug_score_softmax_lanes(int lanes);
 
+/* Network classifier: one hidden ReLU layer with a softmax head -- stein_score_bnn's network with stein_score_softmax's
+ * likelihood, prior and scaling.
+ *   theta [n][d] float   particle i packs five blocks, cols[5] gives the first column of each, in any order:
+ *                        w1 [n_in][n_hidden] row-major (as stein_score_bnn), b1 [n_hidden], w2 [n_hidden][n_classes] row-major
+ *                        (how an [H, C] variable flattens), b2 [n_classes], log_lambda (cols[4] < 0: lambda = prior_precision,
+ *                        no entry); any other column gets score 0
+ *   X [batch][n_in] float, labels [batch] int32 class indices (device; never read on the host)
+ *   pre_bh = b1_h + sum_f x_bf w1_fh (f ascending), a_bh = relu(pre_bh);  z_bc = b2_c + sum_h a_bh w2_hc (h ascending),
+ *   p_b. = softmax(z_b.) evaluated with the row maximum subtracted
+ *   log p = scale * sum_b [z_{b,y_b} - logsumexp_c z_bc] + sum over all P = n_in H + H + H C + C entries of the four blocks of
+ *           log N(. ; 0, 1/lambda) + log Gamma(lambda; 1, gamma_rate), the density at lambda = exp(theta[cols[4]]) without a
+ *           Jacobian term.  The prior and the scaling are stein_score_softmax's over all four blocks; the division of
+ *           everything by n_train that stein_score_bnn inherits from the reference's regression example is not taken over.
+ *   score [n][d] float   with r_bc = 1[y_b = c] - p_bc, m_bh = [pre_bh > 0], delta_bh = m_bh sum_c r_bc w2_hc:
+ *                        d/db2_c = scale sum_b r_bc - lambda b2_c          d/dw2_hc = scale sum_b a_bh r_bc - lambda w2_hc
+ *                        d/db1_h = scale sum_b delta_bh - lambda b1_h      d/dw1_fh = scale sum_b x_bf delta_bh - lambda w1_fh
+ *                        d/dlog_lambda = P / 2 - lambda (1/2 sum of squares of the P entries + gamma_rate)
+ * Domain: 1 <= n_in <= 128, 2 <= n_classes <= 32, 1 <= n_hidden <= 512 and (n_in + CS) * n_hidden <= 16384 with CS =
+ * n_classes rounded up to a multiple of 4 (both layers and their gradients of a particle, 128 KB at most, lie in one
+ * workgroup's LDS beside a row block's activations and residuals); STEIN_E_UNSUPPORTED beyond, with a message that names the
+ * limit.  Refused before the launch, in this order: NULL pointers (STEIN_E_BADARG); a bad shape (STEIN_E_SHAPE); the domain
+ * (STEIN_E_UNSUPPORTED); blocks that do not fit d or overlap (STEIN_E_SHAPE).
+ * A label outside [0, n_classes) is no error code: the call returns STEIN_OK and every entry of the four blocks of every
+ * particle is NaN.
+ * One launch, no workspace, no atomics: the launch plan follows from (n_in, n_hidden, n_classes, batch) alone, a repeated
+ * call is bit-identical, and the row of a particle depends on nothing but the particle (not on n, the grid or the others). */
+enum { STEIN_BNN_CLASS_NIN_MAX = 128, STEIN_BNN_CLASS_C_MIN = 2, STEIN_BNN_CLASS_C_MAX = 32, STEIN_BNN_CLASS_H_MAX = 512,
+       STEIN_BNN_CLASS_W_MAX = 16384 };
+int stein_score_bnn_class(const float* theta, int64_t n, int64_t d, int64_t n_in, int64_t n_hidden, int64_t n_classes,
+                          const int64_t* cols, const float* X, const int32_t* labels, int64_t batch, double scale,
+                          double prior_precision, double gamma_rate, float* score, void* stream);
+
 /* ---- posterior predictive producers (the step after the update) --------------------
  * The forward pass of the same three models for every particle: what the reference's examples hand to function_posterior
  * (stein/samplers/abstract_stein_sampler.py:157-168) and then average.  One call gives any non-empty subset of
@@ -809,6 +841,25 @@ int stein_predict_softmax(const float* theta, int64_t n, int64_t d, int output, 
                           int64_t n_classes, const float* X, const int32_t* labels, int64_t batch,
                           float* pred, float* prob, float* lpd, float* ent, int32_t* label,
                           void* workspace, size_t ws_bytes, void* stream);
+
+/* Network classifier (the model, theta, cols, X, labels and the domain of stein_score_bnn_class; cols[4], the log_lambda
+ * column, is not read): the outputs, their meaning and the workspace rule are exactly stein_predict_softmax's, with
+ *   z_pbc = b2_pc + sum_h relu(b1_ph + sum_f x_bf w1_pfh) w2_phc   (f ascending, then h ascending)
+ * pred [n][batch][n_classes] (probabilities with STEIN_PRED_MEAN, logits with STEIN_PRED_LINK), prob [batch][n_classes],
+ * lpd [batch], ent [batch], label [batch] int32 (the lowest-index argmax of the very floats prob receives); any non-empty
+ * subset, an output passed as NULL is not computed.  A label outside [0, n_classes) gives NaN in that row's lpd and nowhere
+ * else.  pred[p][b][.] depends on the particle and the row alone.
+ * Workspace: a call that asks for prob, lpd, ent or label needs stein_predict_bnn_class_workspace_bytes(n, batch, n_classes)
+ * bytes: 4 (n_classes + 2) per row and particle slice, the slices of stein_predict_glm; it may hold anything on entry.  A
+ * call that only asks for pred needs none (NULL, 0).  Deterministic: no atomics, the slices are merged in slice order in fp64.
+ * Refused before any launch, in this order: theta, cols or X NULL, all five outputs NULL, lpd without labels, an unknown
+ * output (STEIN_E_BADARG); a bad shape (STEIN_E_SHAPE); the domain (STEIN_E_UNSUPPORTED, naming the limit); blocks that do not
+ * fit d or overlap (STEIN_E_SHAPE); the workspace (STEIN_E_WORKSPACE). */
+int stein_predict_bnn_class_workspace_bytes(int64_t n, int64_t batch, int64_t n_classes, size_t* out_bytes);
+int stein_predict_bnn_class(const float* theta, int64_t n, int64_t d, int output, int64_t n_in, int64_t n_hidden,
+                            int64_t n_classes, const int64_t* cols, const float* X, const int32_t* labels, int64_t batch,
+                            float* pred, float* prob, float* lpd, float* ent, int32_t* label,
+                            void* workspace, size_t ws_bytes, void* stream);
 
 /* Order statistics of the outputs: credible bands and the ensemble median per test point, without pred.
  *   out [n_ranks][batch]   out[i][b] = the ranks[i]-th smallest (0-based) of the n values f_pb, p = 0 .. n-1

@@ -34,6 +34,8 @@ FLAG_NO_FOLD = 1024  # ... never takes it
 FLAG_KSD = 256      # also the kernelized Stein discrepancy sums: sqnorm is double[3] = |phi|^2, S, S_diag
 GLM_LINEAR, GLM_LOGISTIC = 0, 1
 SOFTMAX_C_MIN, SOFTMAX_C_MAX, SOFTMAX_F_MAX, SOFTMAX_FC_MAX = 2, 32, 1024, 16384   # STEIN_SOFTMAX_*: the domain of the softmax calls
+# STEIN_BNN_CLASS_*: the domain of the network classifier's calls ((n_in + CS) * n_hidden <= W_MAX, CS = n_classes rounded up to 4)
+BNN_CLASS_NIN_MAX, BNN_CLASS_C_MIN, BNN_CLASS_C_MAX, BNN_CLASS_H_MAX, BNN_CLASS_W_MAX = 128, 2, 32, 512, 16384
 PRED_LINK, PRED_MEAN = 0, 1
 PRED_RANKS_MAX = 8                # STEIN_PRED_RANKS_MAX: order statistics per stein_predict_*_ranks call
 MASS_NORMALISED, MASS_COUNTS = 0, 1   # STEIN_MASS_* (stein_predict_rank_masses)
@@ -72,6 +74,10 @@ _SIGNATURES = {
     "stein_debug_score_softmax_lanes": [_int],
     "stein_predict_softmax_workspace_bytes": [_i64, _i64, _i64, _c.POINTER(_sz)],
     "stein_predict_softmax": [_vp, _i64, _i64, _int, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    "stein_score_bnn_class": [_vp, _i64, _i64, _i64, _i64, _i64, _c.POINTER(_i64), _vp, _vp, _i64, _dbl, _dbl, _dbl, _vp, _vp],
+    "stein_predict_bnn_class_workspace_bytes": [_i64, _i64, _i64, _c.POINTER(_sz)],
+    "stein_predict_bnn_class": [_vp, _i64, _i64, _int, _i64, _i64, _i64, _c.POINTER(_i64), _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
+                                _vp, _sz, _vp],
     "stein_predict_workspace_bytes": [_i64, _i64, _c.POINTER(_sz)],
     "stein_predict_glm": [_vp, _i64, _i64, _int, _int, _i64, _i64, _vp, _vp, _i64, _dbl, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "stein_predict_bnn": [_vp, _i64, _i64, _i64, _i64, _c.POINTER(_i64), _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
@@ -389,6 +395,14 @@ def predict_softmax_workspace_bytes(n, batch, n_classes):
     bytes per row and particle slice, independent of d.  Host arithmetic."""
     total = _sz(0)
     call("stein_predict_softmax_workspace_bytes", n, batch, n_classes, ctypes.byref(total))
+    return int(total.value)
+
+
+def predict_bnn_class_workspace_bytes(n, batch, n_classes):
+    """Workspace bytes of a stein_predict_bnn_class call that asks for a summary (prob, lpd, ent, label): 4 (n_classes + 2)
+    bytes per row and particle slice, independent of d.  Host arithmetic."""
+    total = _sz(0)
+    call("stein_predict_bnn_class_workspace_bytes", n, batch, n_classes, ctypes.byref(total))
     return int(total.value)
 
 

@@ -26,7 +26,8 @@ hand-written HIP kernels (csrc/stein_predict.hip) in two forms:
 ``SoftmaxPredict`` (csrc/stein_predict_softmax.hip) is the producer of the softmax regression model of
 ``stein_amd.scores.SoftmaxScore``: a vector of class probabilities per test point, so ``producer(theta_matrix, feed)`` is
 [n, batch, C] and its summaries -- class probabilities, label, expected entropy, log predictive density -- come from
-``producer.summary`` / ``sampler.predictive_classes``; the scalar-output methods above refuse it.
+``producer.summary`` / ``sampler.predictive_classes``; the scalar-output methods above refuse it.  ``BnnClassPredict``
+(csrc/stein_predict_bnn_class.hip) is the same producer for the network classifier of ``stein_amd.scores.BnnClassScore``.
 """
 import ctypes
 import math
@@ -474,6 +475,7 @@ class SoftmaxPredict(_Buffers):
     distribution of y) have no meaning for a vector of class probabilities and raise a ValueError.
     """
     classes = True    # the samplers' scalar-output methods refuse this producer and name predictive_classes
+    _workspace_bytes = staticmethod(_lib.predict_softmax_workspace_bytes)
 
     def __init__(self, n_feats, n_classes, w_col=0, output="mean"):
         if output not in _OUTPUTS:
@@ -526,12 +528,46 @@ class SoftmaxPredict(_Buffers):
                "ent": torch.empty(batch, dtype=torch.float32, device=dev)}
         if want_y:
             out["lpd"] = torch.empty(batch, dtype=torch.float32, device=dev)
-        ws = self._buffer("_ws", _lib.predict_softmax_workspace_bytes(theta.shape[0], batch, self.n_classes), dev)
+        ws = self._buffer("_ws", self._workspace_bytes(theta.shape[0], batch, self.n_classes), dev)
         self._launch(theta, X, y, batch, None, out["prob"], out.get("lpd"), out["ent"], out["label"], ws)
         return out
 
     def _scalar_only(self, *args, **kw):
-        raise ValueError("a SoftmaxPredict gives a vector of class probabilities per test point, not a scalar output: its "
-                         "summaries come from sampler.predictive_classes(producer, feed) (or producer.summary)")
+        raise ValueError("a %s gives a vector of class probabilities per test point, not a scalar output: its "
+                         "summaries come from sampler.predictive_classes(producer, feed) (or producer.summary)"
+                         % type(self).__name__)
 
     weighted_summary = order_statistics = quantiles = weighted_quantiles = y_cdf = y_quantiles = _scalar_only
+
+
+class BnnClassPredict(SoftmaxPredict):
+    """Class probabilities of the network classifier of BnnClassScore: softmax(relu(X w1 + b1) w2 + b2) per particle
+    (csrc/stein_predict_bnn_class.hip).
+
+    n_in, n_hidden, n_classes, cols : as for BnnClassScore (cols[4], the log_lambda column, is not read and may be left out)
+    output                          : "mean" -> the probabilities p_pbc; "link" -> the logits z_pbc
+
+    The call forms, ``summary``'s dict and the refusals of the scalar-output methods are SoftmaxPredict's:
+    ``producer(theta_matrix, feed)`` -> [n, batch, n_classes]; ``producer.summary(theta_matrix, feed)`` -> {"prob", "label",
+    "ent"} and, with a "y" in the feed, "lpd"; ``sampler.predictive_classes(producer, feed)`` hands them back as NumPy.
+    """
+    _workspace_bytes = staticmethod(_lib.predict_bnn_class_workspace_bytes)
+
+    def __init__(self, n_in, n_hidden, n_classes, cols, output="mean"):
+        if output not in _OUTPUTS:
+            raise ValueError("output must be 'link' or 'mean'")
+        self.output = _OUTPUTS[output]
+        self.n_in, self.n_hidden, self.n_classes = int(n_in), int(n_hidden), int(n_classes)
+        self.n_feats = self.n_in      # the columns of feed["X"], as _inputs checks them
+        cols = list(cols)[:4]
+        if len(cols) != 4:
+            raise ValueError("cols must give the first column of w1, b1, w2 and b2")
+        self._cols = (ctypes.c_int64 * 5)(*([int(c) for c in cols] + [-1]))
+        self._ws = None
+
+    def _launch(self, theta, X, y, batch, pred, prob, lpd, ent, label, ws):
+        n, d = theta.shape
+        p = self._ptr
+        _lib.call_on(theta.device, "stein_predict_bnn_class", theta.data_ptr(), n, d, self.output, self.n_in, self.n_hidden,
+                     self.n_classes, self._cols, X.data_ptr(), p(y), batch, p(pred), p(prob), p(lpd), p(ent), p(label), p(ws),
+                     0 if ws is None else ws.numel(), torch.cuda.current_stream(theta.device).cuda_stream)

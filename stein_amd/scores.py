@@ -131,4 +131,56 @@ class SoftmaxScore:
         return out
 
 
-from .predict import BnnPredict, GlmPredict, SoftmaxPredict  # noqa: E402,F401  (the producers of the step after the update)
+class BnnClassScore:
+    """Score of the network classifier, one hidden ReLU layer with a softmax head, for every particle in one launch
+    (csrc/stein_score_bnn_class.hip).
+
+    score(theta_matrix, feed) -> [n, d] float32 device tensor, feed = {"X": [batch, n_in] float32, "y": [batch] class indices
+    in any integer dtype}.  cols: first column of (w1 [n_in, H], b1 [H], w2 [H, C], b2 [C], log_lambda) in the packed
+    particle matrix, each flattened row-major -- use ``BnnClassScore.columns(sampler.access)``; cols[4] may be None: the fixed
+    prior precision.  Likelihood, prior and scaling are SoftmaxScore's over all four blocks -- every entry ~ N(0, 1/lambda),
+    lambda ~ Gamma(1, gamma_rate), the batch's log-likelihood times n_train / batch; BnnScore's division of everything by
+    n_train is not taken over.  1 <= n_in <= 128, 2 <= n_classes <= 32, n_hidden <= 512 and
+    (n_in + CS) * n_hidden <= 16384 with CS = n_classes rounded up to a multiple of 4.
+    """
+    wants_matrix = True
+    NAMES = ("model/w_1:0", "model/b_1:0", "model/w_2:0", "model/b_2:0", "model/log_lambda:0")
+
+    def __init__(self, n_in, n_hidden, n_classes, cols, n_train=None, prior_precision=1.0, gamma_rate=0.01):
+        import ctypes
+        self.n_in, self.n_hidden, self.n_classes = int(n_in), int(n_hidden), int(n_classes)
+        self.n_train = n_train
+        self.prior_precision, self.gamma_rate = float(prior_precision), float(gamma_rate)
+        cols = list(cols)
+        if len(cols) == 4:
+            cols.append(None)
+        if len(cols) != 5:
+            raise ValueError("cols must give the first column of w1, b1, w2, b2 and log_lambda (None: fixed precision)")
+        self._cols = (ctypes.c_int64 * 5)(*[-1 if c is None else int(c) for c in cols])
+
+    @staticmethod
+    def columns(access, names=NAMES):
+        """first packed column of each parameter block from a sampler's access map {name: (start, end)}; a name that is
+        None or absent from the map (the log_lambda of a fixed-precision model) gives None"""
+        return tuple(access[k][0] if k is not None and k in access else None for k in names)
+
+    def __call__(self, theta, feed, out=None):
+        X = feed["X"]
+        for name, t in (("theta", theta), ("X", X)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                raise ValueError("%s must be a contiguous float32 device tensor" % name)
+        n, d = theta.shape
+        batch = X.shape[0]
+        if X.shape != (batch, self.n_in):
+            raise ValueError("X must be [batch, %d]" % self.n_in)
+        y = _labels_i32(feed["y"], batch, theta.device)
+        if out is None:
+            out = torch.empty_like(theta)
+        scale = 1.0 if self.n_train is None else float(self.n_train) / batch
+        _lib.call_on(theta.device, "stein_score_bnn_class", theta.data_ptr(), n, d, self.n_in, self.n_hidden, self.n_classes,
+                     self._cols, X.data_ptr(), y.data_ptr(), batch, scale, self.prior_precision, self.gamma_rate,
+                     out.data_ptr(), torch.cuda.current_stream(theta.device).cuda_stream)
+        return out
+
+
+from .predict import BnnClassPredict, BnnPredict, GlmPredict, SoftmaxPredict  # noqa: E402,F401  (the producers of the step after the update)
