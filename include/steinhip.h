@@ -861,6 +861,43 @@ int stein_predict_bnn_class(const float* theta, int64_t n, int64_t d, int output
                             float* pred, float* prob, float* lpd, float* ent, int32_t* label,
                             void* workspace, size_t ws_bytes, void* stream);
 
+/* Weighted class summaries: stein_predict_softmax / stein_predict_bnn_class under per-particle weights -- Stein importance
+ * weights (stein_weights), or the counts of a thinned multiset (torch.bincount of stein_thin's indices).  weights [n]: fp64
+ * device data, never read on the host, w_p >= 0, their sum W > 0; they need not sum to 1.
+ *   prob_bc = sum_p w_p p_pbc / W      lpd_b = log(sum_p w_p p_{pb,y_b} / W)      ent_b = sum_p w_p H(p_pb.) / W
+ *   label_b = the lowest-index argmax_c of the very floats prob receives
+ *   ess [1] (fp64, device) = W^2 / sum_p w_p^2, the effective sample size of the weights
+ * with p_pbc and H exactly those of the unweighted calls.  The conventions are those of stein_predict_glm_weighted:
+ *   Lane weights: the lanes hold fl32(w_p / W), the quotient taken in fp64; a weight below 2^-126 W counts as zero.
+ *   Power-of-two scaling: rescaling the weights by a power of two changes no bit of any output (while the sums stay in
+ *     fp64's normal range).
+ *   Zero weight: a particle of lane weight zero enters no summary, even if its probabilities are NaN.
+ *   Bad weights: a negative or non-finite weight, W = 0 or an overflowing W return STEIN_OK with every requested prob / lpd /
+ *     ent row and ess NaN and every label -1.
+ *   Bad labels: a label outside [0, n_classes) still gives NaN in that row's lpd and nowhere else.
+ *   pred does not depend on the weights: it is bit for bit the unweighted call's and is written for every particle.
+ *   Deterministic: no atomics; a repeated call is bit-identical, whatever the workspace holds on entry.
+ *   Summation: a slice's sums are sum_p fl32(w_p / W) q_p taken with one fmaf per term, particles ascending; the slices are
+ *     added in slice order in fp64 and nothing is divided, because the lane weights already sum to 1.
+ * When pred is NULL, particles of lane weight zero are not computed and staging units that hold nothing else are not read:
+ * a thinned sample costs about what its distinct particles cost.  No summary bit depends on whether pred is asked for.
+ * Workspace: a call that asks for prob, lpd, ent, label or ess needs stein_predict_*_weighted_workspace_bytes(n, batch,
+ * n_classes) bytes, 8-byte aligned (STEIN_E_WORKSPACE otherwise) -- the unweighted size plus 24 bytes per particle slice (of
+ * the bound min(ceil(n / 16), 1024)) and 16 more for the sums of the weights, which come first; monotone in n and batch,
+ * independent of d.  It may hold anything on entry.  A call that only asks for pred needs none.
+ * Refusals and their order are those of the unweighted calls, with weights == NULL among the NULL pointers (STEIN_E_BADARG)
+ * and ess counting as a requested output and as a summary: an ess-only call is legal and needs the workspace. */
+int stein_predict_softmax_weighted_workspace_bytes(int64_t n, int64_t batch, int64_t n_classes, size_t* out_bytes);
+int stein_predict_softmax_weighted(const float* theta, int64_t n, int64_t d, int output, int64_t w_col, int64_t n_feats,
+                                   int64_t n_classes, const float* X, const int32_t* labels, int64_t batch,
+                                   const double* weights, float* pred, float* prob, float* lpd, float* ent, int32_t* label,
+                                   double* ess, void* workspace, size_t ws_bytes, void* stream);
+int stein_predict_bnn_class_weighted_workspace_bytes(int64_t n, int64_t batch, int64_t n_classes, size_t* out_bytes);
+int stein_predict_bnn_class_weighted(const float* theta, int64_t n, int64_t d, int output, int64_t n_in, int64_t n_hidden,
+                                     int64_t n_classes, const int64_t* cols, const float* X, const int32_t* labels,
+                                     int64_t batch, const double* weights, float* pred, float* prob, float* lpd, float* ent,
+                                     int32_t* label, double* ess, void* workspace, size_t ws_bytes, void* stream);
+
 /* Order statistics of the outputs: credible bands and the ensemble median per test point, without pred.
  *   out [n_ranks][batch]   out[i][b] = the ranks[i]-th smallest (0-based) of the n values f_pb, p = 0 .. n-1
  * with f_pb bit for bit what stein_predict_glm / stein_predict_bnn write to pred for the same arguments (one body of device

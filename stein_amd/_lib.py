@@ -74,10 +74,16 @@ _SIGNATURES = {
     "stein_debug_score_softmax_lanes": [_int],
     "stein_predict_softmax_workspace_bytes": [_i64, _i64, _i64, _c.POINTER(_sz)],
     "stein_predict_softmax": [_vp, _i64, _i64, _int, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    "stein_predict_softmax_weighted_workspace_bytes": [_i64, _i64, _i64, _c.POINTER(_sz)],
+    "stein_predict_softmax_weighted": [_vp, _i64, _i64, _int, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       _vp, _sz, _vp],
     "stein_score_bnn_class": [_vp, _i64, _i64, _i64, _i64, _i64, _c.POINTER(_i64), _vp, _vp, _i64, _dbl, _dbl, _dbl, _vp, _vp],
     "stein_predict_bnn_class_workspace_bytes": [_i64, _i64, _i64, _c.POINTER(_sz)],
     "stein_predict_bnn_class": [_vp, _i64, _i64, _int, _i64, _i64, _i64, _c.POINTER(_i64), _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
                                 _vp, _sz, _vp],
+    "stein_predict_bnn_class_weighted_workspace_bytes": [_i64, _i64, _i64, _c.POINTER(_sz)],
+    "stein_predict_bnn_class_weighted": [_vp, _i64, _i64, _int, _i64, _i64, _i64, _c.POINTER(_i64), _vp, _vp, _i64, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "stein_predict_workspace_bytes": [_i64, _i64, _c.POINTER(_sz)],
     "stein_predict_glm": [_vp, _i64, _i64, _int, _int, _i64, _i64, _vp, _vp, _i64, _dbl, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "stein_predict_bnn": [_vp, _i64, _i64, _i64, _i64, _c.POINTER(_i64), _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
@@ -403,6 +409,22 @@ def predict_bnn_class_workspace_bytes(n, batch, n_classes):
     bytes per row and particle slice, independent of d.  Host arithmetic."""
     total = _sz(0)
     call("stein_predict_bnn_class_workspace_bytes", n, batch, n_classes, ctypes.byref(total))
+    return int(total.value)
+
+
+def predict_softmax_weighted_workspace_bytes(n, batch, n_classes):
+    """Workspace bytes of a stein_predict_softmax_weighted call that asks for prob, lpd, ent, label or ess: the unweighted
+    size plus the weight pass's per-slice sums.  Host arithmetic."""
+    total = _sz(0)
+    call("stein_predict_softmax_weighted_workspace_bytes", n, batch, n_classes, ctypes.byref(total))
+    return int(total.value)
+
+
+def predict_bnn_class_weighted_workspace_bytes(n, batch, n_classes):
+    """Workspace bytes of a stein_predict_bnn_class_weighted call that asks for prob, lpd, ent, label or ess: the unweighted
+    size plus the weight pass's per-slice sums.  Host arithmetic."""
+    total = _sz(0)
+    call("stein_predict_bnn_class_weighted_workspace_bytes", n, batch, n_classes, ctypes.byref(total))
     return int(total.value)
 
 

@@ -15,26 +15,46 @@
 // from, and in which order, follows from (n_in, H, C) alone: not from its place in the unit, the slice or the grid.
 // k_predict_bnn_class_finish merges the slices in slice order in fp64.  No atomics; every workspace word that is read was
 // written by the same call.
+//
+// Weighted form (stein_predict_bnn_class_weighted; the WEIGHTED instantiations), as stein_predict_softmax.hip describes it:
+// the lane weights fl32(w_p / W) of PC_WB particles at a time lie behind the staging unit (restaged when a unit's last
+// particle passes their end), the running sums become acc = fmaf(w, q, acc), and without pred a particle of lane weight
+// zero is not computed and a unit all of whose (particle, tile) items belong to such particles is not staged either.  A
+// particle whose tiles straddle a skipped unit has weight zero itself; what its remaining tiles would add to the logits is
+// never computed, and the next particle's first tile sets the logits to its b2 (tile == 0 below).
 #include "stein_predict_fwd.h"
 
 constexpr int PC_NIN_MAX = 128, PC_C_MIN = 2, PC_C_MAX = 32, PC_H_MAX = 512, PC_W_MAX = 16384;
 
+constexpr int PC_WB = 64;   // WEIGHTED: particles whose lane weights are staged at a time (more than a unit's PR_PASS + 1)
+
 struct PredClassCols { int w1, b1, w2, b2; };
+
+// a value every lane holds alike, as the scalar the branches on it want
+__device__ __forceinline__ float pc_uniform(float v) {
+  return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
+}
 
 // floats of a staged (particle, tile) pair
 static __host__ __device__ inline int pc_item_floats(int F, int CS) { return (F + 1 + CS) * PR_WT + CS; }
 
-template <int CP>
+// WEIGHTED: wts [n] the weights, head the weight pass's header (head[0] = W)
+template <int CP, bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_predict_bnn_class(const float* __restrict__ theta, int n, int d, int F, int H, int C,
                                                            PredClassCols c, int output, int ld, int ps,
                                                            const float* __restrict__ X, const int* __restrict__ labels, int B,
                                                            int per, float* __restrict__ pred, float* __restrict__ part,
-                                                           int want_lpd) {
+                                                           int want_lpd, const double* __restrict__ wts,
+                                                           const double* __restrict__ head) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int CS = (C + 3) & ~3, cq = CS / 4, iw = pc_item_floats(F, CS);
   const int o_w1 = PR_WT, o_w2 = o_w1 + F * PR_WT, o_b2 = o_w2 + PR_WT * CS;
   float* xs = lds;                                  // [PR_ROWS][ld]
   float* ws = lds + ((PR_ROWS * ld + 3) & ~3);      // [ps][iw]
+  [[maybe_unused]] float* wl = ws + ps * iw;        // [PC_WB], WEIGHTED only
+  [[maybe_unused]] double wtot = 0.0;
+  if constexpr (WEIGHTED) wtot = head[0];
+  [[maybe_unused]] int wb0 = -PC_WB;                // the first particle of wl, counted from p_begin
   const int t = threadIdx.x;
   const int row0 = blockIdx.x * PR_ROWS, row = row0 + t;
   const bool live = row < B;
@@ -52,6 +72,18 @@ __global__ __launch_bounds__(256) void k_predict_bnn_class(const float* __restri
   for (int cc = 0; cc < CP; ++cc) acc[cc] = z[cc] = 0.f;
   for (long j0 = 0; j0 < items; j0 += ps) {
     const int cnt = (int)min((long)ps, items - j0);
+    if constexpr (WEIGHTED) {
+      const int k0 = (int)(j0 / nt), k1 = (int)((j0 + cnt - 1) / nt);   // the unit's particles
+      if (k1 >= wb0 + PC_WB) {
+        wb0 = k0;
+        __syncthreads();   // every lane is past its last read of wl
+        if (t < PC_WB) wl[t] = p_begin + wb0 + t < p_end ? pred_norm_weight(wts[p_begin + wb0 + t], wtot) : 0.f;
+        __syncthreads();
+      }
+      bool any = false;
+      for (int k = k0; k <= k1; ++k) any = any || pc_uniform(wl[k - wb0]) != 0.f;
+      if (!pred && !any) continue;   // a dead unit: nothing of it is staged or computed
+    }
     __syncthreads();     // every lane is past its last read of ws
     for (int i = t; i < cnt * iw; i += 256) {
       const int it = i / iw, o = i - it * iw;
@@ -78,6 +110,11 @@ __global__ __launch_bounds__(256) void k_predict_bnn_class(const float* __restri
       const long j = j0 + it;
       const int pk = (int)(j / nt), tile = (int)(j - (long)pk * nt);
       const float* wk = ws + it * iw;
+      [[maybe_unused]] float wv = 0.f;
+      if constexpr (WEIGHTED) {
+        wv = pc_uniform(wl[pk - wb0]);
+        if (!pred && wv == 0.f) continue;   // a particle of weight zero enters nothing (uniform over the workgroup)
+      }
       if (tile == 0) {   // (uniform over the workgroup)
 #pragma unroll
         for (int q = 0; q < CP / 4; ++q) {
@@ -142,12 +179,23 @@ __global__ __launch_bounds__(256) void k_predict_bnn_class(const float* __restri
         for (int cc = 0; cc < CP; ++cc) {
           const float pc = e[cc] / s;
           if (out && output != STEIN_PRED_LINK && cc < C) out[cc] = pc;
-          acc[cc] += pc;
+          if constexpr (WEIGHTED) {
+            if (wv != 0.f) acc[cc] = fmaf(wv, pc, acc[cc]);
+          } else {
+            acc[cc] += pc;
+          }
           pt = fmaf(pc, z[cc], pt);
           py = (cc == yb && cc < C) ? pc : py;   // (a label in [C, CP) is no class: py stays NaN)
         }
-        acc_y += py;
-        acc_h += logf(s) - pt;
+        if constexpr (WEIGHTED) {
+          if (wv != 0.f) {   // (weight zero: the particle enters no sum, whatever its probabilities are)
+            acc_y = fmaf(wv, py, acc_y);
+            acc_h = fmaf(wv, logf(s) - pt, acc_h);
+          }
+        } else {
+          acc_y += py;
+          acc_h += logf(s) - pt;
+        }
       }
     }
   }
@@ -162,13 +210,18 @@ __global__ __launch_bounds__(256) void k_predict_bnn_class(const float* __restri
 }
 
 // The slices' sums merged in slice order, in fp64, as k_predict_softmax_finish does: PCF_ROWS rows per workgroup, the C + 2
-// quantities of a row over eight threads; then one thread per row takes the argmax of the floats prob received.
+// quantities of a row over eight threads; then one thread per row takes the argmax of the floats prob received.  WEIGHTED:
+// the lane weights sum to 1, so nothing is divided; bad weights (the header's W is NaN) give NaN rows and the label -1.
 constexpr int PCF_ROWS = 32;
 
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_predict_bnn_class_finish(const float* __restrict__ part, int slices, int n, int B,
                                                                   int C, float* __restrict__ prob, float* __restrict__ lpd,
-                                                                  float* __restrict__ ent, int* __restrict__ label) {
+                                                                  float* __restrict__ ent, int* __restrict__ label,
+                                                                  const double* __restrict__ head) {
   __shared__ float pr[PCF_ROWS][PC_C_MAX + 1];
+  [[maybe_unused]] bool bad = false;
+  if constexpr (WEIGHTED) bad = !(head[0] > 0.0);   // a negative or non-finite weight, W = 0 or an overflowing W
   const int r = threadIdx.x % PCF_ROWS, ql = threadIdx.x / PCF_ROWS;
   const int b = blockIdx.x * PCF_ROWS + r;
   if (b < B) {
@@ -177,14 +230,19 @@ __global__ __launch_bounds__(256) void k_predict_bnn_class_finish(const float* _
       const float* p = part + (size_t)q * B + b;
       double sum = 0.0;
       for (int s = 0; s < slices; ++s) sum += (double)p[(size_t)s * (C + 2) * B];
+      if constexpr (WEIGHTED) {
+        if (bad) sum = (double)NAN;
+      } else {
+        sum /= (double)n;
+      }
       if (q < C) {
-        const float v = (float)(sum / (double)n);
+        const float v = (float)sum;
         pr[r][q] = v;
         if (prob) prob[(size_t)b * C + q] = v;
       } else if (q == C) {
-        lpd[b] = (float)log(sum / (double)n);
+        lpd[b] = (float)log(sum);
       } else {
-        ent[b] = (float)(sum / (double)n);
+        ent[b] = (float)sum;
       }
     }
   }
@@ -197,6 +255,7 @@ __global__ __launch_bounds__(256) void k_predict_bnn_class_finish(const float* _
         top = pr[r][cc];
         best = cc;
       }
+    if constexpr (WEIGHTED) best = bad ? -1 : best;
     label[b] = best;
   }
 }
@@ -224,7 +283,7 @@ static int predict_bnn_class_domain(int64_t n_in, int64_t n_hidden, int64_t n_cl
 
 // the kernels take up to 160 KB of dynamic LDS (the X tile alone is 129 KB at 128 inputs): raise each one's limit once per device
 static int predict_bnn_class_attr(const void* fn, int slot) {
-  static bool attr_set[4][64] = {{false}};
+  static bool attr_set[8][64] = {{false}};
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
   if (dev < 0 || dev >= 64 || !attr_set[slot][dev]) {
@@ -234,22 +293,39 @@ static int predict_bnn_class_attr(const void* fn, int slot) {
   return STEIN_OK;
 }
 
-extern "C" int stein_predict_bnn_class_workspace_bytes(int64_t n, int64_t batch, int64_t n_classes, size_t* out_bytes) {
+// the workspace of a weighted call: the weight pass's header of the slice bound ahead of the states; monotone too
+static size_t predict_bnn_class_wws_bytes(int64_t n, int64_t batch, int64_t n_classes) {
+  int64_t s = (n + PR_PASS - 1) / PR_PASS;
+  if (s > PR_SLICE_CAP) s = PR_SLICE_CAP;
+  return pw_doubles(s) * sizeof(double) + predict_bnn_class_ws_bytes(n, batch, n_classes);
+}
+
+static int predict_bnn_class_ws_check(int64_t n, int64_t batch, int64_t n_classes, size_t* out_bytes, bool weighted) {
   if (!out_bytes) return stein_fail(STEIN_E_BADARG, "NULL pointer");
   if (n < 1 || batch < 1 || n_classes < 1 || n > PR_COUNT_MAX || batch > PR_COUNT_MAX)
     return stein_fail(STEIN_E_SHAPE, "bad shape n=%lld batch=%lld C=%lld", (long long)n, (long long)batch, (long long)n_classes);
   if (int rc = predict_bnn_class_domain(1, 1, n_classes)) return rc;
-  *out_bytes = predict_bnn_class_ws_bytes(n, batch, n_classes);
+  *out_bytes = weighted ? predict_bnn_class_wws_bytes(n, batch, n_classes) : predict_bnn_class_ws_bytes(n, batch, n_classes);
   return STEIN_OK;
 }
 
-extern "C" int stein_predict_bnn_class(const float* theta, int64_t n, int64_t d, int output, int64_t n_in, int64_t n_hidden,
-                                       int64_t n_classes, const int64_t* cols /*[5]: w1, b1, w2, b2; cols[4] is not read*/,
-                                       const float* X, const int32_t* labels, int64_t batch, float* pred, float* prob,
-                                       float* lpd, float* ent, int32_t* label, void* workspace, size_t ws_bytes, void* stream) {
-  if (!theta || !cols || !X) return stein_fail(STEIN_E_BADARG, "NULL pointer");
-  if (!pred && !prob && !lpd && !ent && !label)
-    return stein_fail(STEIN_E_BADARG, "no output requested: pred, prob, lpd, ent and label are all NULL");
+extern "C" int stein_predict_bnn_class_workspace_bytes(int64_t n, int64_t batch, int64_t n_classes, size_t* out_bytes) {
+  return predict_bnn_class_ws_check(n, batch, n_classes, out_bytes, false);
+}
+
+extern "C" int stein_predict_bnn_class_weighted_workspace_bytes(int64_t n, int64_t batch, int64_t n_classes, size_t* out_bytes) {
+  return predict_bnn_class_ws_check(n, batch, n_classes, out_bytes, true);
+}
+
+// both entry points (pw.on = false: the unweighted call, for which every check and launch is what it was)
+static int predict_bnn_class(const float* theta, int64_t n, int64_t d, int output, int64_t n_in, int64_t n_hidden,
+                             int64_t n_classes, const int64_t* cols /*[5]: w1, b1, w2, b2; cols[4] is not read*/,
+                             const float* X, const int32_t* labels, int64_t batch, float* pred, float* prob, float* lpd,
+                             float* ent, int32_t* label, void* workspace, size_t ws_bytes, void* stream, const PredWeights& pw) {
+  if (!theta || !cols || !X || (pw.on && !pw.w)) return stein_fail(STEIN_E_BADARG, "NULL pointer");
+  if (!pred && !prob && !lpd && !ent && !label && !pw.ess)
+    return stein_fail(STEIN_E_BADARG, pw.on ? "no output requested: pred, prob, lpd, ent, label and ess are all NULL"
+                                            : "no output requested: pred, prob, lpd, ent and label are all NULL");
   if (lpd && !labels) return stein_fail(STEIN_E_BADARG, "lpd needs labels");
   if (output != STEIN_PRED_LINK && output != STEIN_PRED_MEAN) return stein_fail(STEIN_E_BADARG, "output %d", output);
   if (n < 1 || d < 1 || batch < 1 || n_in < 1 || n_hidden < 1 || n_classes < 1 || n > PR_COUNT_MAX || d > 0x7fffffffl ||
@@ -263,12 +339,16 @@ extern "C" int stein_predict_bnn_class(const float* theta, int64_t n, int64_t d,
     for (int j = 0; j < i; ++j)
       if (cols[i] < cols[j] + len[j] && cols[j] < cols[i] + len[i]) return stein_fail(STEIN_E_SHAPE, "blocks %d and %d overlap", j, i);
   }
-  const bool summary = prob || lpd || ent || label;
-  if (summary) {
+  const bool summary = prob || lpd || ent || label;   // the rows the forward kernel reduces; ess comes from the weight pass alone
+  if (summary || pw.ess) {
     if (!workspace)
-      return stein_fail(STEIN_E_WORKSPACE, "prob, lpd, ent and label need a workspace (stein_predict_bnn_class_workspace_bytes)");
-    const size_t need = predict_bnn_class_ws_bytes(n, batch, n_classes);
+      return stein_fail(STEIN_E_WORKSPACE,
+                        pw.on ? "prob, lpd, ent, label and ess need a workspace (stein_predict_bnn_class_weighted_workspace_bytes)"
+                              : "prob, lpd, ent and label need a workspace (stein_predict_bnn_class_workspace_bytes)");
+    const size_t need = pw.on ? predict_bnn_class_wws_bytes(n, batch, n_classes) : predict_bnn_class_ws_bytes(n, batch, n_classes);
     if (ws_bytes < need) return stein_fail(STEIN_E_WORKSPACE, "workspace too small: %zu < %zu bytes", ws_bytes, need);
+    if (pw.on && (uintptr_t)workspace % sizeof(double))
+      return stein_fail(STEIN_E_WORKSPACE, "the workspace of a weighted call must be 8-byte aligned");
   }
   const PredPlan pl = predict_plan(n, batch);
   const int C = (int)n_classes, F = (int)n_in, H = (int)n_hidden, CS = (C + 3) & ~3;
@@ -278,25 +358,55 @@ extern "C" int stein_predict_bnn_class(const float* theta, int64_t n, int64_t d,
   int ps = (PR_WIDE_LDS - xt) / iw;
   if (ps > PR_PASS) ps = PR_PASS;
   if (ps < 1) return stein_fail(STEIN_E_UNSUPPORTED, "launch plan: no staging unit fits");   // (no shape of the domain gets here)
-  const size_t lds_bytes = ((size_t)xt + (size_t)ps * iw) * sizeof(float);
-  float* part = summary ? (float*)workspace : nullptr;
   hipStream_t s = (hipStream_t)stream;
+  if (pw.on && (summary || pw.ess))
+    if (int rc = predict_weight_pass(pl, n, pw, workspace, s)) return rc;
+  if (!pred && !summary) return STEIN_OK;   // ess alone
+  // a weighted call that only asks for pred runs the unweighted kernel: pred does not depend on the weights
+  const double* head = (pw.on && summary) ? (const double*)workspace : nullptr;
+  float* part = !summary ? nullptr : head ? (float*)((double*)workspace + pw_doubles(pl.slices)) : (float*)workspace;
+  // (the PC_WB lane weights go into the 128 floats PR_WIDE_LDS leaves free)
+  const size_t lds_bytes = ((size_t)xt + (size_t)ps * iw + (head ? PC_WB : 0)) * sizeof(float);
+#define PC_LAUNCH_AS(CP, WEIGHTED, SLOT)                                                                                 \
+  do {                                                                                                                   \
+    if (int rc = predict_bnn_class_attr(reinterpret_cast<const void*>(k_predict_bnn_class<CP, WEIGHTED>), SLOT)) return rc; \
+    hipLaunchKernelGGL((k_predict_bnn_class<CP, WEIGHTED>), dim3((unsigned)pl.row_tiles, (unsigned)pl.slices), dim3(256), \
+                       lds_bytes, s, theta, (int)n, (int)d, F, H, C, c, output, ld, ps, X, labels, (int)batch, pl.per,    \
+                       pred, part, lpd ? 1 : 0, pw.w, head);                                                              \
+  } while (0)
 #define PC_LAUNCH(CP, SLOT)                                                                                              \
   do {                                                                                                                   \
-    if (int rc = predict_bnn_class_attr(reinterpret_cast<const void*>(k_predict_bnn_class<CP>), SLOT)) return rc;        \
-    hipLaunchKernelGGL(k_predict_bnn_class<CP>, dim3((unsigned)pl.row_tiles, (unsigned)pl.slices), dim3(256), lds_bytes,  \
-                       s, theta, (int)n, (int)d, F, H, C, c, output, ld, ps, X, labels, (int)batch, pl.per, pred, part,   \
-                       lpd ? 1 : 0);                                                                                      \
+    if (head) PC_LAUNCH_AS(CP, true, 4 + SLOT);                                                                          \
+    else PC_LAUNCH_AS(CP, false, SLOT);                                                                                  \
   } while (0)
   if (C <= 4) PC_LAUNCH(4, 0);
   else if (C <= 8) PC_LAUNCH(8, 1);
   else if (C <= 16) PC_LAUNCH(16, 2);
   else PC_LAUNCH(32, 3);
 #undef PC_LAUNCH
+#undef PC_LAUNCH_AS
   LAUNCH_CHECK("k_predict_bnn_class");
   if (!summary) return STEIN_OK;
-  hipLaunchKernelGGL(k_predict_bnn_class_finish, dim3((unsigned)((batch + PCF_ROWS - 1) / PCF_ROWS)), dim3(256), 0, s, part,
-                     pl.slices, (int)n, (int)batch, C, prob, lpd, ent, label);
+  const dim3 grid((unsigned)((batch + PCF_ROWS - 1) / PCF_ROWS));
+  if (head) hipLaunchKernelGGL(k_predict_bnn_class_finish<true>, grid, dim3(256), 0, s, part, pl.slices, (int)n, (int)batch, C, prob, lpd, ent, label, head);
+  else hipLaunchKernelGGL(k_predict_bnn_class_finish<false>, grid, dim3(256), 0, s, part, pl.slices, (int)n, (int)batch, C, prob, lpd, ent, label, head);
   LAUNCH_CHECK("k_predict_bnn_class_finish");
   return STEIN_OK;
+}
+
+extern "C" int stein_predict_bnn_class(const float* theta, int64_t n, int64_t d, int output, int64_t n_in, int64_t n_hidden,
+                                       int64_t n_classes, const int64_t* cols, const float* X, const int32_t* labels,
+                                       int64_t batch, float* pred, float* prob, float* lpd, float* ent, int32_t* label,
+                                       void* workspace, size_t ws_bytes, void* stream) {
+  return predict_bnn_class(theta, n, d, output, n_in, n_hidden, n_classes, cols, X, labels, batch, pred, prob, lpd, ent, label,
+                           workspace, ws_bytes, stream, PredWeights{false, nullptr, nullptr});
+}
+
+extern "C" int stein_predict_bnn_class_weighted(const float* theta, int64_t n, int64_t d, int output, int64_t n_in,
+                                                int64_t n_hidden, int64_t n_classes, const int64_t* cols, const float* X,
+                                                const int32_t* labels, int64_t batch, const double* weights, float* pred,
+                                                float* prob, float* lpd, float* ent, int32_t* label, double* ess,
+                                                void* workspace, size_t ws_bytes, void* stream) {
+  return predict_bnn_class(theta, n, d, output, n_in, n_hidden, n_classes, cols, X, labels, batch, pred, prob, lpd, ent, label,
+                           workspace, ws_bytes, stream, PredWeights{true, weights, ess});
 }

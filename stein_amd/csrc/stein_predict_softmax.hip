@@ -17,20 +17,41 @@
 // stride C.  The running state is C + 2 fp32 sums per lane (the class probabilities, p at the true label, the entropy): all
 // terms are non-negative, so a plain sum per slice.  k_predict_softmax_finish merges the slices in slice order in fp64.  No
 // atomics; every workspace word that is read was written by the same call.
+//
+// Weighted form (stein_predict_softmax_weighted; the WEIGHTED instantiations): per-particle weights w_p >= 0 in fp64, W their
+// sum, prob_bc = sum_p w_p p_pbc / W and so on (include/steinhip.h).  The weight pass of stein_predict.hip
+// (predict_weight_pass) leaves W at the head of the workspace; the kernel stages the lane weights fl32(w_p / W) of PS_WB
+// particles at a time behind the staged model weights -- one fp64 quotient per particle and workgroup, taken by the thread
+// that stages it -- and every lane reads them at one address.  The running sums become acc = fmaf(w, q, acc), particles
+// ascending; a particle of lane weight zero skips its softmax tail unless pred wants it, and without pred a pass whose
+// particles all have lane weight zero is neither staged nor computed (one branch for the whole workgroup: the weights come
+// from LDS at one address).  The lane weights sum to 1, so the finish divides by nothing.
 #include "stein_predict_fwd.h"
 
 constexpr int PS_C_MIN = 2, PS_C_MAX = 32, PS_FC_MAX = 16384;
+constexpr int PS_WB = 64;   // WEIGHTED: particles whose lane weights are staged at a time (a multiple of every PP)
 
-template <int CP>
+// a value every lane holds alike, as the scalar the branches on it want
+__device__ __forceinline__ float ps_uniform(float v) {
+  return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
+}
+
+// WEIGHTED: wts [n] the weights, head the weight pass's header (head[0] = W)
+template <int CP, bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_predict_softmax(const float* __restrict__ theta, int n, int d, int w_col, int F, int C,
                                                          int output, int fc, int ld, const float* __restrict__ X,
                                                          const int* __restrict__ labels, int B, int per,
-                                                         float* __restrict__ pred, float* __restrict__ part, int want_lpd) {
+                                                         float* __restrict__ pred, float* __restrict__ part, int want_lpd,
+                                                         const double* __restrict__ wts,
+                                                         const double* __restrict__ head) {
   constexpr int NA = CP > PR_PASS ? CP : PR_PASS;   // staged columns of a pass
   constexpr int PP = NA / CP;                       // its particles
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* xs = lds;                                  // [PR_ROWS][ld]
   float* ws = lds + ((PR_ROWS * ld + 3) & ~3);      // [fc][NA]
+  [[maybe_unused]] float* wl = ws + fc * NA;        // [PS_WB], WEIGHTED only
+  [[maybe_unused]] double wtot = 0.0;
+  if constexpr (WEIGHTED) wtot = head[0];
   const int t = threadIdx.x;
   const int row0 = blockIdx.x * PR_ROWS, row = row0 + t;
   const bool live = row < B;
@@ -49,6 +70,19 @@ __global__ __launch_bounds__(256) void k_predict_softmax(const float* __restrict
   for (int c = 0; c < CP; ++c) acc[c] = 0.f;
   for (int p0 = p_begin; p0 < p_end; p0 += PP) {
     const int cnt = min(PP, p_end - p0);
+    [[maybe_unused]] int wo = 0;                    // the pass's place in wl
+    if constexpr (WEIGHTED) {
+      wo = (p0 - p_begin) % PS_WB;
+      if (wo == 0) {
+        __syncthreads();   // every lane is past its last read of wl
+        if (t < PS_WB) wl[t] = p0 + t < p_end ? pred_norm_weight(wts[p0 + t], wtot) : 0.f;
+        __syncthreads();
+      }
+      bool any = false;
+#pragma unroll
+      for (int pk = 0; pk < PP; ++pk) any = any || ps_uniform(wl[wo + pk]) != 0.f;
+      if (!pred && !any) continue;   // a dead pass: nothing of it is staged or computed
+    }
     float z[NA];
 #pragma unroll
     for (int k = 0; k < NA; ++k) z[k] = 0.f;
@@ -78,7 +112,9 @@ __global__ __launch_bounds__(256) void k_predict_softmax(const float* __restrict
     }
 #pragma unroll
     for (int pk = 0; pk < PP; ++pk) {
-      if (pk < cnt) {    // a particle past the slice's end is no particle
+      [[maybe_unused]] float wv = 0.f;
+      if constexpr (WEIGHTED) wv = ps_uniform(wl[wo + pk]);
+      if (pk < cnt && (!WEIGHTED || pred || wv != 0.f)) {    // a particle past the slice's end is no particle
         float* out = (pred && live) ? pred + ((size_t)(p0 + pk) * B + row) * C : nullptr;
         float m = z[pk * CP];
 #pragma unroll
@@ -101,12 +137,23 @@ __global__ __launch_bounds__(256) void k_predict_softmax(const float* __restrict
         for (int c = 0; c < CP; ++c) {
           const float pc = e[c] / s;
           if (out && output != STEIN_PRED_LINK && c < C) out[c] = pc;
-          acc[c] += pc;
+          if constexpr (WEIGHTED) {
+            if (wv != 0.f) acc[c] = fmaf(wv, pc, acc[c]);
+          } else {
+            acc[c] += pc;
+          }
           pt = fmaf(pc, z[pk * CP + c], pt);
           py = (c == yb && c < C) ? pc : py;   // (a label in [C, CP) is no class: py stays NaN)
         }
-        acc_y += py;
-        acc_h += logf(s) - pt;
+        if constexpr (WEIGHTED) {
+          if (wv != 0.f) {   // (weight zero: the particle enters no sum, whatever its probabilities are)
+            acc_y = fmaf(wv, py, acc_y);
+            acc_h = fmaf(wv, logf(s) - pt, acc_h);
+          }
+        } else {
+          acc_y += py;
+          acc_h += logf(s) - pt;
+        }
       }
     }
   }
@@ -122,13 +169,18 @@ __global__ __launch_bounds__(256) void k_predict_softmax(const float* __restrict
 
 // The slices' sums merged in slice order, in fp64: PSF_ROWS rows per workgroup, the C + 2 quantities of a row over eight
 // threads; then one thread per row takes the argmax of the floats prob received (through LDS; written whether or not prob
-// is wanted).
+// is wanted).  WEIGHTED: the lane weights sum to 1, so nothing is divided; bad weights (the header's W is NaN) give NaN rows
+// and the label -1.
 constexpr int PSF_ROWS = 32;
 
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_predict_softmax_finish(const float* __restrict__ part, int slices, int n, int B, int C,
                                                                 float* __restrict__ prob, float* __restrict__ lpd,
-                                                                float* __restrict__ ent, int* __restrict__ label) {
+                                                                float* __restrict__ ent, int* __restrict__ label,
+                                                                const double* __restrict__ head) {
   __shared__ float pr[PSF_ROWS][PS_C_MAX + 1];
+  [[maybe_unused]] bool bad = false;
+  if constexpr (WEIGHTED) bad = !(head[0] > 0.0);   // a negative or non-finite weight, W = 0 or an overflowing W
   const int r = threadIdx.x % PSF_ROWS, ql = threadIdx.x / PSF_ROWS;
   const int b = blockIdx.x * PSF_ROWS + r;
   if (b < B) {
@@ -137,14 +189,19 @@ __global__ __launch_bounds__(256) void k_predict_softmax_finish(const float* __r
       const float* p = part + (size_t)q * B + b;
       double sum = 0.0;
       for (int s = 0; s < slices; ++s) sum += (double)p[(size_t)s * (C + 2) * B];
+      if constexpr (WEIGHTED) {
+        if (bad) sum = (double)NAN;
+      } else {
+        sum /= (double)n;
+      }
       if (q < C) {
-        const float v = (float)(sum / (double)n);
+        const float v = (float)sum;
         pr[r][q] = v;
         if (prob) prob[(size_t)b * C + q] = v;
       } else if (q == C) {
-        lpd[b] = (float)log(sum / (double)n);
+        lpd[b] = (float)log(sum);
       } else {
-        ent[b] = (float)(sum / (double)n);
+        ent[b] = (float)sum;
       }
     }
   }
@@ -157,6 +214,7 @@ __global__ __launch_bounds__(256) void k_predict_softmax_finish(const float* __r
         top = pr[r][c];
         best = c;
       }
+    if constexpr (WEIGHTED) best = bad ? -1 : best;
     label[b] = best;
   }
 }
@@ -182,7 +240,7 @@ static int predict_softmax_domain(int64_t n_feats, int64_t n_classes) {
 
 // the 32-class kernel takes 66 KB of dynamic LDS at 58 features and more: raise each kernel's limit once per device
 static int predict_softmax_attr(const void* fn, int slot) {
-  static bool attr_set[4][64] = {{false}};
+  static bool attr_set[8][64] = {{false}};
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
   if (dev < 0 || dev >= 64 || !attr_set[slot][dev]) {
@@ -192,22 +250,39 @@ static int predict_softmax_attr(const void* fn, int slot) {
   return STEIN_OK;
 }
 
-extern "C" int stein_predict_softmax_workspace_bytes(int64_t n, int64_t batch, int64_t n_classes, size_t* out_bytes) {
+// the workspace of a weighted call: the weight pass's header of the slice bound ahead of the states; monotone too
+static size_t predict_softmax_wws_bytes(int64_t n, int64_t batch, int64_t n_classes) {
+  int64_t s = (n + PR_PASS - 1) / PR_PASS;
+  if (s > PR_SLICE_CAP) s = PR_SLICE_CAP;
+  return pw_doubles(s) * sizeof(double) + predict_softmax_ws_bytes(n, batch, n_classes);
+}
+
+static int predict_softmax_ws_check(int64_t n, int64_t batch, int64_t n_classes, size_t* out_bytes, bool weighted) {
   if (!out_bytes) return stein_fail(STEIN_E_BADARG, "NULL pointer");
   if (n < 1 || batch < 1 || n_classes < 1 || n > PR_COUNT_MAX || batch > PR_COUNT_MAX)
     return stein_fail(STEIN_E_SHAPE, "bad shape n=%lld batch=%lld C=%lld", (long long)n, (long long)batch, (long long)n_classes);
   if (int rc = predict_softmax_domain(1, n_classes)) return rc;
-  *out_bytes = predict_softmax_ws_bytes(n, batch, n_classes);
+  *out_bytes = weighted ? predict_softmax_wws_bytes(n, batch, n_classes) : predict_softmax_ws_bytes(n, batch, n_classes);
   return STEIN_OK;
 }
 
-extern "C" int stein_predict_softmax(const float* theta, int64_t n, int64_t d, int output, int64_t w_col, int64_t n_feats,
-                                     int64_t n_classes, const float* X, const int32_t* labels, int64_t batch, float* pred,
-                                     float* prob, float* lpd, float* ent, int32_t* label, void* workspace, size_t ws_bytes,
-                                     void* stream) {
-  if (!theta || !X) return stein_fail(STEIN_E_BADARG, "NULL pointer");
-  if (!pred && !prob && !lpd && !ent && !label)
-    return stein_fail(STEIN_E_BADARG, "no output requested: pred, prob, lpd, ent and label are all NULL");
+extern "C" int stein_predict_softmax_workspace_bytes(int64_t n, int64_t batch, int64_t n_classes, size_t* out_bytes) {
+  return predict_softmax_ws_check(n, batch, n_classes, out_bytes, false);
+}
+
+extern "C" int stein_predict_softmax_weighted_workspace_bytes(int64_t n, int64_t batch, int64_t n_classes, size_t* out_bytes) {
+  return predict_softmax_ws_check(n, batch, n_classes, out_bytes, true);
+}
+
+// both entry points (pw.on = false: the unweighted call, for which every check and launch is what it was)
+static int predict_softmax(const float* theta, int64_t n, int64_t d, int output, int64_t w_col, int64_t n_feats,
+                           int64_t n_classes, const float* X, const int32_t* labels, int64_t batch, float* pred, float* prob,
+                           float* lpd, float* ent, int32_t* label, void* workspace, size_t ws_bytes, void* stream,
+                           const PredWeights& pw) {
+  if (!theta || !X || (pw.on && !pw.w)) return stein_fail(STEIN_E_BADARG, "NULL pointer");
+  if (!pred && !prob && !lpd && !ent && !label && !pw.ess)
+    return stein_fail(STEIN_E_BADARG, pw.on ? "no output requested: pred, prob, lpd, ent, label and ess are all NULL"
+                                            : "no output requested: pred, prob, lpd, ent and label are all NULL");
   if (lpd && !labels) return stein_fail(STEIN_E_BADARG, "lpd needs labels");
   if (output != STEIN_PRED_LINK && output != STEIN_PRED_MEAN) return stein_fail(STEIN_E_BADARG, "output %d", output);
   if (n < 1 || d < 1 || batch < 1 || n_feats < 1 || n_classes < 1 || n > PR_COUNT_MAX || d > 0x7fffffffl || batch > PR_COUNT_MAX)
@@ -217,35 +292,68 @@ extern "C" int stein_predict_softmax(const float* theta, int64_t n, int64_t d, i
   if (w_col < 0 || w_col + n_feats * n_classes > d)
     return stein_fail(STEIN_E_SHAPE, "weights [%lld, %lld) do not fit d=%lld", (long long)w_col,
                       (long long)(w_col + n_feats * n_classes), (long long)d);
-  const bool summary = prob || lpd || ent || label;
-  if (summary) {
+  const bool summary = prob || lpd || ent || label;   // the rows the forward kernel reduces; ess comes from the weight pass alone
+  if (summary || pw.ess) {
     if (!workspace)
-      return stein_fail(STEIN_E_WORKSPACE, "prob, lpd, ent and label need a workspace (stein_predict_softmax_workspace_bytes)");
-    const size_t need = predict_softmax_ws_bytes(n, batch, n_classes);
+      return stein_fail(STEIN_E_WORKSPACE,
+                        pw.on ? "prob, lpd, ent, label and ess need a workspace (stein_predict_softmax_weighted_workspace_bytes)"
+                              : "prob, lpd, ent and label need a workspace (stein_predict_softmax_workspace_bytes)");
+    const size_t need = pw.on ? predict_softmax_wws_bytes(n, batch, n_classes) : predict_softmax_ws_bytes(n, batch, n_classes);
     if (ws_bytes < need) return stein_fail(STEIN_E_WORKSPACE, "workspace too small: %zu < %zu bytes", ws_bytes, need);
+    if (pw.on && (uintptr_t)workspace % sizeof(double))
+      return stein_fail(STEIN_E_WORKSPACE, "the workspace of a weighted call must be 8-byte aligned");
   }
   const PredPlan pl = predict_plan(n, batch);
   const int C = (int)n_classes, na = C > PR_PASS ? 32 : PR_PASS;
   const int fc = (int)(n_feats <= PR_FC ? n_feats : PR_FC), ld = fc | 1;
-  const size_t lds_bytes = ((size_t)((PR_ROWS * ld + 3) & ~3) + (size_t)fc * na) * sizeof(float);
-  float* part = summary ? (float*)workspace : nullptr;
   hipStream_t s = (hipStream_t)stream;
+  if (pw.on && (summary || pw.ess))
+    if (int rc = predict_weight_pass(pl, n, pw, workspace, s)) return rc;
+  if (!pred && !summary) return STEIN_OK;   // ess alone
+  // a weighted call that only asks for pred runs the unweighted kernel: pred does not depend on the weights
+  const double* head = (pw.on && summary) ? (const double*)workspace : nullptr;
+  float* part = !summary ? nullptr : head ? (float*)((double*)workspace + pw_doubles(pl.slices)) : (float*)workspace;
+  const size_t lds_bytes = ((size_t)((PR_ROWS * ld + 3) & ~3) + (size_t)fc * na + (head ? PS_WB : 0)) * sizeof(float);
+#define PS_LAUNCH_AS(CP, WEIGHTED, SLOT)                                                                                 \
+  do {                                                                                                                   \
+    if (int rc = predict_softmax_attr(reinterpret_cast<const void*>(k_predict_softmax<CP, WEIGHTED>), SLOT)) return rc;  \
+    hipLaunchKernelGGL((k_predict_softmax<CP, WEIGHTED>), dim3((unsigned)pl.row_tiles, (unsigned)pl.slices), dim3(256),   \
+                       lds_bytes, s, theta, (int)n, (int)d, (int)w_col, (int)n_feats, C, output, fc, ld, X, labels,       \
+                       (int)batch, pl.per, pred, part, lpd ? 1 : 0, pw.w, head);                                          \
+  } while (0)
 #define PS_LAUNCH(CP, SLOT)                                                                                              \
   do {                                                                                                                   \
-    if (int rc = predict_softmax_attr(reinterpret_cast<const void*>(k_predict_softmax<CP>), SLOT)) return rc;            \
-    hipLaunchKernelGGL(k_predict_softmax<CP>, dim3((unsigned)pl.row_tiles, (unsigned)pl.slices), dim3(256), lds_bytes, s, \
-                       theta, (int)n, (int)d, (int)w_col, (int)n_feats, C, output, fc, ld, X, labels, (int)batch, pl.per, \
-                       pred, part, lpd ? 1 : 0);                                                                          \
+    if (head) PS_LAUNCH_AS(CP, true, 4 + SLOT);                                                                          \
+    else PS_LAUNCH_AS(CP, false, SLOT);                                                                                  \
   } while (0)
   if (C <= 4) PS_LAUNCH(4, 0);
   else if (C <= 8) PS_LAUNCH(8, 1);
   else if (C <= 16) PS_LAUNCH(16, 2);
   else PS_LAUNCH(32, 3);
 #undef PS_LAUNCH
+#undef PS_LAUNCH_AS
   LAUNCH_CHECK("k_predict_softmax");
   if (!summary) return STEIN_OK;
-  hipLaunchKernelGGL(k_predict_softmax_finish, dim3((unsigned)((batch + PSF_ROWS - 1) / PSF_ROWS)), dim3(256), 0, s, part,
-                     pl.slices, (int)n, (int)batch, C, prob, lpd, ent, label);
+  const dim3 grid((unsigned)((batch + PSF_ROWS - 1) / PSF_ROWS));
+  if (head) hipLaunchKernelGGL(k_predict_softmax_finish<true>, grid, dim3(256), 0, s, part, pl.slices, (int)n, (int)batch, C, prob, lpd, ent, label, head);
+  else hipLaunchKernelGGL(k_predict_softmax_finish<false>, grid, dim3(256), 0, s, part, pl.slices, (int)n, (int)batch, C, prob, lpd, ent, label, head);
   LAUNCH_CHECK("k_predict_softmax_finish");
   return STEIN_OK;
+}
+
+extern "C" int stein_predict_softmax(const float* theta, int64_t n, int64_t d, int output, int64_t w_col, int64_t n_feats,
+                                     int64_t n_classes, const float* X, const int32_t* labels, int64_t batch, float* pred,
+                                     float* prob, float* lpd, float* ent, int32_t* label, void* workspace, size_t ws_bytes,
+                                     void* stream) {
+  return predict_softmax(theta, n, d, output, w_col, n_feats, n_classes, X, labels, batch, pred, prob, lpd, ent, label,
+                         workspace, ws_bytes, stream, PredWeights{false, nullptr, nullptr});
+}
+
+extern "C" int stein_predict_softmax_weighted(const float* theta, int64_t n, int64_t d, int output, int64_t w_col,
+                                              int64_t n_feats, int64_t n_classes, const float* X, const int32_t* labels,
+                                              int64_t batch, const double* weights, float* pred, float* prob, float* lpd,
+                                              float* ent, int32_t* label, double* ess, void* workspace, size_t ws_bytes,
+                                              void* stream) {
+  return predict_softmax(theta, n, d, output, w_col, n_feats, n_classes, X, labels, batch, pred, prob, lpd, ent, label,
+                         workspace, ws_bytes, stream, PredWeights{true, weights, ess});
 }

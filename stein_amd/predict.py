@@ -26,7 +26,8 @@ hand-written HIP kernels (csrc/stein_predict.hip) in two forms:
 ``SoftmaxPredict`` (csrc/stein_predict_softmax.hip) is the producer of the softmax regression model of
 ``stein_amd.scores.SoftmaxScore``: a vector of class probabilities per test point, so ``producer(theta_matrix, feed)`` is
 [n, batch, C] and its summaries -- class probabilities, label, expected entropy, log predictive density -- come from
-``producer.summary`` / ``sampler.predictive_classes``; the scalar-output methods above refuse it.  ``BnnClassPredict``
+``producer.summary`` / ``sampler.predictive_classes``, under per-particle weights from ``producer.weighted_summary`` /
+``sampler.predictive_classes(..., weights=w)``; the other scalar-output methods above refuse it.  ``BnnClassPredict``
 (csrc/stein_predict_bnn_class.hip) is the same producer for the network classifier of ``stein_amd.scores.BnnClassScore``.
 """
 import ctypes
@@ -471,18 +472,24 @@ class SoftmaxPredict(_Buffers):
     the posterior predictive class probabilities mean_p p_pbc, their argmax, the expected entropy mean_p H(p_pb.) and -- only
     when the feed has a "y" -- the log predictive density log(mean_p p_{pb,y_b}); device tensors, no [n, batch, C] formed.
     ``sampler.predictive_classes(producer, feed)`` hands them back as NumPy with the entropy of prob and the mutual
-    information.  The scalar-output methods of GlmPredict / BnnPredict (mean and variance, order statistics, quantiles, the
-    distribution of y) have no meaning for a vector of class probabilities and raise a ValueError.
+    information.
+    ``producer.weighted_summary(theta_matrix, feed, weights)`` -> the same dict under per-particle weights w_p >= 0 (Stein
+    importance weights, or the counts of a thinned sample): sum_p w_p (.) / W in the place of every mean, and "ess", the
+    weights' effective sample size (``sampler.predictive_classes(producer, feed, weights=w)``).
+    The scalar-output methods of GlmPredict / BnnPredict (order statistics, quantiles, the distribution of y) have no
+    meaning for a vector of class probabilities and raise a ValueError.
     """
     classes = True    # the samplers' scalar-output methods refuse this producer and name predictive_classes
     _workspace_bytes = staticmethod(_lib.predict_softmax_workspace_bytes)
+    _weighted_workspace_bytes = staticmethod(_lib.predict_softmax_weighted_workspace_bytes)
+    _weights = staticmethod(_Predict._weights)
 
     def __init__(self, n_feats, n_classes, w_col=0, output="mean"):
         if output not in _OUTPUTS:
             raise ValueError("output must be 'link' or 'mean'")
         self.output = _OUTPUTS[output]
         self.n_feats, self.n_classes, self.w_col = int(n_feats), int(n_classes), int(w_col)
-        self._ws = None
+        self._ws = self._wws = None
 
     def _inputs(self, theta, feed, want_y):
         X = feed["X"]
@@ -498,11 +505,13 @@ class SoftmaxPredict(_Buffers):
             y = _labels_i32(feed["y"], batch, theta.device)
         return X, y, batch
 
-    def _launch(self, theta, X, y, batch, pred, prob, lpd, ent, label, ws):
+    def _launch(self, theta, X, y, batch, pred, prob, lpd, ent, label, ws, weights=None, ess=None):
         n, d = theta.shape
         p = self._ptr
-        _lib.call_on(theta.device, "stein_predict_softmax", theta.data_ptr(), n, d, self.output, self.w_col, self.n_feats,
-                     self.n_classes, X.data_ptr(), p(y), batch, p(pred), p(prob), p(lpd), p(ent), p(label), p(ws),
+        name, w, e = ("stein_predict_softmax", (), ()) if weights is None else \
+            ("stein_predict_softmax_weighted", (weights.data_ptr(),), (ess.data_ptr(),))
+        _lib.call_on(theta.device, name, theta.data_ptr(), n, d, self.output, self.w_col, self.n_feats,
+                     self.n_classes, X.data_ptr(), p(y), batch, *w, p(pred), p(prob), p(lpd), p(ent), p(label), *e, p(ws),
                      0 if ws is None else ws.numel(), torch.cuda.current_stream(theta.device).cuda_stream)
 
     def __call__(self, theta, feed, out=None):
@@ -518,18 +527,42 @@ class SoftmaxPredict(_Buffers):
         self._launch(theta, X, None, batch, out, None, None, None, None, None)
         return out
 
-    def summary(self, theta, feed):
-        """-> {"prob", "label", "ent"} and, when `feed` has a "y", "lpd": device tensors (see the class)."""
-        want_y = feed.get("y") is not None
-        X, y, batch = self._inputs(theta, feed, want_y)
-        dev = theta.device
+    def _summary_outputs(self, batch, want_y, dev):
         out = {"prob": torch.empty(batch, self.n_classes, dtype=torch.float32, device=dev),
                "label": torch.empty(batch, dtype=torch.int32, device=dev),
                "ent": torch.empty(batch, dtype=torch.float32, device=dev)}
         if want_y:
             out["lpd"] = torch.empty(batch, dtype=torch.float32, device=dev)
+        return out
+
+    def summary(self, theta, feed):
+        """-> {"prob", "label", "ent"} and, when `feed` has a "y", "lpd": device tensors (see the class)."""
+        want_y = feed.get("y") is not None
+        X, y, batch = self._inputs(theta, feed, want_y)
+        dev = theta.device
+        out = self._summary_outputs(batch, want_y, dev)
         ws = self._buffer("_ws", self._workspace_bytes(theta.shape[0], batch, self.n_classes), dev)
         self._launch(theta, X, y, batch, None, out["prob"], out.get("lpd"), out["ent"], out["label"], ws)
+        return out
+
+    def weighted_summary(self, theta, feed, weights):
+        """-> {"prob", "label", "ent", "ess"} and, when `feed` has a "y", "lpd", under per-particle weights w_p >= 0 (Stein
+        importance weights, or the counts ``torch.bincount(idx, minlength=n)`` of a thinned sample; they need not sum to
+        1): prob_bc = sum_p w_p p_pbc / W, ent_b = sum_p w_p H(p_pb.) / W, lpd_b = log(sum_p w_p p_{pb,y_b} / W), label the
+        argmax of prob, ess = W^2 / sum_p w_p^2 as a 1-element float64 tensor; all device tensors.  `weights`: any
+        real-valued [n] tensor or NumPy array (an integer dtype is taken as counts); it is moved to the particles' device as
+        contiguous float64 and never read on the host, so a negative or non-finite weight (or W = 0) shows as NaN in every
+        row and in ess, and as the label -1.  Particles of weight zero are not computed: a thinned sample costs about what
+        its distinct particles cost."""
+        want_y = feed.get("y") is not None
+        X, y, batch = self._inputs(theta, feed, want_y)
+        n, dev = theta.shape[0], theta.device
+        w = self._weights(weights, n, dev)
+        out = self._summary_outputs(batch, want_y, dev)
+        out["ess"] = torch.empty(1, dtype=torch.float64, device=dev)
+        ws = self._buffer("_wws", self._weighted_workspace_bytes(n, batch, self.n_classes), dev)
+        self._launch(theta, X, y, batch, None, out["prob"], out.get("lpd"), out["ent"], out["label"], ws, weights=w,
+                     ess=out["ess"])
         return out
 
     def _scalar_only(self, *args, **kw):
@@ -537,7 +570,7 @@ class SoftmaxPredict(_Buffers):
                          "summaries come from sampler.predictive_classes(producer, feed) (or producer.summary)"
                          % type(self).__name__)
 
-    weighted_summary = order_statistics = quantiles = weighted_quantiles = y_cdf = y_quantiles = _scalar_only
+    order_statistics = quantiles = weighted_quantiles = y_cdf = y_quantiles = _scalar_only
 
 
 class BnnClassPredict(SoftmaxPredict):
@@ -549,9 +582,12 @@ class BnnClassPredict(SoftmaxPredict):
 
     The call forms, ``summary``'s dict and the refusals of the scalar-output methods are SoftmaxPredict's:
     ``producer(theta_matrix, feed)`` -> [n, batch, n_classes]; ``producer.summary(theta_matrix, feed)`` -> {"prob", "label",
-    "ent"} and, with a "y" in the feed, "lpd"; ``sampler.predictive_classes(producer, feed)`` hands them back as NumPy.
+    "ent"} and, with a "y" in the feed, "lpd"; ``producer.weighted_summary(theta_matrix, feed, weights)`` -> the same
+    under per-particle weights, with "ess"; ``sampler.predictive_classes(producer, feed, weights=None)`` hands them back as
+    NumPy.
     """
     _workspace_bytes = staticmethod(_lib.predict_bnn_class_workspace_bytes)
+    _weighted_workspace_bytes = staticmethod(_lib.predict_bnn_class_weighted_workspace_bytes)
 
     def __init__(self, n_in, n_hidden, n_classes, cols, output="mean"):
         if output not in _OUTPUTS:
@@ -563,11 +599,13 @@ class BnnClassPredict(SoftmaxPredict):
         if len(cols) != 4:
             raise ValueError("cols must give the first column of w1, b1, w2 and b2")
         self._cols = (ctypes.c_int64 * 5)(*([int(c) for c in cols] + [-1]))
-        self._ws = None
+        self._ws = self._wws = None
 
-    def _launch(self, theta, X, y, batch, pred, prob, lpd, ent, label, ws):
+    def _launch(self, theta, X, y, batch, pred, prob, lpd, ent, label, ws, weights=None, ess=None):
         n, d = theta.shape
         p = self._ptr
-        _lib.call_on(theta.device, "stein_predict_bnn_class", theta.data_ptr(), n, d, self.output, self.n_in, self.n_hidden,
-                     self.n_classes, self._cols, X.data_ptr(), p(y), batch, p(pred), p(prob), p(lpd), p(ent), p(label), p(ws),
-                     0 if ws is None else ws.numel(), torch.cuda.current_stream(theta.device).cuda_stream)
+        name, w, e = ("stein_predict_bnn_class", (), ()) if weights is None else \
+            ("stein_predict_bnn_class_weighted", (weights.data_ptr(),), (ess.data_ptr(),))
+        _lib.call_on(theta.device, name, theta.data_ptr(), n, d, self.output, self.n_in, self.n_hidden,
+                     self.n_classes, self._cols, X.data_ptr(), p(y), batch, *w, p(pred), p(prob), p(lpd), p(ent), p(label), *e,
+                     p(ws), 0 if ws is None else ws.numel(), torch.cuda.current_stream(theta.device).cuda_stream)

@@ -346,14 +346,20 @@ class AbstractSteinSampler:
             out["ess"] = float(ess.item())
         return out
 
-    def predictive_classes(self, producer, feed):
+    def predictive_classes(self, producer, feed, weights=None):
         """Per-test-point summaries of a class-probability producer (stein_amd.predict.SoftmaxPredict) under the current
         particles, NumPy arrays: "prob" [batch, C], the posterior predictive class probabilities mean_p p_pbc; "label"
         [batch] int32, their argmax (ties to the lowest class); "entropy" [batch], H(prob_b.), the total predictive
         uncertainty; "mutual_information" [batch], entropy minus the expected entropy mean_p H(p_pb.), clipped at 0 -- the
         part of the uncertainty that comes from the particles disagreeing, large far from the training data; and, when
         `feed` has a "y", "lpd" [batch] = log(mean_p p_{pb,y_b}).  The [n, batch, C] tensor that function_posterior returns
-        is never formed.  One rank only."""
+        is never formed.  One rank only.
+
+        weights ([n], w_p >= 0: ``importance_weights(...)``, or the integer counts ``torch.bincount(thin(m), minlength=n)``):
+        every mean over the particles becomes the weighted mean sum_p w_p (.) / W (``producer.weighted_summary``), the
+        entropy and the mutual information are taken of the weighted prob as before, and "ess" (float), the weights'
+        effective sample size W^2 / sum_p w_p^2, joins the dict.  The weights are never read on the host: bad ones (negative,
+        non-finite, all zero) give NaN rows, NaN "ess" and the label -1."""
         if self._group is not None:
             raise ValueError("predictive_classes works on one rank only: a sharded sampler would have to merge the ranks' "
                              "sums; use function_posterior, which gathers the outputs")
@@ -361,7 +367,10 @@ class AbstractSteinSampler:
             raise ValueError("predictive_classes needs a class-probability producer (SoftmaxPredict); GlmPredict and "
                              "BnnPredict go to posterior_predictive")
         with torch.no_grad():
-            s = producer.summary(self._matrix_f32(), feed)
+            if weights is None:
+                s = producer.summary(self._matrix_f32(), feed)
+            else:
+                s = producer.weighted_summary(self._matrix_f32(), feed, weights)
         prob = s["prob"].cpu().numpy()
         p64 = prob.astype(np.float64)
         entropy = -(p64 * np.log(np.where(p64 > 0, p64, 1.0))).sum(-1)
@@ -369,6 +378,8 @@ class AbstractSteinSampler:
         out["mutual_information"] = np.maximum(out["entropy"] - s["ent"].cpu().numpy(), np.float32(0))
         if "lpd" in s:
             out["lpd"] = s["lpd"].cpu().numpy()
+        if weights is not None:
+            out["ess"] = float(s["ess"].item())
         return out
 
     def predictive_quantiles(self, producer, feed, q, weights=None):
